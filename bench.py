@@ -1,25 +1,30 @@
 #!/usr/bin/env python3
 """Training-throughput benchmark (BASELINE.json metric) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model unet|stf] ...
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model unet|stf] [--dump-outputs DIR] [--full] ...
 
 Default workload = BASELINE.json configs[1]: 2-D UNet(in=8, base_c=64), 256x256
 DCE frames, batch 64 per GPU, bf16 compute (fp32 master weights / statistics),
 one step = forward + CE+Dice criterion + backward (+ RCCL gradient all-reduce
 when N > 1, or at N = 1 with --hook) + AdamW + LambdaLR step + the host's read of
 the loss, exactly train_one_epoch's step (train_utils/train_and_eval.py:384-409:
-``metric_logger.update(loss=loss.item(), ...)`` syncs the host once per step).  The
-same K steps without the per-step loss read are timed as well and reported beside
-the headline (``no_step_sync``).  Inputs are synthetic seeded DCE stacks
-already resident in HBM.  For N > 1 the driver launches one process per GPU via
+``metric_logger.update(loss=loss.item(), ...)`` syncs the host once per step).
+Inputs are synthetic seeded DCE stacks already resident in HBM, identical from run
+to run for the same arguments.  For N > 1 the driver launches one process per GPU via
 torch.distributed.run; every rank keeps its own batch (weak scaling) and the
 timed region is bracketed by barrier + synchronize, max over ranks.
 
-Prints ONE JSON line (rank 0) with the metric, the roofline of the dominant
-kernel family (stf_igemm, timed with HIP events on its launch stream inside the
-timed region) and the CPU baseline (the fp32 oracle restatement timed on this
-host's cores on a bounded sample: the cpu_baseline leg is the only place bench.py
-touches oracle/).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and
+prints the metric (``value``, ``ms_per_step``) and what follows from it by arithmetic
+(model FLOP/s).  ``--dump-outputs DIR`` also writes what the last timed step returned
+(its loss and logits, and a fixed seeded sample of the parameters it updated) as
+``DIR/<name>.npy``.  Everything that takes runs or instrumentation of its own is behind
+``--full``: the same K steps without the per-step loss read (``no_step_sync``), the
+roofline of the dominant kernel family (stf_igemm, timed with HIP events on its launch
+stream: a census in the last warm-up step and that kernel's launches in the last timed
+step), the per-DoubleConv MFMA report, the trained-weight Dice leg and the CPU baseline
+(the fp32 oracle restatement timed on this host's cores on a bounded sample: the
+cpu_baseline leg is the only place bench.py touches oracle/).
 """
 import argparse
 import json
@@ -57,10 +62,17 @@ def parse():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp16"],
                     help="16-bit activation storage; fp16 = the reference's --amp step (autocast float16 + "
                          "GradScaler, train_and_eval.py:389-404) on the fp16 library")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (float32): "
+                         "loss, logits, params_sample (a fixed seeded sample of the updated parameters)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline: no_step_sync, kernel census + roofline + "
+                         "DoubleConv report, Dice vs reference, CPU baseline (each has a --no-... switch)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--cpu-steps", type=int, default=3)
-    ap.add_argument("--no-kernel-timer", action="store_true")
-    ap.add_argument("--no-dice", action="store_true", help="skip the trained-weight Dice-vs-reference leg")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="--full without the kernel census / roofline")
+    ap.add_argument("--no-dice", action="store_true",
+                    help="--full without the trained-weight Dice-vs-reference leg")
     ap.add_argument("--hook", action="store_true",
                     help="N = 1: form a world-1 RCCL group and attach the data-parallel gradient hook "
                          "(stfunet.ddp.GradAllReduce), i.e. time the per-GPU half of the DP step")
@@ -77,6 +89,8 @@ def parse():
         for k, v in presets[a.config].items():
             if k != "batch" or a.batch is None:          # an explicit --batch wins
                 setattr(a, k, v)
+    if not a.full:          # a plain run: the headline alone
+        a.no_cpu_baseline = a.no_kernel_timer = a.no_dice = True
     return a
 
 
@@ -395,11 +409,16 @@ def main():
                          pk_channels=3 if args.pk else 0, mask_hw=half) for i in range(2)]
     batches = [(engine.preprocess_input(x, model), t) for x, t in batches]
 
+    last_out = {}           # --dump-outputs: the most recent step's model output
+
     def train_step(i):
         # train_one_epoch's step (train_and_eval.py:384-409); fp16 = its --amp branch
         x, t = batches[i % len(batches)]
         with torch.amp.autocast(device_type="cuda", enabled=fp16):
-            loss = engine.criterion(model(x), t)
+            out = model(x)
+            loss = engine.criterion(out, t)
+        if args.dump_outputs:
+            last_out["out"] = out["out"]
         opt.zero_grad()
         if scaler is not None:
             scaler.scale(loss).backward()
@@ -466,9 +485,9 @@ def main():
             el = float(e.item())
         return el, loss
 
-    # the same K steps twice: without the per-step host read of the loss, then (the headline)
-    # with it, as the reference's loop does
-    elapsed_nosync, _ = timed(False, False)
+    # the headline: K steps with the per-step host read of the loss, as the reference's loop does;
+    # --full times the same K steps without it first
+    elapsed_nosync = timed(False, False)[0] if args.full else None
     elapsed, loss = timed(True, True)
     kt = nhwc.TIMER.summary() if nhwc.TIMER is not None else {}
     nhwc.TIMER = None
@@ -479,6 +498,8 @@ def main():
             kt = {dominant: dict(launches=n, ms=ms, flops=fl, avg_us=1e3 * ms / n,
                                  tflops=fl / (ms * 1e-3) / 1e12 if ms > 0 else 0.0)}
     last_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, last_out["out"], model)
 
     samples = args.batch * world * args.steps
     value = samples / elapsed
@@ -510,9 +531,10 @@ def main():
             "step": "train_one_epoch's step incl. the per-step host read loss.item() (train_and_eval.py:409)"
                     + (" + the data-parallel gradient hook (world-1 RCCL group)" if (args.hook and world == 1)
                        else (" + RCCL gradient all-reduce" if world > 1 else "")),
-            "no_step_sync": {"value": round(samples / elapsed_nosync, 3),
-                             "ms_per_step": round(1e3 * elapsed_nosync / args.steps, 3),
-                             "note": "same steps, the host reads the loss only after the last one"},
+            **({"no_step_sync": {"value": round(samples / elapsed_nosync, 3),
+                                 "ms_per_step": round(1e3 * elapsed_nosync / args.steps, 3),
+                                 "note": "same steps, the host reads the loss only after the last one"}}
+               if args.full else {}),
             "execution": "native_plan" if runtime.fwd is not None else "eager",
             "config": {"workload": workload,
                        "model": "UNet" if args.model == "unet" else "STFLSTMUNet",
@@ -523,10 +545,12 @@ def main():
             "train_gflop_per_sample": round(train_gflop, 2),
             "model_tflops_per_gpu": round(value / world * train_gflop / 1e3, 2),
             "model_mfu": round(value / world * train_gflop / 1e3 / MFMA_BF16_PEAK_TFLOPS, 4),
-            "roofline": roof,
-            "doubleconv": doubleconv_report(blocks),
-            "kernels_census_step": {k: {kk: (round(vv, 3) if isinstance(vv, float) else vv) for kk, vv in d.items()}
-                                    for k, d in census.items()},
+            **({"roofline": roof,
+                "doubleconv": doubleconv_report(blocks),
+                "kernels_census_step": {k: {kk: (round(vv, 3) if isinstance(vv, float) else vv)
+                                            for kk, vv in d.items()} for k, d in census.items()}}
+               if args.full else {}),
+            "full": args.full,
             "last_loss": round(last_loss, 5),
             "build": _build_record(),
         }
@@ -546,7 +570,7 @@ def main():
     if prog is not None:
         prog.grad_ready_hook = None
         prog.runtime.close()
-    del ddp, prog, runtime, model, opt, sched, batches, loss
+    del ddp, prog, runtime, model, opt, sched, batches, loss, last_out
     plan.drain_pools()
     import gc
     gc.collect()
@@ -555,6 +579,36 @@ def main():
     if dist_on:
         dist.barrier()
         dist.destroy_process_group()
+
+
+PARAM_SAMPLE = 1 << 20          # parameters written by --dump-outputs (4 MiB as float32)
+DUMP_CAP_BYTES = 48 << 20       # per array; with the parameter sample the dump stays under 64 MB
+
+
+def _seeded_sample(flat, n, seed):
+    """``n`` elements of the 1-D tensor ``flat`` at fixed positions (seeded, ascending); all of it
+    if it has no more than ``n``."""
+    if flat.numel() <= n:
+        return flat
+    g = torch.Generator().manual_seed(seed)
+    idx = torch.randperm(flat.numel(), generator=g)[:n].sort().values
+    return flat[idx.to(flat.device)]
+
+
+def dump_outputs(path, loss, logits, model):
+    """What a caller of the timed step holds after its last call, as float32 ``.npy`` files: the
+    loss it returned, the logits the model returned (a fixed seeded sample of them if they
+    exceed DUMP_CAP_BYTES) and a fixed seeded sample of the parameters the step updated."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    logits = logits.detach().float()
+    if logits.numel() * 4 > DUMP_CAP_BYTES:
+        logits = _seeded_sample(logits.flatten(), DUMP_CAP_BYTES // 4, seed=11)
+    params = torch.cat([p.detach().float().flatten() for p in model.parameters()])
+    arrays = {"loss": loss.detach().float().reshape(1), "logits": logits,
+              "params_sample": _seeded_sample(params, PARAM_SAMPLE, seed=12)}
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy().astype(np.float32, copy=False))
 
 
 def _contend_proxy(spec, dev):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile collection (GPU box, repo root), all on ONE box so the numbers agree:
-#   1. the bench lines (python bench.py [--model stf], default steps)
+#   1. the bench lines (python bench.py --full [--model stf], default steps)
 #   2. rocprofv3 --kernel-trace --stats of the same workloads (per-kernel averages that
 #      the bench line's roofline avg_launch_us is checked against; without the dice / CPU
 #      legs, whose training steps would mix other shapes into the statistics)
@@ -13,18 +13,18 @@ root=$GRAFT_REPO_ROOT
 out=$root/gpurun_out/prof_$tag
 mkdir -p $out
 if [ -z "$ONLY_PMC" ]; then
-timeout -k 10 600 python3 bench.py > $out/bench_unet256_b64.json 2> $out/bench_unet.err
-timeout -k 10 600 python3 bench.py --model stf > $out/bench_stf256_t8_b16.json 2> $out/bench_stf.err
-timeout -k 10 600 python3 bench.py --config 4 --steps 20 --warmup 5 > $out/bench_cfg4_stf256_t16_b16.json 2> $out/bench_cfg4.err
-timeout -k 10 600 python3 bench.py --config 5 --steps 10 --warmup 3 > $out/bench_cfg5_stf512_t32pk_b4_fp16.json 2> $out/bench_cfg5.err
-timeout -k 10 600 python3 bench.py --dtype fp16 --no-cpu-baseline > $out/bench_unet256_b64_fp16.json 2> $out/bench_unet16.err
+timeout -k 10 600 python3 bench.py --full > $out/bench_unet256_b64.json 2> $out/bench_unet.err
+timeout -k 10 600 python3 bench.py --full --model stf > $out/bench_stf256_t8_b16.json 2> $out/bench_stf.err
+timeout -k 10 600 python3 bench.py --full --config 4 --steps 20 --warmup 5 > $out/bench_cfg4_stf256_t16_b16.json 2> $out/bench_cfg4.err
+timeout -k 10 600 python3 bench.py --full --config 5 --steps 10 --warmup 3 > $out/bench_cfg5_stf512_t32pk_b4_fp16.json 2> $out/bench_cfg5.err
+timeout -k 10 600 python3 bench.py --full --dtype fp16 --no-cpu-baseline > $out/bench_unet256_b64_fp16.json 2> $out/bench_unet16.err
 cd /tmp && export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/unet -o run -- \
-  python3 $root/bench.py --no-dice --no-cpu-baseline > $out/unet_rocprof_bench.json 2> $out/unet.log
+  python3 $root/bench.py --full --no-dice --no-cpu-baseline > $out/unet_rocprof_bench.json 2> $out/unet.log
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stf -o run -- \
-  python3 $root/bench.py --model stf --no-dice --no-cpu-baseline > $out/stf_rocprof_bench.json 2> $out/stf.log
+  python3 $root/bench.py --full --model stf --no-dice --no-cpu-baseline > $out/stf_rocprof_bench.json 2> $out/stf.log
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/cfg5 -o run -- \
-  python3 $root/bench.py --config 5 --steps 10 --warmup 3 --no-dice --no-cpu-baseline > $out/cfg5_rocprof_bench.json 2> $out/cfg5.log
+  python3 $root/bench.py --full --config 5 --steps 10 --warmup 3 --no-dice --no-cpu-baseline > $out/cfg5_rocprof_bench.json 2> $out/cfg5.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/pk -o run -- \
   python3 $root/tools/bench_pk.py > $out/bench_pk.json 2> $out/pk.log
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/aug -o run -- \
