@@ -314,6 +314,158 @@ __global__ void loss_bwd_kernel(const float* __restrict__ logits, const int64_t*
   }
 }
 
+// ------------------------------------------------------------------ loss with options
+// The same three kernels with class weights w (ones when absent), a pixel mask
+// m = (ignore >= 0 ? t != ignore : 1) and a Dice switch (stf_loss_opt_*):
+//   CE = sum m w[t] (-log p_t) / sum m w[t]        (torch's weighted mean with ignore_index)
+//   I, S as above over the pixels with m = 1 only; weights do not enter Dice
+//   loss = CE + (dice ? 1 - mean_k mean_b D : 0)
+// Backward: dz_k = go * [ m w[t] (p_k - [t=k]) / Wsum + m p_k (G_k - sum_j p_j G_j) ], G = 0 with
+// Dice off; an ignored pixel gets a stored 0.  w[t] is a sum of selects over k, never an indexed
+// read, so a target outside [0, K) that is not the ignore value reads nothing and weighs 0.
+// A batch with every pixel ignored has Wsum = 0 and the loss is 0/0 = NaN, as F.cross_entropy.
+template <int K>
+__global__ void loss_opt_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, int HW,
+                                    const float* __restrict__ cw, int ignore, float* __restrict__ part) {
+  // grid (LCHUNK, N): partial[n][chunk][3K + 2] = (I, sum p, sum t) per class, CE numerator, Wsum
+  constexpr int NV = 3 * K + 2;
+  __shared__ float red[NT / 64][NV];
+  const int n = blockIdx.y;
+  float w[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) w[k] = cw ? cw[k] : 1.f;
+  float s[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) s[i] = 0.f;
+  for (int hw = blockIdx.x * NT + threadIdx.x; hw < HW; hw += gridDim.x * NT) {
+    float z[K], e[K], mx = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { z[k] = logits[((long)n * K + k) * HW + hw]; mx = fmaxf(mx, z[k]); }
+    float se = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { e[k] = expf(z[k] - mx); se += e[k]; }
+    const int64_t t64 = target[(long)n * HW + hw];
+    const bool keep = !(ignore >= 0 && t64 == (int64_t)ignore);
+    const int t = (t64 >= 0 && t64 < K) ? (int)t64 : -1;
+    const float inv = 1.f / se, lse = logf(se);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float p = keep ? e[k] * inv : 0.f;
+      const float tk = t == k ? 1.f : 0.f;     // the ignore value is outside [0, K): tk = 0 there
+      s[3 * k] += p * tk;
+      s[3 * k + 1] += p;
+      s[3 * k + 2] += tk;
+      if (t == k) {
+        s[3 * K] += w[k] * (lse - (z[k] - mx));
+        s[3 * K + 1] += w[k];
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) s[i] = wave_sum(s[i]);
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int i = 0; i < NV; ++i) red[threadIdx.x >> 6][i] = s[i];
+  __syncthreads();
+  if (threadIdx.x < NV) {
+    float a = 0.f;
+    for (int wv = 0; wv < NT / 64; ++wv) a += red[wv][threadIdx.x];
+    part[((size_t)n * gridDim.x + blockIdx.x) * NV + threadIdx.x] = a;
+  }
+}
+
+template <int K>
+__global__ void loss_opt_finalize_kernel(const float* __restrict__ part, int N, int dice, float* __restrict__ terms,
+                                         float* __restrict__ loss) {
+  constexpr int NV = 3 * K + 2;
+  // one thread per (n, value), fixed summation order over chunks
+  __shared__ double acc[64][NV];
+  double ce = 0.0, wsum = 0.0, dsum = 0.0;
+  for (int base = 0; base < N; base += 64) {
+    const int n = base + (int)threadIdx.x;
+    if (threadIdx.x < 64) {
+      for (int i = 0; i < NV; ++i) {
+        double a = 0.0;
+        if (n < N)
+          for (int c = 0; c < LCHUNK; ++c) a += part[((size_t)n * LCHUNK + c) * NV + i];
+        acc[threadIdx.x][i] = a;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int r = 0; r < 64 && base + r < N; ++r) {
+        for (int k = 0; k < K; ++k) {
+          const double I = acc[r][3 * k], S = acc[r][3 * k + 1] + acc[r][3 * k + 2];
+          const float If = (float)I, Sf = (float)S;
+          const float setsum = Sf == 0.f ? 2.f * If : Sf;     // an image with every pixel ignored: D = 1
+          dsum += (double)((2.f * If + DICE_EPS) / (setsum + DICE_EPS));
+          terms[((size_t)(base + r) * K + k) * 3 + 0] = If;
+          terms[((size_t)(base + r) * K + k) * 3 + 1] = (float)acc[r][3 * k + 1];
+          terms[((size_t)(base + r) * K + k) * 3 + 2] = (float)acc[r][3 * k + 2];
+        }
+        ce += acc[r][3 * K];
+        wsum += acc[r][3 * K + 1];
+      }
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    terms[(size_t)N * K * 3] = (float)ce;
+    terms[(size_t)N * K * 3 + 1] = (float)wsum;
+    loss[0] = (float)(ce / wsum + (dice ? 1.0 - dsum / ((double)N * K) : 0.0));
+  }
+}
+
+template <int K>
+__global__ void loss_opt_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, int N,
+                                    int HW, const float* __restrict__ cw, int ignore, int dice,
+                                    const float* __restrict__ terms, const float* __restrict__ grad_out,
+                                    float* __restrict__ dlogits) {
+  const long P = (long)N * HW;
+  const float go = grad_out ? grad_out[0] : 1.f;
+  const float inv_w = 1.f / terms[(size_t)N * K * 3 + 1];
+  const float dscale = -1.f / (float)(K * N);
+  float w[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) w[k] = cw ? cw[k] : 1.f;
+  for (long i = blockIdx.x * (long)NT + threadIdx.x; i < P; i += (long)gridDim.x * NT) {
+    const long n = i / HW, hw = i - n * HW;
+    float z[K], mx = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { z[k] = logits[(n * K + k) * HW + hw]; mx = fmaxf(mx, z[k]); }
+    float se = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { z[k] = expf(z[k] - mx); se += z[k]; }
+    const int64_t t64 = target[i];
+    const bool keep = !(ignore >= 0 && t64 == (int64_t)ignore);
+    const int t = (t64 >= 0 && t64 < K) ? (int)t64 : -1;
+    float p[K], G[K], pg = 0.f, wt = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      p[k] = z[k] / se;
+      const float tk = t == k ? 1.f : 0.f;
+      wt += tk * w[k];
+      float dd = 0.f;
+      if (dice) {
+        const float I = terms[(n * K + k) * 3], S = terms[(n * K + k) * 3 + 1] + terms[(n * K + k) * 3 + 2];
+        if (S != 0.f) {
+          const float den = S + DICE_EPS;
+          dd = 2.f * tk / den - (2.f * I + DICE_EPS) / (den * den);
+        }
+      }
+      G[k] = dscale * dd;
+      pg += p[k] * G[k];
+    }
+    const float cs = wt * inv_w;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const float tk = t == k ? 1.f : 0.f;
+      const float g = go * ((p[k] - tk) * cs + p[k] * (G[k] - pg));
+      dlogits[(n * K + k) * HW + hw] = keep ? g : 0.f;     // dlogits arrives uninitialised
+    }
+  }
+}
+
 // column sums of partial[tiles][C]: columns < split go to out[c], the rest to out2[c - split]
 __global__ void sum_tiles_kernel(const float* __restrict__ partial, int tiles, int C, int split,
                                  float* __restrict__ out, float* __restrict__ out2) {
@@ -399,6 +551,43 @@ extern "C" int stf_loss_bwd(const float* logits, const int64_t* target, int N, i
   if (blocks > 8192) blocks = 8192;
   STF_KDISPATCH(classes, hipLaunchKernelGGL(loss_bwd_kernel<KK>, dim3(blocks), dim3(NT), 0, s, logits, target, N,
                                             H * W, terms, grad_out, dlogits));
+  STF_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stf_loss_opt_scratch_floats(int N, int classes) {
+  return N * classes * 3 + 2 + N * LCHUNK * (3 * classes + 2);
+}
+
+static bool loss_opt_ok(int classes, int ignore_index) {
+  return classes >= 1 && classes <= MAXK && !(ignore_index >= 0 && ignore_index < classes);
+}
+
+extern "C" int stf_loss_opt_fwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
+                                const float* class_weight, int ignore_index, int dice, float* terms, float* loss,
+                                stf_stream_t stream) {
+  if (!loss_opt_ok(classes, ignore_index)) return STF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  float* part = terms + N * classes * 3 + 2;
+  STF_KDISPATCH(classes, {
+    hipLaunchKernelGGL(loss_opt_fwd_kernel<KK>, dim3(LCHUNK, N), dim3(NT), 0, s, logits, target, H * W, class_weight,
+                       ignore_index, part);
+    hipLaunchKernelGGL(loss_opt_finalize_kernel<KK>, dim3(1), dim3(64), 0, s, part, N, dice, terms, loss);
+  });
+  STF_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stf_loss_opt_bwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
+                                const float* class_weight, int ignore_index, int dice, const float* terms,
+                                const float* grad_out, float* dlogits, stf_stream_t stream) {
+  if (!loss_opt_ok(classes, ignore_index)) return STF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long P = (long)N * H * W;
+  long blocks = (P + NT - 1) / NT;
+  if (blocks > 8192) blocks = 8192;
+  STF_KDISPATCH(classes, hipLaunchKernelGGL(loss_opt_bwd_kernel<KK>, dim3(blocks), dim3(NT), 0, s, logits, target, N,
+                                            H * W, class_weight, ignore_index, dice, terms, grad_out, dlogits));
   STF_CHECK_LAUNCH();
   return 0;
 }

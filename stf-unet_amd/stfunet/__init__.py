@@ -6,7 +6,8 @@ output and ``state_dict`` keys) whose forward/backward run hand-written HIP
 kernels through the C ABI in ``include/stfunet.h``.
 """
 from . import _lib  # noqa: F401
+from .loss import criterion  # noqa: F401
 from .stf_lstm_unet import STFLSTMUNet  # noqa: F401
 from .unet import UNet  # noqa: F401
 
-__all__ = ["STFLSTMUNet", "UNet"]
+__all__ = ["STFLSTMUNet", "UNet", "criterion"]

@@ -312,16 +312,22 @@ def evaluate(model, data_loader, device, num_classes):
 
 
 def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler=None,
-                    print_freq=10, scaler=None):
+                    print_freq=10, scaler=None, *, loss_weight=None, dice=True, ignore_index=-100):
+    """The reference's loop (its positional signature and defaults); the keyword-only
+    ``loss_weight`` / ``dice`` / ``ignore_index`` go to ``criterion`` (``ignore_index=255`` for
+    batches whose targets ``collate_fn`` padded to a common size)."""
     model.train()
     logger = MetricLogger(delimiter="  ")
     logger.add_meter("lr", SmoothedValue(window_size=1, fmt="{value:.6f}"))
     lr = optimizer.param_groups[0]["lr"]
+    if loss_weight is not None:      # once per epoch, not a host-to-device copy per step
+        loss_weight = torch.as_tensor(loss_weight, dtype=torch.float32).to(device)
     for image, target in logger.log_every(data_loader, print_freq, f"Epoch: [{epoch}]"):
         image = preprocess_input(image, model).to(device)
         target = target.to(device)
         with torch.amp.autocast(device_type="cuda", enabled=scaler is not None):
-            loss = criterion(model(image), target)
+            loss = criterion(model(image), target, loss_weight=loss_weight, num_classes=num_classes, dice=dice,
+                             ignore_index=ignore_index)
         optimizer.zero_grad()
         if scaler is not None:
             scaler.scale(loss).backward()

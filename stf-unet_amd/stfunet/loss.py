@@ -7,6 +7,19 @@ losses['aux']`` when an aux head is present.  The reference's per-image Python
 loop and its ``if sets_sum == 0`` host sync (dice_coefficient_loss.py:24-35)
 become two kernels with a branch-free empty-set rule; the scalar loss stays on
 the device.
+
+The reference's three options run on the device as well (``stf_loss_opt_fwd`` /
+``stf_loss_opt_bwd``; the default configuration keeps ``stf_loss_fwd`` / ``stf_loss_bwd``):
+
+* ``loss_weight``: per-class weights of the cross-entropy (torch's weighted mean:
+  ``sum w[t] nll / sum w[t]``); they do not enter the Dice term.
+* ``ignore_index >= 0``: pixels whose target equals it are left out of the cross-entropy
+  and of every Dice sum, and get a gradient of exactly 0.  ``DriveDataset.collate_fn`` pads
+  the targets of a mixed-size batch with 255, so such a batch trains with
+  ``ignore_index=255``.  An image whose pixels are all ignored has Dice 1 (the reference's
+  empty-set rule); a batch whose pixels are all ignored has a NaN loss, as
+  ``F.cross_entropy`` gives -- not special-cased.
+* ``dice=False``: cross-entropy only.
 """
 import torch
 
@@ -40,23 +53,83 @@ class _CEDice(torch.autograd.Function):
         return dl, None
 
 
-def ce_dice_loss(logits, target):
+class _CEDiceOpt(torch.autograd.Function):
+    """CE + Dice with class weights, an ignored target value and the Dice switch."""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight, ignore_index, dice):
+        logits = logits.detach().contiguous().float()
+        target = target.contiguous()
+        if target.dtype != torch.int64:
+            target = target.long()
+        N, K, H, W = logits.shape
+        assert target.shape == (N, H, W), f"target {tuple(target.shape)} vs logits {tuple(logits.shape)}"
+        terms = torch.empty(_lib.load().stf_loss_opt_scratch_floats(N, K), dtype=torch.float32,
+                            device=logits.device)
+        loss = torch.empty((), dtype=torch.float32, device=logits.device)
+        wp = _p(weight) if weight is not None else None
+        call("stf_loss_opt_fwd", _p(logits), _p(target), N, H, W, K, wp, ignore_index, int(dice), _p(terms),
+             _p(loss), stream())
+        ctx.save_for_backward(logits, target, terms)
+        ctx.weight, ctx.ignore_index, ctx.dice = weight, ignore_index, int(dice)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        logits, target, terms = ctx.saved_tensors
+        N, K, H, W = logits.shape
+        go = grad_out.detach().float().contiguous().reshape(1)
+        dl = torch.empty_like(logits)
+        wp = _p(ctx.weight) if ctx.weight is not None else None
+        call("stf_loss_opt_bwd", _p(logits), _p(target), N, H, W, K, wp, ctx.ignore_index, ctx.dice, _p(terms),
+             _p(go), _p(dl), stream())
+        return dl, None, None, None, None
+
+
+def _class_weight(weight, num_classes, device=None):
+    """``weight`` (tensor or sequence of ``num_classes`` floats) as a contiguous fp32 vector,
+    on ``device`` when given; ValueError for another length."""
+    if weight is None:
+        return None
+    w = torch.as_tensor(weight, dtype=torch.float32).detach().reshape(-1)
+    if w.numel() != num_classes:
+        raise ValueError(f"loss_weight has {w.numel()} entries for {num_classes} classes")
+    if device is not None:
+        w = w.to(device)
+    return w.contiguous()
+
+
+def _check_ignore(ignore_index, num_classes):
+    if 0 <= ignore_index < num_classes:
+        raise ValueError(f"ignore_index={ignore_index} is a class id (num_classes={num_classes}): the reference's "
+                         "result there is an accident of its one-hot encoding")
+
+
+def ce_dice_loss(logits, target, weight=None, ignore_index=-100, dice=True):
+    ignore_index = int(ignore_index)
+    K = logits.shape[1]
+    _check_ignore(ignore_index, K)
+    weight = _class_weight(weight, K, logits.device)
     if not logits.is_cuda:
         raise RuntimeError("stfunet loss kernels need a ROCm device (no CPU fallback)")
-    return _CEDice.apply(logits, target)
+    if weight is None and dice and ignore_index < 0:
+        return _CEDice.apply(logits, target)
+    return _CEDiceOpt.apply(logits, target, weight, ignore_index, bool(dice))
 
 
 def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool = True, ignore_index: int = -100):
     """Same signature and reduction as the reference ``criterion``.
 
-    Supported configuration is the one the reference trains with
-    (train_and_eval.py:395): no class weights, Dice on, ignore_index -100
-    (targets never hold it: the reference's one-hot would fail on it).
+    The defaults (the configuration the reference trains with, train_and_eval.py:395) take the
+    fused default kernels; ``loss_weight`` (a tensor or a sequence of ``num_classes`` floats),
+    ``ignore_index >= 0`` and ``dice=False`` take the option kernels (module docstring).
+    ValueError for ``0 <= ignore_index < num_classes`` and for a weight vector whose length
+    is not ``num_classes``.  A weight that is not yet a tensor on the logits' device is copied
+    there on every call; a training loop converts it once (``engine.train_one_epoch`` does).
     """
-    if loss_weight is not None or not dice or ignore_index >= 0:
-        raise NotImplementedError("stfunet.criterion implements the reference training configuration "
-                                  "(loss_weight=None, dice=True, ignore_index=-100)")
-    losses = {name: ce_dice_loss(x, target) for name, x in inputs.items()}
+    _check_ignore(int(ignore_index), num_classes)
+    loss_weight = _class_weight(loss_weight, num_classes)
+    losses = {name: ce_dice_loss(x, target, loss_weight, ignore_index, dice) for name, x in inputs.items()}
     if len(losses) == 1:
         return losses["out"]
     return losses["out"] + 0.5 * losses["aux"]

@@ -1,0 +1,109 @@
+"""Loss-kernel pair timing at the cfg2 shape (64 x 2 x 256 x 256 logits): the option kernels
+(stf_loss_opt_fwd + stf_loss_opt_bwd: class weights, ignore_index 255, Dice on) against the
+default pair (stf_loss_fwd + stf_loss_bwd) on the same logits and target, and once more on a
+target with a padded band of 255; interleaved in one process, HIP events over --reps launches
+per round after warm-up.
+
+    python tools/bench_loss.py [--base-lib PATH] [--reps 100] [--rounds 7] [--out FILE]
+
+--base-lib: take the default pair from another build of the library (e.g. the parent commit's
+libstfunet_hip.so) instead of the one in the tree.  Prints per-round times, then one JSON line
+with the medians and minima (us per fwd + bwd pair) and their ratio."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path[:0] = [os.path.dirname(HERE), os.path.join(os.path.dirname(HERE), "stf-unet_amd")]
+import torch  # noqa: E402
+from stfunet import _lib  # noqa: E402
+from stfunet._lib import stream  # noqa: E402
+from stfunet.nhwc import _p  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--base-lib", default=None)
+ap.add_argument("--reps", type=int, default=100)
+ap.add_argument("--rounds", type=int, default=7)
+ap.add_argument("--shape", default="64,2,256,256")
+ap.add_argument("--out", default=None)
+args = ap.parse_args()
+
+N, K, H, W = (int(v) for v in args.shape.split(","))
+dev = "cuda"
+lib = _lib.load()
+base = lib
+if args.base_lib:
+    base = ctypes.CDLL(os.path.abspath(args.base_lib))
+    for name in ("stf_loss_scratch_floats", "stf_loss_fwd", "stf_loss_bwd"):
+        getattr(base, name).restype, getattr(base, name).argtypes = _lib._SIGS[name]
+
+g = torch.Generator(device=dev).manual_seed(0)
+logits = torch.randn(N, K, H, W, device=dev, generator=g) * 2
+target = (torch.rand(N, H, W, device=dev, generator=g) > 0.9).long()
+padded = target.clone()
+padded[:, :, W - W // 8:] = 255                       # a collate-padded band
+weight = torch.linspace(0.5, 2.0, K, device=dev)
+terms = torch.empty(max(lib.stf_loss_opt_scratch_floats(N, K), base.stf_loss_scratch_floats(N, K)), device=dev)
+loss, go, dl = torch.empty(1, device=dev), torch.ones(1, device=dev), torch.empty_like(logits)
+
+
+def check(rc):
+    if rc != 0:
+        raise RuntimeError(f"launch failed: {rc}")
+
+
+def base_pair():
+    s = stream()
+    check(base.stf_loss_fwd(_p(logits), _p(target), N, H, W, K, _p(terms), _p(loss), s))
+    check(base.stf_loss_bwd(_p(logits), _p(target), N, H, W, K, _p(terms), _p(go), _p(dl), s))
+
+
+def opt_on(t):
+    s = stream()
+    check(lib.stf_loss_opt_fwd(_p(logits), _p(t), N, H, W, K, _p(weight), 255, 1, _p(terms), _p(loss), s))
+    check(lib.stf_loss_opt_bwd(_p(logits), _p(t), N, H, W, K, _p(weight), 255, 1, _p(terms), _p(go), _p(dl), s))
+
+
+def opt_pair():            # the default pair's own target: like for like
+    opt_on(target)
+
+
+def opt_pair_padded():     # a W/8 band of 255, as a collated mixed-size batch has
+    opt_on(padded)
+
+
+def timeit(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(args.reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / args.reps * 1e3     # us per pair
+
+
+for fn in (base_pair, opt_pair, opt_pair_padded):
+    for _ in range(20):
+        fn()
+torch.cuda.synchronize()
+tb, to, tp = [], [], []
+for r in range(args.rounds):
+    tb.append(timeit(base_pair))
+    to.append(timeit(opt_pair))
+    tp.append(timeit(opt_pair_padded))
+    print(f"round {r}: default pair {tb[-1]:8.2f} us   option pair {to[-1]:8.2f} us   "
+          f"option pair, padded target {tp[-1]:8.2f} us", flush=True)
+res = {"shape": [N, K, H, W], "reps": args.reps, "rounds": args.rounds, "base_lib": args.base_lib or "in-tree",
+       "default_pair_us": {"median": statistics.median(tb), "min": min(tb)},
+       "option_pair_us": {"median": statistics.median(to), "min": min(to)},
+       "option_pair_padded_us": {"median": statistics.median(tp), "min": min(tp)},
+       "ratio_median": statistics.median(to) / statistics.median(tb)}
+line = json.dumps(res)
+print(line)
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
