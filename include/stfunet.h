@@ -512,6 +512,43 @@ int stf_eval_counts_sm(const float* logits, const float* probs, const int64_t* t
                        int64_t HW, int64_t ignore_index, int64_t* confmat, int64_t* dice_counts,
                        stf_stream_t stream);
 
+/* ---------------------------------------------------------------- inference outputs
+ * The per-image side of the reference's test.py:146-176: the predicted mask, the counts of
+ * train_utils/visualize.py:9-50 (compute_metrics) and the overlay of test.py:52-82 /
+ * train_utils/merge_tumor_images.py:94-120.  Additive to ABI v17; no entry point allocates.
+ *
+ * Mask of a batch of fp32 logits [B][K][HW] (NCHW), written as uint8 [B][HW], in one pass:
+ *   rule 0 (argmax)   the class id of the first maximum over the K planes, a NaN wins
+ *                     (torch.argmax; the prediction of the evaluation counts above);
+ *   rule 1 (sigmoid)  1/(1+exp(-x)) > threshold in fp32 on the plane `channel` alone
+ *                     (test.py:168-169): x = 0 at threshold 0.5 gives 0, NaN 0, +inf 1, -inf 0.
+ * With target (int64 [B][HW], may be NULL) counts [B][3] int64 is OVERWRITTEN with the
+ * per-image (|P&T|, |P|, |T|), P = mask > 0 and T = target > 0 (compute_metrics' target > 0.5:
+ * a 255 pad is foreground); ignore >= 0 leaves the pixels whose target equals it out of all
+ * three, a negative value none.  The counts are integers: any summation order is exact.
+ * STF_EINVAL (nothing launched) for K outside 1..16, channel outside [0, K), a rule other than
+ * 0 / 1, a NULL logits or mask, or a target without counts. */
+int stf_predict_mask(const float* logits, const int64_t* target, int B, int K, int64_t HW, int rule,
+                     int channel, float threshold, int64_t ignore, uint8_t* mask, int64_t* counts,
+                     stf_stream_t stream);
+/* Bytes of the scratch the overlay needs for B images of HW pixels (per-image min / max rows). */
+size_t stf_predict_overlay_scratch_bytes(int B, int64_t HW);
+/* The mask painted over one fp32 [H][W] plane per image, out uint8 [B][H][W][3].  Image b's
+ * plane starts at frames + b * batch_stride (elements), so the shown frame of a [B,T,C,H,W]
+ * input is passed as the view inputs[:,0,0] without a copy.  Two launches: per-image min / max
+ * into scratch, then, every fp32 operation rounded on its own (no FMA) as numpy evaluates them,
+ *   gray = (uint8)(((x - min) / (max - min + 1e-8f)) * 255.f)                      (test.py:71)
+ *   painted pixels:  (uint8)(gray * (1 - alpha) + colour_c * alpha), c = 0, 1, 2   (:114-118)
+ *   other pixels:    gray in all three channels
+ * where a pixel is painted when (mask != 0) == paint; test.py:75-76 inverts its mask before
+ * painting, which is paint = 0.  A constant image gives gray = 0.  The result for a plane with
+ * non-finite pixels is undefined.  Channel c of out takes colour c: the reference hands
+ * (c0, c1, c2) to cv2 as B, G, R.  STF_EINVAL (nothing launched) for alpha outside [0, 1], a
+ * colour outside 0..255, paint other than 0 / 1, a negative stride or a NULL pointer. */
+int stf_predict_overlay(const float* frames, int64_t batch_stride, const uint8_t* mask, int B, int H,
+                        int W, int c0, int c1, int c2, float alpha, int paint, uint8_t* out,
+                        void* scratch, stf_stream_t stream);
+
 /* ---------------------------------------------------------------- PK maps (extended Tofts)
  * pk_fitting.py ToftsModelFitter, all fp32.  The host builds
  * the reference's constant tables exactly as the reference does (pk_fitting.py:

@@ -6,8 +6,10 @@ output and ``state_dict`` keys) whose forward/backward run hand-written HIP
 kernels through the C ABI in ``include/stfunet.h``.
 """
 from . import _lib  # noqa: F401
+from . import predict  # noqa: F401  (the module; its loop is stfunet.predict.predict)
 from .loss import criterion  # noqa: F401
+from .predict import image_metrics, overlay, predict_masks  # noqa: F401
 from .stf_lstm_unet import STFLSTMUNet  # noqa: F401
 from .unet import UNet  # noqa: F401
 
-__all__ = ["STFLSTMUNet", "UNet", "criterion"]
+__all__ = ["STFLSTMUNet", "UNet", "criterion", "image_metrics", "overlay", "predict", "predict_masks"]

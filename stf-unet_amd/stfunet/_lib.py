@@ -160,6 +160,10 @@ _SIGS = {
     "stf_bilinear_ac_bwd_tsum": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int64, c_int64, c_int,
                                          c_int, P]),
     "stf_eval_counts_sm": (c_int, [P, P, P, c_int, c_int, c_int64, c_int64, P, P, P]),
+    "stf_predict_mask": (c_int, [P, P, c_int, c_int, c_int64, c_int, c_int, c_float, c_int64, P, P, P]),
+    "stf_predict_overlay_scratch_bytes": (c_size_t, [c_int, c_int64]),
+    "stf_predict_overlay": (c_int, [P, c_int64, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P,
+                                    P]),
     "stf_tofts_forward": (c_int, [P, P, P, c_int, c_int, P, P, P, P, P, c_int, c_float, P, P]),
     "stf_tofts_fit": (c_int, [P, c_int, c_int, P, P, P, P, P, c_int, c_float, c_int, c_int, P, c_float, c_float,
                               c_float, P, P, P]),

@@ -1,0 +1,181 @@
+"""Inference on the device: masks, per-image Dice / IoU and overlays.
+
+The reference's inference script (``test.py:146-176``) with its helpers restated on the
+gfx950 kernels of ``csrc/predict.hip``:
+
+* ``predict_masks``   logits -> ``uint8`` mask (``torch.sigmoid(outputs) > 0.5``, test.py:168-169,
+  or the argmax ``evaluate`` scores) and, with a target, the per-image (|P&T|, |P|, |T|) counts
+* ``image_metrics``   counts -> per-image Dice and IoU (``compute_metrics``,
+  train_utils/visualize.py:9-50), on the device, no host synchronisation
+* ``overlay``         the mask painted over a frame (``save_overlay_from_tensor``, test.py:52-82,
+  through ``merge_images``, train_utils/merge_tumor_images.py:94-120)
+* ``predict``         the loop: eval mode, ``no_grad``, ``preprocess_input``, forward, masks,
+  counts when the loader yields targets, one PNG per slice when ``output_dir`` is given
+
+``predict(model, loader, device, rule="sigmoid", channel=0, paint=0)`` reproduces test.py bit for
+bit (it thresholds channel 0 and inverts the mask before painting, :75-76), except that the
+PNGs are RGB: channel ``c`` of an overlay takes ``color[c]``, where the reference hands the same
+triple to cv2 as B, G, R.  The default colour (0, 255, 0) reads the same both ways.
+
+There is no CPU path: tensors on the host raise.
+"""
+import os
+
+import torch
+
+from ._lib import call, load, stream
+from .nhwc import _p
+
+RULES = {"argmax": 0, "sigmoid": 1}
+MAX_CLASSES = 16
+
+
+def _device_only(t, what):
+    if not t.is_cuda:
+        raise RuntimeError(f"stfunet.predict.{what} runs the gfx950 predict kernels: tensors must be on a ROCm "
+                           "device (no CPU fallback)")
+
+
+def _check_paint(color, alpha, paint):
+    color = tuple(color)
+    if len(color) != 3 or any(int(c) != c or not 0 <= c <= 255 for c in color):
+        raise ValueError(f"color must be three integers in 0..255, not {color}")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"alpha must be in [0, 1], not {alpha}")
+    if paint not in (0, 1):
+        raise ValueError(f"paint must be 0 (colour where the mask is zero) or 1, not {paint}")
+    return tuple(int(c) for c in color)
+
+
+def predict_masks(outputs, rule="argmax", channel=0, threshold=0.5, target=None, ignore_index=None):
+    """``uint8 [B, H, W]`` mask of logits ``[B, K, H, W]`` (or the models' ``{"out": logits}``).
+
+    ``rule="argmax"``: the class id of the first maximum (``torch.argmax(outputs, 1)``).
+    ``rule="sigmoid"``: ``torch.sigmoid(outputs[:, channel]) > threshold`` in fp32.
+    With ``target`` (``[B, H, W]`` integers) also returns ``int64 [B, 3]`` per-image counts
+    (|P&T|, |P|, |T|) with P = mask > 0 and T = target > 0; pixels whose target equals
+    ``ignore_index`` are left out of all three."""
+    if isinstance(outputs, dict):
+        outputs = outputs["out"]
+    if rule not in RULES:
+        raise ValueError(f"unknown rule {rule!r} (one of {sorted(RULES)})")
+    if outputs.dim() != 4:
+        raise ValueError(f"logits must be [B, K, H, W], not {tuple(outputs.shape)}")
+    B, K, H, W = outputs.shape
+    if not 1 <= K <= MAX_CLASSES:
+        raise ValueError(f"1..{MAX_CLASSES} classes are supported, not {K}")
+    if not 0 <= channel < K:
+        raise ValueError(f"channel {channel} is outside [0, {K})")
+    if target is not None and tuple(target.shape) != (B, H, W):
+        raise ValueError(f"target {tuple(target.shape)} does not match the logits' {(B, H, W)}")
+    _device_only(outputs, "predict_masks")
+    x = outputs.detach().float().contiguous()
+    mask = torch.empty((B, H, W), dtype=torch.uint8, device=x.device)
+    counts = None
+    if target is not None:
+        target = target.detach().to(device=x.device, dtype=torch.int64).contiguous()
+        counts = torch.empty((B, 3), dtype=torch.int64, device=x.device)
+    with torch.cuda.device(x.device):
+        call("stf_predict_mask", _p(x), _p(target), B, K, H * W, RULES[rule], channel, threshold,
+             -1 if ignore_index is None else ignore_index, _p(mask), _p(counts), stream())
+    return mask if target is None else (mask, counts)
+
+
+def image_metrics(counts, smooth=1e-5):
+    """Per-image ``dice = (2I + s) / (P + T + s)`` and ``iou = (I + s) / (P + T - I + s)`` of
+    ``[B, 3]`` counts (I, P, T), as float64 tensors on the counts' device."""
+    c = counts.to(torch.float64)
+    inter, p, t = c.unbind(-1)
+    return (2 * inter + smooth) / (p + t + smooth), (inter + smooth) / (p + t - inter + smooth)
+
+
+def overlay(frames, mask, color=(0, 255, 0), alpha=0.5, paint=1):
+    """``uint8 [B, H, W, 3]``: ``frames`` normalised to 0..255 per image, with ``color`` blended
+    at ``alpha`` into the pixels where the mask is non-zero (``paint=1``) or zero (``paint=0``).
+
+    ``frames`` is ``[B, H, W]`` fp32, contiguous or any view whose last two dimensions are
+    (``inputs[:, 0, 0]`` of a ``[B, T, C, H, W]`` batch is read in place).  Frames with
+    non-finite pixels give an undefined picture."""
+    color = _check_paint(color, alpha, paint)
+    if frames.dim() != 3:
+        raise ValueError(f"frames must be [B, H, W], not {tuple(frames.shape)}")
+    if tuple(mask.shape) != tuple(frames.shape):
+        raise ValueError(f"mask {tuple(mask.shape)} does not match the frames' {tuple(frames.shape)}")
+    _device_only(frames, "overlay")
+    _device_only(mask, "overlay")
+    B, H, W = frames.shape
+    frames = frames.detach()
+    if frames.dtype != torch.float32:
+        frames = frames.float()
+    if B and H * W and (frames.stride(2) != 1 or frames.stride(1) != W or frames.stride(0) < 0):
+        frames = frames.contiguous()
+    if mask.dtype == torch.bool:
+        mask = mask.view(torch.uint8)
+    elif mask.dtype != torch.uint8:
+        mask = (mask != 0).view(torch.uint8)
+    mask = mask.to(frames.device).contiguous()
+    out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=frames.device)
+    if B == 0 or H * W == 0:
+        return out
+    nbytes = load().stf_predict_overlay_scratch_bytes(B, H * W)
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=frames.device)
+    with torch.cuda.device(frames.device):
+        call("stf_predict_overlay", _p(frames), frames.stride(0), _p(mask), B, H, W, color[0], color[1], color[2],
+             alpha, paint, _p(out), _p(scratch), stream())
+    return out
+
+
+def shown_frame(inputs):
+    """The frame test.py paints on (:173 then :67-68): ``inputs[:, 0, 0]`` of a 5-D model input,
+    ``inputs[:, 0]`` of a 4-D one -- a view, not a copy."""
+    if inputs.dim() == 5:
+        return inputs[:, 0, 0]
+    if inputs.dim() == 4:
+        return inputs[:, 0]
+    raise ValueError(f"model input must be [B, T, C, H, W] or [B, C, H, W], not {tuple(inputs.shape)}")
+
+
+def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5, ignore_index=None,
+            output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5, paint=1, keep_masks=False):
+    """The inference loop of test.py:146-176 for any batch size.
+
+    The loader yields ``inputs`` or ``(inputs, targets)`` (targets may be None).  Returns a dict:
+    ``num`` slices seen and, when targets came, per-image ``dice`` / ``iou`` (float64 device
+    tensors in slice order) with their means ``mean_dice`` / ``mean_iou`` (None otherwise).
+    With ``output_dir`` every slice is written as ``{prefix}_{idx}.png`` (RGB, ``idx`` the running
+    slice index); that is the loop's only device-to-host copy, one per batch.  ``keep_masks=True``
+    adds ``masks``, the list of each batch's ``uint8 [B, H, W]`` device mask."""
+    if rule not in RULES:
+        raise ValueError(f"unknown rule {rule!r} (one of {sorted(RULES)})")
+    color = _check_paint(color, alpha, paint)
+    from .engine import preprocess_input
+    if output_dir is not None:
+        from PIL import Image
+        os.makedirs(output_dir, exist_ok=True)
+    model.eval()
+    all_counts, masks, idx = [], [], 0
+    with torch.no_grad():
+        for batch in data_loader:
+            inputs, targets = batch if isinstance(batch, (tuple, list)) else (batch, None)
+            inputs = preprocess_input(inputs, model).to(device)
+            outputs = model(inputs)
+            if targets is not None:
+                mask, counts = predict_masks(outputs, rule, channel, threshold, target=targets.to(device),
+                                             ignore_index=ignore_index)
+                all_counts.append(counts)
+            else:
+                mask = predict_masks(outputs, rule, channel, threshold)
+            if output_dir is not None:
+                pics = overlay(shown_frame(inputs), mask, color, alpha, paint).cpu().numpy()
+                for j, pic in enumerate(pics):
+                    Image.fromarray(pic).save(os.path.join(output_dir, f"{prefix}_{idx + j}.png"))
+            if keep_masks:
+                masks.append(mask)
+            idx += mask.shape[0]
+    res = {"num": idx, "dice": None, "iou": None, "mean_dice": None, "mean_iou": None}
+    if all_counts:
+        dice, iou = image_metrics(torch.cat(all_counts))
+        res.update(dice=dice, iou=iou, mean_dice=dice.mean(), mean_iou=iou.mean())
+    if keep_masks:
+        res["masks"] = masks
+    return res
