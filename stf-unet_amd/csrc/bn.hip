@@ -987,8 +987,7 @@ extern "C" int stf_bn_bwd_reduce(const void* dz, int dz_cstride, const void* dpo
     STF_CHECK_LAUNCH();
     return 0;
   }
-  static const bool lanes = stf::ab_switch("STF_POOL_LANES", 1) != 0;
-  if (dpool && lanes && 64 % (C / 8) == 0 && mask_mode != 2 && (long)N * H * W < (1L << 31))
+  if (dpool && 64 % (C / 8) == 0 && mask_mode != 2 && (long)N * H * W < (1L << 31))
     hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel, grid, dim3(PNT), 0, s, (const uint16_t*)dz, dz_cstride,
                        (const uint16_t*)dpool, (const uint16_t*)y, y_cstride, (long)N, H, W, C, groups, tpg, scale,
                        shift, mean, invstd, mask_mode, (uint16_t*)g_out, partial);

@@ -2265,89 +2265,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c8_kernel(Geo a, int TY, int T
   if (a.stats && run_key >= 0) flush();
 }
 
-constexpr int HALO_PW = 32;
-// 16 x 32 tile, 8 waves, 2-stage ring (1 WG/CU)
-constexpr int HALO_PH = 16;
-int halo_ph() { return HALO_PH; }
-// tile width: 32 for W >= 32; 16x16 tiles (32 pixels per wave) for 16 <= W < 32
-int halo_pw(const stf_conv_geom& c) { return c.Wd >= 32 ? HALO_PW : 16; }
-// narrowest layer the halo kernel takes (measured in round 3: at 16 <= W < 32 the 16x16 tile
-// wins up to 256 output channels, the 256x256 linear tile above that)
-constexpr int HALO_MIN_W = 16;
-// 8 x 8 layers through the halo kernel, four images per 8 x 32 tile (conv3x3_halo4_kernel;
-// STF_HALO4=0: the linear split-K kernels, A/B)
-bool halo8(const stf_igemm_args* a) {
-  static const int mode = stf::ab_switch("STF_HALO4", 1);
-  const stf_conv_geom& c = a->g;
-  if (mode == 0 || (mode == 2 && a->bnr)) return false;
-  if (c.Hd != 8 || c.Wd != 8 || c.N % 4 || a->Nout % 64 || c.Cs % 32) return false;
-  const long M = (long)c.N * c.Hd * c.Wd;
-  const long Mg = a->group_rows > 0 ? a->group_rows : M;
-  return (Mg / (c.Hd * c.Wd)) % 4 == 0;
-}
+// ---------------------------------------------------------------------------
+// Host side.  Every entry point below computes one Route (route_of) and reads everything else from
+// it.  The Route names one entry of VARIANTS, which carries the kernel's name as the profiler
+// prints it AND the kernel, so stf_igemm_kernel_name and the launch cannot disagree.
 
-// 8-channel-input 3x3 layer through conv3x3_c8_kernel (STF_C8HALO=0: the linear 'e' kernel, A/B)
-bool c8_halo(const stf_igemm_args* a) {
-  static const bool on = stf::ab_switch("STF_C8HALO", 1) != 0;
-  const stf_conv_geom& c = a->g;
-  return on && !a->lstm && !a->scatter2x2 && !c.transposed && !a->bnr && !a->accumulate && c.Cs == 8 &&
-         c.src_cstride % 8 == 0 && c.R == 3 && c.S == 3 && c.stride == 1 && c.pad == 1 && c.Hd == c.Hs &&
-         c.Wd == c.Ws && a->Nout == 64 && a->dst_cstride % 8 == 0 && ((uintptr_t)a->dst & 15) == 0 &&
-         (uint64_t)c.N * c.Hd * c.Wd * a->dst_cstride * 2 < 0xFFFFFF00ull;
-}
-
-// direct-store epilogue; STF_HALO_DIRECT=0 disables, =1 only without BN statistics (dgrad),
-// =2 always (default: measured 1.7 % faster on the forward convs than the LDS-staged one)
-bool halo_direct(const stf_igemm_args* a) {
-  static const int mode = stf::ab_switch("STF_HALO_DIRECT", 2);
-  return !halo8(a) && (mode == 2 || (mode == 1 && !a->stats));
-}
-
-// BN-backward reduction fused into the halo direct epilogue (STF_BNR_FUSED=0: separate
-// stf_bn_bwd_reduce pass after the GEMM, for A/B measurements)
-bool bnr_fused(const stf_igemm_args* a, char k) {
-  static const bool on = stf::ab_switch("STF_BNR_FUSED", 1) != 0;
-  return on && a->bnr && k == 'H' && halo_direct(a);
-}
-
-int halo_ix(const stf_igemm_args* a, bool with_stats);
-int halo_grid(const stf_igemm_args* a, int ix);
-void halo_tiles(const stf_conv_geom& c, int& ty, int& tx);
-
-// the wide halo kernel (conv3x3_wide_kernel: 128-channel output slices) for 3x3 layers with >= 128
-// output channels and W >= 32, forward, plain dgrad and BN-backward-fused dgrad (STF_WIDE_BNR=0: that one
-// on the 64-channel kernel, A/B); STF_HALO_WIDE=0: the 64-channel halo kernel (A/B)
-bool bnr_fused(const stf_igemm_args* a, char k);
-bool halo_wide(const stf_igemm_args* a) {
-  static const int on = stf::ab_switch("STF_HALO_WIDE", 1);
-  static const int wbnr = stf::ab_switch("STF_WIDE_BNR", 1);
-  const stf_conv_geom& c = a->g;
-  if (a->bnr && !(wbnr && bnr_fused(a, 'H'))) return false;
-  return on && !a->lstm && !a->scatter2x2 && !c.transposed && halo_direct(a) && a->Nout % 128 == 0 &&
-         c.Wd >= 32 && c.Cs % 32 == 0 && halo_ix(a, a->stats != nullptr) == 1;
-}
-
-// deferred epilogue of the second wave half (halo_body DEFER; default on, STF_HALO_DEFER=0: off, A/B).  Its
-// statistics fold keeps at most 2 (group, slice) keys per workgroup: the item run of a workgroup
-// (items / grid + 1, slice-major, image-major within a slice) must not span more.
-bool halo_defer(const stf_igemm_args* a) {
-  static const int on = stf::ab_switch("STF_HALO_DEFER", 1);
-  if (!(on && halo_direct(a) && !halo8(a)) || halo_wide(a)) return false;
-  // (not the two-image 16 x 16 tiles: their deferred variants spill registers)
-  const int ix = halo_ix(a, a->stats != nullptr);
-  if (ix > 1) return false;
-  if (!a->stats && !a->bnr) return true;                 // no statistics rows
-  const stf_conv_geom& c = a->g;
-  int ty, tx;
-  halo_tiles(c, ty, tx);
-  if (ix > 1) ty = tx = 1;
-  const long M = (long)c.N * c.Hd * c.Wd;
-  const long Mg = a->group_rows > 0 ? a->group_rows : M;
-  const long run = (Mg / ((long)c.Hd * c.Wd) / ix) * ty * tx;   // items per (group, slice) key
-  const long items = (long)(c.N / ix) * ty * tx * (a->Nout / 64);
-  const long per = items / halo_grid(a, ix) + 1;
-  return run > 0 && (per + run - 1) / run + 1 <= 2;
-}
+constexpr int HALO_PH = 16, HALO_PW = 32;   // halo tile: 16 x 32 pixels, 8 waves, 2-stage ring (1 WG/CU)
+constexpr int HALO_MIN_W = 16;              // narrowest layer of the halo kernel (16 x 16 tiles below W = 32)
 
 int num_cus() {
   static const int n = [] {
@@ -2359,19 +2283,105 @@ int num_cus() {
   return n;
 }
 
-int c8_tiles(const stf_conv_geom& c) { return c.N * ((c.Hd + C8_T - 1) / C8_T) * ((c.Wd + C8_T - 1) / C8_T); }
-int c8_grid(const stf_igemm_args* a) { return std::min(c8_tiles(a->g), 2 * num_cus()); }
+// Tiles of the linear DMA kernel (BM, BN, waves WM x WN, BK, ring stages) and of the register-staged one
+struct Cfg { int bm, bn, wm, wn, bkk, stages; };
+#define TILE_A 128, 128, 2, 2, 32, 4   // 4 waves, 2 blocks/CU
+#define TILE_B 256, 128, 4, 2, 64, 3   // 8 waves
+#define TILE_C 256, 256, 2, 4, 64, 2   // 8 waves
+#define TILE_D 512, 64, 8, 1, 64, 2    // 8 waves
+#define TILE_E 256, 64, 4, 1, 32, 4    // 4 waves, 2 blocks/CU
+#define TILE_F 128, 256, 2, 4, 32, 2   // 8 waves, 2 blocks/CU (80 KiB each)
+#define TILE_R 128, 128, 2, 2          // register-staged
+#define TILE_S 256, 64, 4, 1           // register-staged, Nout <= 64
 
-// Tile configurations of the DMA kernel.  'auto' picks per shape; the
-// STF_IGEMM_CFG environment variable forces one (A/B measurements).
-struct Cfg { int bm, bn, bkk; };
-constexpr Cfg CFG_A{128, 128, 32};   // 4 waves (2x2), 4 stages, 2 blocks/CU
-constexpr Cfg CFG_B{256, 128, 64};   // 8 waves (4x2), 3 stages
-constexpr Cfg CFG_C{256, 256, 64};   // 8 waves (2x4), 2 stages
-constexpr Cfg CFG_D{512, 64, 64};    // 8 waves (8x1), 2 stages
-constexpr Cfg CFG_E{256, 64, 32};    // 4 waves (4x1), 4 stages, 2 blocks/CU
-constexpr Cfg CFG_F{128, 256, 32};   // 8 waves (2x4), 2 stages, 2 blocks/CU (80 KiB each)
+Cfg cfg_of(char k) {
+  switch (k) {
+    case 'B': return Cfg{TILE_B};
+    case 'C': return Cfg{TILE_C};
+    case 'D': return Cfg{TILE_D};
+    case 'E': case 'e': return Cfg{TILE_E};
+    case 'F': return Cfg{TILE_F};
+    default: return Cfg{TILE_A};
+  }
+}
 
+// One launchable instantiation.  family: 'K' 8-channel input, '4' four 8 x 8 images per tile, 'W' wide
+// (128-channel slices), '2' two 16 x 16 images per tile, 'h' / 'H' single-image 16 x 16 / 16 x 32 tiles,
+// a linear DMA tile letter ('a' / 'e': the 8-channel-input forms of A / E), 'R' / 'S' register-staged.
+// key: halo families {DIRECT, BNR, DEFER, DIAG}; DMA {TRANS, SCATTER, EPI}; register-staged
+// {SMALLC, TRANS, SCATTER, EPI}.  Name, key and kernel of an entry come from the same macro arguments.
+struct Variant {
+  const char* name;
+  char family;
+  int key[4];
+  int threads, bn;
+  void (*tile)(Geo, uint32_t, int, int, int, int);
+  void (*c8)(Geo, int, int, int, int, int);
+  void (*dma)(Geo, uint32_t);
+  void (*reg)(Geo);
+};
+#define STF_STR_(...) #__VA_ARGS__
+#define STF_STR(...) STF_STR_(__VA_ARGS__)
+#define V_TILE(FAM, THREADS, KERNEL, K0, K1, K2, K3, ...) \
+  {#KERNEL "<" STF_STR(__VA_ARGS__) ">", FAM, {K0, K1, K2, K3}, THREADS, 64, KERNEL<__VA_ARGS__>, nullptr, nullptr, nullptr}
+#define V_HALO(PW, DIAG, DIRECT, BNR, DEFER) \
+  V_TILE(PW == 16 ? 'h' : 'H', 512, conv3x3_halo_kernel, DIRECT, BNR, DEFER, DIAG, 16, PW, 8, 2, DIAG, DIRECT, BNR, DEFER)
+#define V_HALO2(DIRECT, BNR) V_TILE('2', 512, conv3x3_halo2_kernel, DIRECT, BNR, 0, 0, DIRECT, BNR, false)
+#define V_WIDE(DIRECT, BNR) V_TILE('W', 512, conv3x3_wide_kernel, DIRECT, BNR, 0, 0, DIRECT, BNR)
+#define V_DMA(FAM, TILE, TR, SC, EPI, C8)                                                              \
+  {"igemm_dma_kernel<" STF_STR(TILE, TR, SC, EPI, C8) ">", FAM, {TR, SC, EPI, 0},                      \
+   64 * Cfg{TILE}.wm * Cfg{TILE}.wn, Cfg{TILE}.bn, nullptr, nullptr, igemm_dma_kernel<TILE, TR, SC, EPI, C8>, nullptr}
+#define V_REG(FAM, TILE, SMALLC, TR, SC, EPI)                                                          \
+  {"igemm_kernel<" STF_STR(TILE, SMALLC, TR, SC, EPI) ">", FAM, {SMALLC, TR, SC, EPI}, NT, Cfg{TILE, 0, 0}.bn, \
+   nullptr, nullptr, nullptr, igemm_kernel<TILE, SMALLC, TR, SC, EPI>}
+const Variant VARIANTS[] = {
+    {"conv3x3_c8_kernel", 'K', {0, 0, 0, 0}, 256, 64, nullptr, conv3x3_c8_kernel, nullptr, nullptr},
+    V_TILE('4', 256, conv3x3_halo4_kernel, 0, 0, 0, 0, 0),
+    V_WIDE(2, false), V_WIDE(1, false), V_WIDE(1, true),
+    V_HALO2(2, false), V_HALO2(1, false), V_HALO2(1, true),
+    // (no 16 x 16 <1, false, false>: a launch without statistics rows always defers)
+    V_HALO(16, 0, 2, false, false), V_HALO(16, 0, 2, false, true), V_HALO(16, 0, 1, false, true),
+    V_HALO(16, 0, 1, true, false), V_HALO(16, 0, 1, true, true),
+    V_HALO(32, 0, 2, false, false), V_HALO(32, 0, 2, false, true), V_HALO(32, 0, 1, false, true),
+    V_HALO(32, 0, 1, true, false), V_HALO(32, 0, 1, true, true),
+    // STF_HALO_DIAG (timing only, results wrong): 4 = cycle buckets (tools/halo_timeline.py), no
+    // statistics; 2 = no DMA reloads after the first stage
+    V_HALO(32, 4, 1, false, false), V_HALO(32, 2, 2, false, false), V_HALO(32, 2, 1, false, false),
+    V_DMA('A', TILE_A, false, false, 0, false), V_DMA('A', TILE_A, false, false, 1, false),
+    V_DMA('A', TILE_A, false, false, 2, false), V_DMA('A', TILE_A, false, true, 0, false),
+    V_DMA('A', TILE_A, true, false, 0, false),
+    V_DMA('E', TILE_E, false, false, 0, false), V_DMA('E', TILE_E, false, true, 0, false),
+    V_DMA('E', TILE_E, true, false, 0, false),
+    V_DMA('a', TILE_A, false, false, 0, true), V_DMA('e', TILE_E, false, false, 0, true),
+    V_DMA('B', TILE_B, false, false, 0, false), V_DMA('B', TILE_B, false, true, 0, false),
+    V_DMA('C', TILE_C, false, false, 0, false), V_DMA('C', TILE_C, false, true, 0, false),
+    V_DMA('D', TILE_D, false, false, 0, false), V_DMA('D', TILE_D, false, true, 0, false),
+    V_DMA('F', TILE_F, false, false, 0, false), V_DMA('F', TILE_F, false, true, 0, false),   // forced only
+    V_REG('R', TILE_R, false, false, false, 0), V_REG('R', TILE_R, true, false, false, 0),
+    V_REG('R', TILE_R, false, true, false, 0), V_REG('R', TILE_R, true, true, false, 0),
+    V_REG('R', TILE_R, false, false, true, 0), V_REG('R', TILE_R, true, false, true, 0),
+    V_REG('R', TILE_R, false, false, false, 1), V_REG('R', TILE_R, false, false, false, 2),
+    V_REG('S', TILE_S, false, false, false, 0), V_REG('S', TILE_S, true, false, false, 0),
+    V_REG('S', TILE_S, false, true, false, 0), V_REG('S', TILE_S, true, true, false, 0),
+    V_REG('S', TILE_S, false, false, true, 0), V_REG('S', TILE_S, true, false, true, 0),
+};
+#undef V_REG
+#undef V_DMA
+#undef V_WIDE
+#undef V_HALO2
+#undef V_HALO
+#undef V_TILE
+
+int find_variant(char family, int k0, int k1, int k2, int k3) {
+  for (int i = 0; i < (int)(sizeof VARIANTS / sizeof VARIANTS[0]); ++i) {
+    const Variant& v = VARIANTS[i];
+    if (v.family == family && v.key[0] == k0 && v.key[1] == k1 && v.key[2] == k2 && v.key[3] == k3) return i;
+  }
+  return -1;
+}
+
+// STF_IGEMM_CFG forces a tile (tools/bench_gemm_shape.py): A-F a linear DMA tile, H the halo family
+// wherever it applies, L the linear kernels only; '0' = auto
 char forced_cfg() {
   static const char c = [] {
     const char e = stf::ab_letter("STF_IGEMM_CFG");
@@ -2380,283 +2390,187 @@ char forced_cfg() {
   return c;
 }
 
-// STF_IGEMM_DMA=0 selects the register-staged kernel (A/B comparisons); read once.
-bool dma_enabled() {
-  static const bool on = stf::ab_switch("STF_IGEMM_DMA", 1) != 0;
-  return on;
-}
+// Which kernel runs a launch, on what grid, and what its size queries answer.
+struct Route {
+  int variant = -1;      // index into VARIANTS; -1: no kernel takes these arguments (STF_EINVAL)
+  char kind = 'R';       // 'K' 8-channel input, 'H' halo family, a linear DMA tile letter, 'R' register-staged
+  // persistent tile kernels ('K', 'H'): images per tile, tile width, tiles per image, work items
+  // (tile x output slice), grid, items per workgroup and the remainder
+  int ix = 1, pw = HALO_PW, ty = 0, tx = 0, grid = 0, per = 0, rem = 0;
+  long items = 0;
+  bool wide = false;         // 128-channel output slices (conv3x3_wide_kernel)
+  int direct = 0;            // epilogue: 0 LDS-staged, 1 direct stores, 2 direct with statistics
+  bool bnr_fused = false;    // the BN-backward reduction runs in the epilogue (else stf_bn_bwd_reduce after)
+  bool defer = false;        // deferred epilogue of the second wave half
+  // linear kernels: M tile, M tiles per statistics group, split-K factor, stride-2 transposed
+  // parity mode (0 off, 1 rows by output parity class, 2 also skipping the tap-less classes)
+  int bm = 128, tpg = 0, ksplit = 1, par = 0;
+  int stat_tiles = 0, bnr_tiles = 0;   // partial rows per group: BN statistics, BN-backward sums
+  size_t ws_bytes = 0;                 // split-K workspace
+};
 
-// which kernel runs: 'R' = register-staged (BM 256 for Nout <= 64, else 128), or a DMA config letter
-char choose(const stf_igemm_args* a, bool dma_ok) {
+// with_stats: the launch writes BN statistics.  stf_igemm passes a->stats != nullptr; the size
+// queries pass what the launch will do (stf_igemm_stat_tiles is asked before the statistics buffer
+// exists: true; stf_igemm_bnr_tiles: false).
+//
+// The rules, in the order they apply (STF_IGEMM_CFG: see forced_cfg; it also turns rule 1 off):
+//  1. 8-channel network input, 3x3, 64 outputs -> conv3x3_c8_kernel (cfg2 step 23.4 -> 23.2 ms against
+//     the linear 'e' kernel, profiles/r03/ab_c8.txt); any other plain 8-channel gather -> 'e' / 'a'.
+//  2. sources or weights past the 4 GiB buffer descriptor, or Cs not a multiple of 32 -> register-staged
+//     (256 x 64 tile for Nout <= 64, else 128 x 128).
+//  3. LSTM steps (1x1 GEMM, K = 2C) -> the 128 x 128 DMA tile (any tile gives the same gates -- the same
+//     MFMA sequence over ascending K -- so the backward recompute may run another tile).
+//  4. 3x3 / stride 1 / pad 1 with Nout % 64 == 0 -> the halo family when W >= 32; at 16 <= W < 32 up to
+//     256 outputs (round 3: the 16 x 16 tile wins up to 256 output channels, the 256 x 256 linear tile
+//     above); above 256 outputs when the two-image tile applies (rule 6; UNet's bottleneck); at
+//     8 x 8 when the four-image tile applies (rule 5).
+//  5. 8 x 8 layers, N and the images per statistics group multiples of 4 -> four images per 8 x 32 tile
+//     (conv3x3_halo4_kernel, LDS-staged epilogue; against the linear split-K kernels the STF step
+//     10.34 -> 10.25 ms, profiles/r03/ab_halo2.txt).  A BN-backward request is not fused on it.
+//  6. 16 x 16 layers, N and the images per group even -> two images per 16 x 32 tile, for launches that
+//     write statistics (the forward convs) and for every launch with more than 256 outputs (UNet's
+//     bottleneck: its dgrads run 4-22 % faster on them than on single-image tiles or the linear
+//     kernels, tools/bench_layers.py, profiles/r06/ab_bottleneck_halo2.txt).  The other dgrads stay on
+//     single-image tiles: they run beside the side-stream weight gradients, and the 160 KiB workgroup
+//     of the 16 x 32 tile cannot share a CU with them (128 KiB for 16 x 16); all on two-image tiles
+//     re-measured neutral to -0.9 % (profiles/r06/ab_halo2_all_stf.txt).
+//  7. single-image tiles, Nout % 128 == 0 and W >= 32 -> the wide kernel (128-channel slices), forward,
+//     plain and BN-backward-fused dgrad (cfg2 +0.5..0.8 %, profiles/r06/ab_wide_halo.txt, ab_wide_bnr.txt).
+//  8. every halo tile but the four-image one stores directly (1.7 % faster on the forward convs than
+//     the LDS-staged epilogue) and fuses a BN-backward request into that epilogue.
+//  9. single-image 64-channel-slice tiles defer the second wave half's epilogue (the two-image tiles
+//     would spill registers).  Its statistics fold keeps at most 2 (group, slice) keys per workgroup:
+//     the item run of a workgroup (items / grid + 1, slice-major, image-major within a slice) must not
+//     span more, else the launch does not defer.
+// 10. other gathers -> linear DMA tiles, measured per layer (tools/bench_layers.py, cfg2 shapes): with
+//     Cs % 64 == 0 and not transposed C where it fills the chip, B for 128-multiples of outputs, D for
+//     64 outputs; else E for Nout <= 64 and A.
+// 11. stride-2 transposed gathers on A / E with one statistics group walk their rows by output parity
+//     class, only that class's taps; accumulating launches whose epilogue adds nothing of its own (no
+//     bias, statistics or BN reduce) skip the tap-less classes.
+// 12. plain gathers on the upper-case DMA tiles that would leave the chip under-filled (small M: STF
+//     layer4 at 8 x 8, LSTM backward GEMMs) split K: slices until ~256 workgroups, each keeping >= 8
+//     K steps, at most 8.  STF_SPLITK=0 disables it.
+Route route_of(const stf_igemm_args* a, bool with_stats) {
   const stf_conv_geom& c = a->g;
-  const bool plain = !a->lstm && !a->scatter2x2 && !c.transposed;
-  if (c8_halo(a) && forced_cfg() == '0') return 'K';     // 8-channel network input, 3x3
-  if (dma_enabled() && dma_ok && plain && c.Cs == 8 && forced_cfg() != 'R')   // 8-channel network inputs
-    return a->Nout <= 64 ? 'e' : 'a';
-  if (!dma_enabled() || !dma_ok || c.Cs % 32) return 'R';
+  Route r;
   const char f = forced_cfg();
-  const bool bk64 = c.Cs % 64 == 0;
-  if (a->lstm) {
-    // LSTM steps (1x1 GEMM, K = 2C): the 128 x 128 tile (any tile gives the same gates -- the
-    // same MFMA sequence over ascending K -- so the backward recompute may run another tile)
-    return 'A';
-  }
-  const bool halo_ok = plain && c.R == 3 && c.S == 3 && c.stride == 1 && c.pad == 1 && c.Hd == c.Hs &&
-                       c.Wd == c.Ws && a->Nout % 64 == 0;
-  if (f == 'H' && halo_ok) return 'H';
-  // auto: the halo kernel for full-size 3x3 layers ('L' = auto over the linear kernels only)
-  if (f == '0' && halo_ok && (c.Wd >= 32 || (c.Wd >= HALO_MIN_W && a->Nout <= 256))) return 'H';
-  // 16 x 16 layers with more output channels (UNet's bottleneck): the two-image halo tiles
-  if (f == '0' && halo_ok && a->Nout > 256 && halo_ix(a, a->stats != nullptr) == 2) return 'H';
-  if (f == '0' && halo_ok && halo8(a)) return 'H';
-  if (f != '0' && f != 'H' && f != 'L') {
-    if (f == 'A' || f == 'E') return (f == 'E' && !(a->Nout <= 64 && !a->lstm)) ? 'A' : f;
-    if ((plain || a->scatter2x2) && bk64 && !a->lstm && !c.transposed) return f;
-  }
-  if ((plain || (a->scatter2x2 && !c.transposed && !a->lstm)) && bk64) {
-    // measured per layer (tools/bench_layers.py, cfg2 shapes): C where it fills the chip,
-    // B for 128-multiples, D for 64 output channels
-    const long M = (long)c.N * c.Hd * c.Wd;
-    const long blocks_c = ((M + 255) / 256) * ((a->Nout + 255) / 256);
-    if (a->Nout % 256 == 0 && blocks_c >= 240) return 'C';
-    if (a->Nout % 128 == 0) return 'B';
-    if (a->Nout == 64) return 'D';
-  }
-  if (a->Nout <= 64 && !a->lstm) return 'E';
-  return 'A';
-}
+  const long M = (long)c.N * c.Hd * c.Wd;
+  const long Mg = a->group_rows > 0 ? a->group_rows : M;
+  const long hw = (long)c.Hd * c.Wd, imgs = hw > 0 ? Mg / hw : 0;      // images per statistics group
+  const int lstm_epi = a->lstm ? (a->lstm->backward ? 2 : 1) : 0;
+  const bool plain = !a->lstm && !a->scatter2x2 && !c.transposed;
+  const bool dma_ok = (uint64_t)c.N * c.Hs * c.Ws * c.src_cstride * 2 < 0xFFFFFF00ull &&
+                      (uint64_t)a->Nout * c.R * c.S * c.Cs * 2 < 0xFFFFFF00ull;
+  const bool conv3 = plain && c.R == 3 && c.S == 3 && c.stride == 1 && c.pad == 1 && c.Hd == c.Hs && c.Wd == c.Ws;
+  const bool c8 = f == '0' && conv3 && !a->bnr && !a->accumulate && c.Cs == 8 && c.src_cstride % 8 == 0 &&
+                  a->Nout == 64 && a->dst_cstride % 8 == 0 && ((uintptr_t)a->dst & 15) == 0 &&
+                  (uint64_t)c.N * c.Hd * c.Wd * a->dst_cstride * 2 < 0xFFFFFF00ull;
+  const bool four = c.Hd == 8 && c.Wd == 8 && c.N % 4 == 0 && a->Nout % 64 == 0 && c.Cs % 32 == 0 && imgs % 4 == 0;
+  const bool two = !four && (with_stats || a->Nout > 256) && c.Hd == 16 && c.Wd == 16 && c.N % 2 == 0 && imgs % 2 == 0;
+  const bool halo = conv3 && a->Nout % 64 == 0 &&
+                    (f == 'H' || (f == '0' && (c.Wd >= 32 || (c.Wd >= HALO_MIN_W && a->Nout <= 256) ||
+                                               (a->Nout > 256 && two) || four)));
+  const char small = a->Nout <= 64 ? 'E' : 'A';
+  const bool bk64 = c.Cs % 64 == 0 && !c.transposed;
+  if (c8) r.kind = 'K';
+  else if (dma_ok && plain && c.Cs == 8) r.kind = a->Nout <= 64 ? 'e' : 'a';
+  else if (!dma_ok || c.Cs % 32) r.kind = 'R';
+  else if (a->lstm) r.kind = 'A';
+  else if (halo) r.kind = 'H';
+  else if (f == 'A' || f == 'E') r.kind = f == 'E' ? small : 'A';
+  else if (f >= 'B' && f <= 'F' && bk64) r.kind = f;
+  else if (bk64 && a->Nout % 256 == 0 && ((M + 255) / 256) * ((a->Nout + 255) / 256) >= 240) r.kind = 'C';
+  else if (bk64 && a->Nout % 128 == 0) r.kind = 'B';
+  else if (bk64 && a->Nout == 64) r.kind = 'D';
+  else r.kind = small;
+  const char k = r.kind;
 
-Cfg cfg_of(char k) {
-  switch (k) {
-    case 'a': return CFG_A;
-    case 'e': return CFG_E;
-    case 'B': return CFG_B;
-    case 'C': return CFG_C;
-    case 'D': return CFG_D;
-    case 'E': return CFG_E;
-    case 'F': return CFG_F;
-    default: return CFG_A;
-  }
-}
-
-template <int BM, int BN, int WM, int WN, int BKK, int STAGES>
-void launch_dma(const Geo& g, bool trans, bool scatter, int lstm, bool c8, uint32_t src_bytes, hipStream_t s) {
-  dim3 grid(g.tpg * ((g.M + g.Mg - 1) / g.Mg), (g.Nout + BN - 1) / BN, g.ksplit), block(64 * WM * WN);
-#define STF_D(TR, SCA, E) \
-  hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, BKK, STAGES, TR, SCA, E>), grid, block, 0, s, g, src_bytes)
-  if (c8)
-    hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, BKK, STAGES, false, false, 0, true>), grid, block, 0, s, g,
-                       src_bytes);
-  else if (lstm == 2) STF_D(false, false, 2);
-  else if (lstm) STF_D(false, false, 1);
-  else if (scatter) STF_D(false, true, 0);
-  else if (trans) STF_D(true, false, 0);
-  else STF_D(false, false, 0);
-#undef STF_D
-}
-
-// plain forward gather (or its ConvT 2x2 scatter epilogue, or an LSTM step: lstm 1 =
-// cell, 2 = cell backward) on the 8-wave tiles
-template <int BM, int BN, int WM, int WN, int BKK, int STAGES>
-void launch_dma_plain(const Geo& g, bool scatter, uint32_t src_bytes, hipStream_t s, int lstm = 0) {
-  dim3 grid(g.tpg * ((g.M + g.Mg - 1) / g.Mg), (g.Nout + BN - 1) / BN, g.ksplit), block(64 * WM * WN);
-  if constexpr (lstm_bwd_lds<BM, BN>() <= 163840) {
-    if (lstm == 2) {
-      hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, BKK, STAGES, false, false, 2>), grid, block, 0, s, g,
-                         src_bytes);
-      return;
+  if (k == 'K') {
+    r.ty = (c.Hd + C8_T - 1) / C8_T;
+    r.tx = (c.Wd + C8_T - 1) / C8_T;
+    r.items = c.N * r.ty * r.tx;
+    r.grid = (int)std::min<long>(r.items, 2 * num_cus());             // two workgroups per CU
+    r.variant = find_variant('K', 0, 0, 0, 0);
+  } else if (k == 'H') {
+    r.ix = four ? 4 : two ? 2 : 1;
+    r.pw = c.Wd >= 32 ? HALO_PW : 16;
+    r.wide = r.ix == 1 && a->Nout % 128 == 0 && c.Wd >= 32;
+    r.ty = r.ix > 1 ? 1 : (c.Hd + HALO_PH - 1) / HALO_PH;
+    r.tx = r.ix > 1 ? 1 : (c.Wd + r.pw - 1) / r.pw;
+    r.items = (long)(c.N / r.ix) * r.ty * r.tx * (a->Nout / (r.wide ? 128 : 64));
+    // one workgroup per CU (160 KiB LDS each; the single-stage 8 x 8 kernel two)
+    r.grid = (int)std::min<long>(r.items, (long)num_cus() * (four ? 2 : 1));
+    r.direct = four ? 0 : with_stats ? 2 : 1;
+    r.bnr_fused = a->bnr && !four;
+    if (r.ix == 1 && !r.wide && r.grid > 0) {
+      const long run = imgs * r.ty * r.tx, per = r.items / r.grid + 1;   // items per (group, slice) key
+      r.defer = (!with_stats && !a->bnr) || (run > 0 && (per + run - 1) / run + 1 <= 2);
     }
+    const int d = r.bnr_fused ? 1 : r.direct;
+    static const int diag = stf::ablation_env("STF_HALO_DIAG");
+    if (four) r.variant = find_variant('4', 0, 0, 0, 0);
+    else if (r.wide) r.variant = find_variant('W', r.direct, r.bnr_fused, 0, 0);
+    else if (two) r.variant = find_variant('2', d, r.bnr_fused, 0, 0);
+    else if (r.pw == 16) r.variant = find_variant('h', d, r.bnr_fused, r.defer, 0);
+    else if ((diag == 2 || diag == 4) && !r.bnr_fused) r.variant = find_variant('H', diag == 4 ? 1 : d, 0, 0, diag);
+    else r.variant = find_variant('H', d, r.bnr_fused, r.defer, 0);
+  } else {
+    const bool reg = k == 'R';
+    r.bm = reg ? ((a->Nout <= 64 && !a->lstm) ? 256 : 128) : cfg_of(k).bm;
+    if (reg) r.variant = find_variant(r.bm == 256 ? 'S' : 'R', c.Cs % BK != 0, c.transposed != 0, a->scatter2x2 != 0, lstm_epi);
+    else r.variant = find_variant(k, c.transposed != 0, a->scatter2x2 != 0, lstm_epi, 0);
   }
-  if (lstm)
-    hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, BKK, STAGES, false, false, 1>), grid, block, 0, s, g,
-                       src_bytes);
-  else if (scatter)
-    hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, BKK, STAGES, false, true, 0>), grid, block, 0, s, g,
-                       src_bytes);
-  else
-    hipLaunchKernelGGL((igemm_dma_kernel<BM, BN, WM, WN, BKK, STAGES, false, false, 0>), grid, block, 0, s, g,
-                       src_bytes);
-}
-
-template <int BM, int BN, int WM, int WN>
-int launch_reg(const Geo& g, bool smallc, bool trans, bool scatter, int lstm, hipStream_t s) {
-  dim3 grid(g.tpg * ((g.M + g.Mg - 1) / g.Mg), (g.Nout + BN - 1) / BN), block(NT);
-#define STF_L(SC, TR, SCA, E) hipLaunchKernelGGL((igemm_kernel<BM, BN, WM, WN, SC, TR, SCA, E>), grid, block, 0, s, g)
-  if (lstm) {
-    if (smallc) return STF_EINVAL;
-    if (lstm == 2) STF_L(false, false, false, 2);
-    else STF_L(false, false, false, 1);
+  if (r.grid > 0) {
+    r.per = (int)(r.items / r.grid);
+    r.rem = (int)(r.items % r.grid);
   }
-  else if (scatter) { if (smallc) STF_L(true, false, true, 0); else STF_L(false, false, true, 0); }
-  else if (trans) { if (smallc) STF_L(true, true, false, 0); else STF_L(false, true, false, 0); }
-  else { if (smallc) STF_L(true, false, false, 0); else STF_L(false, false, false, 0); }
-#undef STF_L
-  STF_CHECK_LAUNCH();
-  return 0;
-}
 
-bool dma_fits(const stf_igemm_args* a) {
-  const stf_conv_geom& c = a->g;
-  const uint64_t src_bytes = (uint64_t)c.N * c.Hs * c.Ws * c.src_cstride * 2;
-  const uint64_t wgt_bytes = (uint64_t)a->Nout * c.R * c.S * c.Cs * 2;
-  return src_bytes < 0xFFFFFF00ull && wgt_bytes < 0xFFFFFF00ull;
-}
+  r.tpg = (int)((Mg + r.bm - 1) / r.bm);
+  if (c.transposed && c.stride == 2 && (k == 'A' || k == 'E') && Mg == M) {
+    r.par = a->accumulate && !a->bias && !with_stats && !a->bnr ? 2 : 1;
+    long blocks = 0;
+    for (int cl = 0; cl < 4; ++cl) {
+      const int ntap = ((c.R - (((cl >> 1) + c.pad) & 1) + 1) >> 1) * ((c.S - (((cl & 1) + c.pad) & 1) + 1) >> 1);
+      if (r.par == 2 && ntap == 0) continue;
+      blocks += ((long)c.N * ((c.Hd - (cl >> 1) + 1) >> 1) * ((c.Wd - (cl & 1) + 1) >> 1) + r.bm - 1) / r.bm;
+    }
+    r.tpg = (int)blocks;
+  }
+  static const bool splitk_on = stf::ab_switch("STF_SPLITK", 1) != 0;
+  if (splitk_on && plain && c.Cs != 8 && k >= 'A' && k <= 'F' && a->Nout % 8 == 0 && NT % (a->Nout / 8) == 0 &&
+      a->dst_cstride % 8 == 0 && ((uintptr_t)a->dst & 15) == 0) {
+    const Cfg t = cfg_of(k);
+    const long blocks = (M / Mg) * ((Mg + t.bm - 1) / t.bm) * ((a->Nout + t.bn - 1) / t.bn);
+    const long kt = (long)c.R * c.S * c.Cs / t.bkk;
+    if (blocks < 192 && kt >= 16) r.ksplit = (int)std::max<long>(1, std::min<long>({(256 + blocks - 1) / blocks, kt / 8, 8}));
+  }
+  if (r.ksplit > 1) r.ws_bytes = (size_t)r.ksplit * c.N * c.Hd * c.Wd * a->Nout * sizeof(float);
 
-int pick_mtile(const stf_igemm_args* a) {
-  const char k = choose(a, dma_fits(a));
-  if (k == 'R') return (a->Nout <= 64 && !a->lstm) ? 256 : 128;
-  return cfg_of(k).bm;
-}
-
-void halo_tiles(const stf_conv_geom& c, int& ty, int& tx) {
-  ty = (c.Hd + halo_ph() - 1) / halo_ph();
-  tx = (c.Wd + halo_pw(c) - 1) / halo_pw(c);
-}
-
-// images per halo tile: 2 for 16 x 16 layers (conv3x3_halo2_kernel: two images side by side
-// in one 16 x 32 tile) when the statistics groups hold an even number of images.
-// STF_HALO2=0: one 16 x 16 image per tile; 1 (default): forward convs (with BN statistics)
-// only -- the dgrads run beside the side-stream weight gradients, and the 160 KiB workgroup
-// of the wide tile cannot share a CU with them (128 KiB for the 16 x 16 tile); 2: all
-// with_stats: the launch writes BN statistics (the size queries pass what the launch will do:
-// stf_igemm_stat_tiles is asked before the statistics buffer exists)
-int halo_ix(const stf_igemm_args* a, bool with_stats) {
-  static const int mode = stf::ab_switch("STF_HALO2", 1);
-  const stf_conv_geom& c = a->g;
-  if (halo8(a)) return 4;
-  // (mode 1: two images per tile for the forward convs with statistics, and for every conv with more
-  // than 256 output channels -- the UNet bottleneck, whose dgrads run 4-22 % faster on them than on
-  // single-image tiles or the linear kernels, tools/bench_layers.py)
-  if (mode == 0 || (mode == 1 && !with_stats && a->Nout <= 256)) return 1;
-  if (c.Hd != 16 || c.Wd != 16 || c.N % 2) return 1;
-  const long M = (long)c.N * c.Hd * c.Wd;
-  const long Mg = a->group_rows > 0 ? a->group_rows : M;
-  return ((Mg / (c.Hd * c.Wd)) % 2) ? 1 : 2;
-}
-
-long halo_items_ix(const stf_igemm_args* a, int ix) {
-  int ty, tx;
-  halo_tiles(a->g, ty, tx);
-  if (ix > 1) ty = tx = 1;
-  return (long)(a->g.N / ix) * ty * tx * (a->Nout / (ix == 1 && halo_wide(a) ? 128 : 64));
-}
-
-// persistent halo grid: one workgroup per CU (160 KiB LDS each; the single-stage 8 x 8 kernel two)
-int halo_grid(const stf_igemm_args* a, int ix) {
-  const long items = halo_items_ix(a, ix);
-  return (int)std::min<long>(items, (long)num_cus() * (ix == 4 ? 2 : 1));
-}
-
-// Split-K factor for a plain gather on the linear DMA kernels that would leave the
-// chip under-filled (small-M layers: STF layer4 at 8x8, LSTM backward GEMMs):
-// K slices until ~256 workgroups, each keeping >= 8 K steps.  1 = no split.
-// STF_SPLITK=0 disables it (A/B).
-int ksplit_of(const stf_igemm_args* a) {
-  static const bool on = stf::ab_switch("STF_SPLITK", 1) != 0;
-  const stf_conv_geom& c = a->g;
-  const char k = choose(a, dma_fits(a));
-  if (!on || a->lstm || a->scatter2x2 || c.transposed || c.Cs == 8) return 1;
-  if (!(k == 'A' || k == 'B' || k == 'C' || k == 'D' || k == 'E' || k == 'F')) return 1;
-  if (a->Nout % 8 || NT % (a->Nout / 8) || a->dst_cstride % 8 || ((uintptr_t)a->dst & 15)) return 1;
-  const Cfg f = cfg_of(k);
-  const long M = (long)c.N * c.Hd * c.Wd;
-  const long Mg = a->group_rows > 0 ? a->group_rows : M;
-  const long blocks = (M / Mg) * ((Mg + f.bm - 1) / f.bm) * ((a->Nout + f.bn - 1) / f.bn);
-  const long kt = (long)c.R * c.S * c.Cs / f.bkk;
-  if (blocks >= 192 || kt < 16) return 1;
-  long ks = (256 + blocks - 1) / blocks;
-  if (ks > kt / 8) ks = kt / 8;
-  if (ks > 8) ks = 8;
-  return ks < 2 ? 1 : (int)ks;
-}
-
-// BatchNorm partial-statistics rows per group for the kernel that will run
-int stat_tiles(const stf_igemm_args* a) {
-  const stf_conv_geom& c = a->g;
-  const long M = (long)c.N * c.Hd * c.Wd;
-  const long Mg = a->group_rows > 0 ? a->group_rows : M;
-  if (choose(a, dma_fits(a)) == 'H') return halo_grid(a, halo_ix(a, true));
-  if (choose(a, dma_fits(a)) == 'K') return c8_grid(a);
-  if (ksplit_of(a) > 1) return (int)((Mg + sk_rows(a->Nout) - 1) / sk_rows(a->Nout));
-  const int bm = pick_mtile(a);
-  return (int)((Mg + bm - 1) / bm);
+  if (k == 'H' || k == 'K') r.stat_tiles = r.grid;
+  else if (r.ksplit > 1) r.stat_tiles = (int)((Mg + sk_rows(a->Nout) - 1) / sk_rows(a->Nout));
+  else r.stat_tiles = (int)((Mg + r.bm - 1) / r.bm);
+  const int groups = a->group_rows > 0 ? (int)std::max<long>(1, M / a->group_rows) : 1;
+  r.bnr_tiles = r.bnr_fused ? r.grid : stf_bn_bwd_tiles(c.N, c.Hd, c.Wd, a->Nout, groups, 0);
+  return r;
 }
 
 }  // namespace
 
-extern "C" int stf_igemm_stat_tiles(const stf_igemm_args* a) { return stat_tiles(a); }
+// BatchNorm partial-statistics rows per group for the kernel that will run
+extern "C" int stf_igemm_stat_tiles(const stf_igemm_args* a) { return route_of(a, true).stat_tiles; }
 
-extern "C" size_t stf_igemm_ws_bytes(const stf_igemm_args* a) {
-  const int ks = ksplit_of(a);
-  if (ks < 2) return 0;
-  const stf_conv_geom& c = a->g;
-  return (size_t)ks * c.N * c.Hd * c.Wd * a->Nout * sizeof(float);
-}
+extern "C" size_t stf_igemm_ws_bytes(const stf_igemm_args* a) { return route_of(a, a->stats != nullptr).ws_bytes; }
 
-extern "C" int stf_igemm_bnr_tiles(const stf_igemm_args* a) {
-  const stf_conv_geom& c = a->g;
-  const long M = (long)c.N * c.Hd * c.Wd;
-  const int groups = a->group_rows > 0 ? (int)(M / a->group_rows) : 1;
-  if (bnr_fused(a, choose(a, dma_fits(a)))) return halo_grid(a, halo_ix(a, false));
-  return stf_bn_bwd_tiles(c.N, c.Hd, c.Wd, a->Nout, groups, 0);
-}
+extern "C" int stf_igemm_bnr_tiles(const stf_igemm_args* a) { return route_of(a, false).bnr_tiles; }
 
 // Name of the device kernel these args run (as rocprofv3 prints it), for timers
 extern "C" const char* stf_igemm_kernel_name(const stf_igemm_args* a) {
-  static thread_local char buf[128];
-  const stf_conv_geom& c = a->g;
-  const char k = choose(a, dma_fits(a));
-  const int epi = a->lstm ? (a->lstm->backward ? 2 : 1) : 0;
-  const char* tr = c.transposed ? "true" : "false";
-  const char* sc = a->scatter2x2 ? "true" : "false";
-  switch (k) {
-    case 'K': snprintf(buf, sizeof buf, "conv3x3_c8_kernel"); break;
-    case 'H':
-      if (halo8(a))
-        snprintf(buf, sizeof buf, "conv3x3_halo4_kernel<0>");
-      else if (halo_wide(a))
-        snprintf(buf, sizeof buf, "conv3x3_wide_kernel<%d, %s>", a->stats ? 2 : 1, a->bnr ? "true" : "false");
-      else if (halo_ix(a, a->stats != nullptr) > 1)
-        snprintf(buf, sizeof buf, "conv3x3_halo2_kernel<%d, %s, %s>", halo_direct(a) ? (a->stats ? 2 : 1) : 0,
-                 bnr_fused(a, k) ? "true" : "false", halo_defer(a) ? "true" : "false");
-      else
-        snprintf(buf, sizeof buf, "conv3x3_halo_kernel<16, %d, 8, 2, 0, %d, %s, %s>", halo_pw(c),
-                 halo_direct(a) ? (a->stats ? 2 : 1) : 0, bnr_fused(a, k) ? "true" : "false",
-                 halo_defer(a) ? "true" : "false");
-      break;
-    case 'A': snprintf(buf, sizeof buf, "igemm_dma_kernel<128, 128, 2, 2, 32, 4, %s, %s, %d, false>", tr, sc, epi); break;
-    case 'E': snprintf(buf, sizeof buf, "igemm_dma_kernel<256, 64, 4, 1, 32, 4, %s, %s, %d, false>", tr, sc, epi); break;
-    case 'a': snprintf(buf, sizeof buf, "igemm_dma_kernel<128, 128, 2, 2, 32, 4, false, false, 0, true>"); break;
-    case 'e': snprintf(buf, sizeof buf, "igemm_dma_kernel<256, 64, 4, 1, 32, 4, false, false, 0, true>"); break;
-    case 'B': snprintf(buf, sizeof buf, "igemm_dma_kernel<256, 128, 4, 2, 64, 3, false, %s, %d, false>", sc, epi); break;
-    case 'C': snprintf(buf, sizeof buf, "igemm_dma_kernel<256, 256, 2, 4, 64, 2, false, %s, %d, false>", sc, epi); break;
-    case 'D': snprintf(buf, sizeof buf, "igemm_dma_kernel<512, 64, 8, 1, 64, 2, false, %s, %d, false>", sc, epi); break;
-    case 'F': snprintf(buf, sizeof buf, "igemm_dma_kernel<128, 256, 2, 4, 32, 2, false, %s, 0, false>", sc); break;
-    default: {
-      const bool small = (a->Nout <= 64 && !a->lstm);
-      snprintf(buf, sizeof buf, "igemm_kernel<%s, %s, %s, %s, %d>", small ? "256, 64, 4, 1" : "128, 128, 2, 2",
-               (c.Cs % BK) ? "true" : "false", tr, sc, epi);
-    }
-  }
-  return buf;
+  const Route r = route_of(a, a->stats != nullptr);
+  return r.variant < 0 ? "(no kernel)" : VARIANTS[r.variant].name;
 }
-
-static int igemm_launch(const stf_igemm_args* a, stf_stream_t stream);
 
 extern "C" int stf_igemm(const stf_igemm_args* a, stf_stream_t stream) {
-  const int rc = igemm_launch(a, stream);
-  if (rc || !a->bnr || bnr_fused(a, choose(a, dma_fits(a)))) return rc;
-  // unfused: one stf_bn_bwd_reduce pass over the stored dz (same partial layout)
-  const stf_conv_geom& c = a->g;
-  const long M = (long)c.N * c.Hd * c.Wd;
-  if (M <= 0) return 0;
-  const int groups = a->group_rows > 0 ? (int)(M / a->group_rows) : 1;
-  return stf_bn_bwd_reduce(a->dst, a->dst_cstride, nullptr, a->bnr->y, a->bnr->y_cstride, c.N, c.Hd, c.Wd, a->Nout,
-                           groups, a->bnr->scale, a->bnr->shift, a->bnr->mean, a->bnr->invstd, a->bnr->relu ? 1 : 0,
-                           nullptr, 0, nullptr, a->bnr->partial, stream);
-}
-
-static int igemm_launch(const stf_igemm_args* a, stf_stream_t stream) {
   const stf_conv_geom& c = a->g;
   if (a->Nout % 8 || c.Cs % 8 || c.src_cstride % 8 || a->dst_cstride % 4) return STF_EINVAL;
   if (c.transposed && !(c.stride == 1 || c.stride == 2)) return STF_EINVAL;
@@ -2672,27 +2586,20 @@ static int igemm_launch(const stf_igemm_args* a, stf_stream_t stream) {
   g.Hd = c.Hd; g.Wd = c.Wd; g.R = c.R; g.S = c.S; g.st = c.stride; g.pad = c.pad;
   g.M = c.N * c.Hd * c.Wd; g.K = c.R * c.S * c.Cs; g.Nout = a->Nout; g.dcs = a->dst_cstride;
   if (g.M <= 0) return 0;
-  const int bm = pick_mtile(a);
   g.Mg = a->group_rows > 0 ? a->group_rows : g.M;
   if (g.M % g.Mg) return STF_EINVAL;
-  g.tpg = (g.Mg + bm - 1) / bm;
   g.accumulate = a->accumulate;
   g.c_prev = nullptr; g.c_out = nullptr; g.h_out = nullptr; g.hcs = 0; g.gates = nullptr;
   g.bnr_y = nullptr; g.bnr_ycs = 0; g.bnr_scale = g.bnr_shift = g.bnr_mean = g.bnr_invstd = nullptr;
   g.bnr_relu = 0; g.bnr_part = nullptr;
-  g.par = 0;
   g.ksplit = 1; g.ws = nullptr;
-  static const int wkeep = stf::ab_switch("STF_HALO_WKEEP", 1);
-  g.wkeep = wkeep;
-  static const int full = stf::ab_switch("STF_HALO_FULL", 1);
-  g.full = full;
+  g.wkeep = 1; g.full = 1;       // always on; still kernel arguments
   if (a->bnr) {
     g.bnr_y = (const uint16_t*)a->bnr->y; g.bnr_ycs = a->bnr->y_cstride;
     g.bnr_scale = a->bnr->scale; g.bnr_shift = a->bnr->shift; g.bnr_mean = a->bnr->mean;
     g.bnr_invstd = a->bnr->invstd; g.bnr_relu = a->bnr->relu; g.bnr_part = a->bnr->partial;
   }
   g.l_dh = nullptr; g.l_dhcs = 0; g.l_dcn = nullptr; g.l_dcp = nullptr; g.l_dg = nullptr;
-  int lstm_epi = 0;
   if (a->lstm) {
     const stf_lstm_epi& l = *a->lstm;
     if (a->scatter2x2 || c.transposed || a->Nout % 4 || !l.c_out) return STF_EINVAL;
@@ -2700,135 +2607,32 @@ static int igemm_launch(const stf_igemm_args* a, stf_stream_t stream) {
       if (!l.dh || !l.dc_prev || !l.dgates || ((uintptr_t)l.dgates & 7)) return STF_EINVAL;
       g.l_dh = (const uint16_t*)l.dh; g.l_dhcs = l.dh_cstride; g.l_dcn = l.dc_next; g.l_dcp = l.dc_prev;
       g.l_dg = (uint16_t*)l.dgates;
-      lstm_epi = 2;
-    } else {
-      if (!l.h_out) return STF_EINVAL;
-      lstm_epi = 1;
+    } else if (!l.h_out) {
+      return STF_EINVAL;
     }
     g.c_prev = l.c_prev; g.c_out = l.c_out; g.h_out = (uint16_t*)l.h_out;
     g.hcs = l.h_cstride; g.gates = l.gates;
   }
-  const bool smallc = (c.Cs % BK) != 0;
+  const Route r = route_of(a, a->stats != nullptr);
+  if (r.variant < 0) return STF_EINVAL;
+  const Variant& v = VARIANTS[r.variant];
+  g.tpg = r.tpg;
+  g.par = r.par;
+  if (r.ksplit > 1) {
+    if (!a->ws || ((uintptr_t)a->ws & 15)) return STF_EINVAL;
+    g.ksplit = r.ksplit; g.ws = a->ws;
+  }
   hipStream_t s = (hipStream_t)stream;
   const uint32_t src_bytes = (uint32_t)((uint64_t)c.N * c.Hs * c.Ws * c.src_cstride * 2);
-  const char k = choose(a, dma_fits(a));
-  if (k == 'K') {
+  const dim3 lin_grid(g.tpg * ((g.M + g.Mg - 1) / g.Mg), (g.Nout + v.bn - 1) / v.bn, g.ksplit);
+  if (v.c8 || v.tile) {
     if ((g.Mg % (c.Hd * c.Wd)) != 0) return STF_EINVAL;
-    const int TY = (c.Hd + C8_T - 1) / C8_T, TX = (c.Wd + C8_T - 1) / C8_T;
-    const int tiles = c8_tiles(c), grid = c8_grid(a);
-    // whole-pixel-row stores (STF_C8_FULL=0: the half-row stores, A/B)
-    static const int c8_full = stf::ab_switch("STF_C8_FULL", 1) != 0;
-    hipLaunchKernelGGL(conv3x3_c8_kernel, dim3(grid), dim3(256), 0, s, g, TY, TX, tiles / grid, tiles % grid,
-                       c8_full);
-    STF_CHECK_LAUNCH();
-    return 0;
-  }
-  if (k == 'H') {
-    if ((g.Mg % (c.Hd * c.Wd)) != 0) return STF_EINVAL;
-    int ty, tx;
-    halo_tiles(c, ty, tx);
-    const int ix = halo_ix(a, a->stats != nullptr);
-    if (ix > 1) ty = tx = 1;
-    const long items = halo_items_ix(a, ix);
-    const int grid = halo_grid(a, ix);
-    static const int diag = stf::ablation_env("STF_HALO_DIAG");
-#define STF_H(D) hipLaunchKernelGGL((conv3x3_halo_kernel<16, HALO_PW, 8, 2, D>), dim3(grid), dim3(512), 0, s, g, \
-                                   src_bytes, ty, tx, (int)(items / grid), (int)(items % grid))
-    const int d = halo_direct(a) ? (a->stats ? 2 : 1) : 0;
-    const int per = (int)(items / grid), rem = (int)(items % grid);
-    const bool dfr = halo_defer(a);
-#define STF_HL(PWV, D, B) do {                                                                                      \
-      if (dfr) hipLaunchKernelGGL((conv3x3_halo_kernel<16, PWV, 8, 2, 0, D, B, true>), dim3(grid), dim3(512), 0, s, g, \
-                                  src_bytes, ty, tx, per, rem);                                                        \
-      else hipLaunchKernelGGL((conv3x3_halo_kernel<16, PWV, 8, 2, 0, D, B>), dim3(grid), dim3(512), 0, s, g,          \
-                              src_bytes, ty, tx, per, rem);                                                            \
-    } while (0)
-#define STF_H2(D, B) do {                                                                                           \
-      if (dfr) hipLaunchKernelGGL((conv3x3_halo2_kernel<D, B, true>), dim3(grid), dim3(512), 0, s, g, src_bytes, ty,  \
-                                  tx, per, rem);                                                                       \
-      else hipLaunchKernelGGL((conv3x3_halo2_kernel<D, B>), dim3(grid), dim3(512), 0, s, g, src_bytes, ty, tx, per,   \
-                              rem);                                                                                    \
-    } while (0)
-    if (ix == 1 && halo_wide(a)) {
-      if (d == 2) hipLaunchKernelGGL((conv3x3_wide_kernel<2>), dim3(grid), dim3(512), 0, s, g, src_bytes, ty, tx, per, rem);
-      else if (a->bnr) hipLaunchKernelGGL((conv3x3_wide_kernel<1, true>), dim3(grid), dim3(512), 0, s, g, src_bytes, ty, tx,
-                                          per, rem);
-      else hipLaunchKernelGGL((conv3x3_wide_kernel<1>), dim3(grid), dim3(512), 0, s, g, src_bytes, ty, tx, per, rem);
-    } else if (ix == 4) {
-      hipLaunchKernelGGL((conv3x3_halo4_kernel<0>), dim3(grid), dim3(256), 0, s, g, src_bytes, ty, tx, per, rem);
-    } else if (ix > 1) {
-      if (bnr_fused(a, k)) STF_H2(1, true);
-      else if (d == 2) STF_H2(2, false);
-      else if (d == 1) STF_H2(1, false);
-      else STF_H2(0, false);
-    } else if (bnr_fused(a, k)) {
-      if (halo_pw(c) == 16) STF_HL(16, 1, true);
-      else STF_HL(HALO_PW, 1, true);
-    } else if (halo_pw(c) == 16) {
-      if (d == 2) STF_HL(16, 2, false);
-      else if (d == 1) STF_HL(16, 1, false);
-      else STF_HL(16, 0, false);
-    } else if (diag == 4) {                        // cycle buckets (tools/halo_timeline.py), no statistics
-      hipLaunchKernelGGL((conv3x3_halo_kernel<16, HALO_PW, 8, 2, 4, 1, false>), dim3(grid), dim3(512), 0, s, g,
-                         src_bytes, ty, tx, per, rem);
-    } else if (diag == 2) {                        // ablation: no DMA reloads after the first stage
-      if (d == 2) hipLaunchKernelGGL((conv3x3_halo_kernel<16, HALO_PW, 8, 2, 2, 2, false>), dim3(grid), dim3(512), 0,
-                                     s, g, src_bytes, ty, tx, per, rem);
-      else if (d == 1) hipLaunchKernelGGL((conv3x3_halo_kernel<16, HALO_PW, 8, 2, 2, 1, false>), dim3(grid), dim3(512),
-                                          0, s, g, src_bytes, ty, tx, per, rem);
-      else STF_H(2);
-    } else if (d == 2) STF_HL(HALO_PW, 2, false);
-    else if (d == 1) STF_HL(HALO_PW, 1, false);
-    else STF_H(0);
-#undef STF_H2
-#undef STF_HL
-#undef STF_H
-    STF_CHECK_LAUNCH();
-    return 0;
-  }
-  // stride-2 transposed gathers: rows by output parity class, only that class's taps
-  // (STF_TRANS_PAR=0: all nine taps, 3/4 of them masked)
-  static const bool par_on = stf::ab_switch("STF_TRANS_PAR", 1) != 0;
-  if (par_on && c.transposed && c.stride == 2 && (k == 'A' || k == 'E') && g.Mg == g.M) {
-    const int bmp = cfg_of(k).bm;
-    // accumulating: tap-less classes add nothing, skip them (STF_TRANS_SKIP=0: launch them, A/B)
-    static const bool skip_on = stf::ab_switch("STF_TRANS_SKIP", 1) != 0;
-    // (only when the epilogue adds nothing of its own: no bias, statistics or fused BN reduce)
-    const int par = a->accumulate && skip_on && !a->bias && !a->stats && !a->bnr ? 2 : 1;
-    long blocks = 0;
-    for (int cl = 0; cl < 4; ++cl) {
-      const int ntap = ((c.R - (((cl >> 1) + c.pad) & 1) + 1) >> 1) * ((c.S - (((cl & 1) + c.pad) & 1) + 1) >> 1);
-      if (par == 2 && ntap == 0) continue;
-      blocks += ((long)c.N * ((c.Hd - (cl >> 1) + 1) >> 1) * ((c.Wd - (cl & 1) + 1) >> 1) + bmp - 1) / bmp;
-    }
-    g.par = par;
-    g.tpg = (int)blocks;
-  }
-  const int ks = ksplit_of(a);
-  if (ks > 1) {
-    if (!a->ws || ((uintptr_t)a->ws & 15)) return STF_EINVAL;
-    g.ksplit = ks; g.ws = a->ws;
-  }
-  switch (k) {
-    case 'A': launch_dma<128, 128, 2, 2, 32, 4>(g, c.transposed, a->scatter2x2, lstm_epi, false, src_bytes, s); break;
-    case 'E': launch_dma<256, 64, 4, 1, 32, 4>(g, c.transposed, a->scatter2x2, lstm_epi, false, src_bytes, s); break;
-    case 'a': launch_dma<128, 128, 2, 2, 32, 4>(g, false, false, false, true, src_bytes, s); break;
-    case 'e': launch_dma<256, 64, 4, 1, 32, 4>(g, false, false, false, true, src_bytes, s); break;
-    case 'B': launch_dma_plain<256, 128, 4, 2, 64, 3>(g, a->scatter2x2, src_bytes, s, lstm_epi); break;
-    case 'C': launch_dma_plain<256, 256, 2, 4, 64, 2>(g, a->scatter2x2, src_bytes, s, lstm_epi); break;
-    case 'D': launch_dma_plain<512, 64, 8, 1, 64, 2>(g, a->scatter2x2, src_bytes, s, lstm_epi); break;
-    case 'F': {                                    // plain gathers and the ConvT scatter only
-      if (lstm_epi) return STF_EINVAL;
-      dim3 grid(g.tpg * ((g.M + g.Mg - 1) / g.Mg), (g.Nout + 255) / 256, g.ksplit), block(512);
-      if (a->scatter2x2)
-        hipLaunchKernelGGL((igemm_dma_kernel<128, 256, 2, 4, 32, 2, false, true, 0>), grid, block, 0, s, g, src_bytes);
-      else
-        hipLaunchKernelGGL((igemm_dma_kernel<128, 256, 2, 4, 32, 2, false, false, 0>), grid, block, 0, s, g, src_bytes);
-      break;
-    }
-    default:
-      if (bm == 256) return launch_reg<256, 64, 4, 1>(g, smallc, c.transposed, a->scatter2x2, lstm_epi, s);
-      return launch_reg<128, 128, 2, 2>(g, smallc, c.transposed, a->scatter2x2, lstm_epi, s);
+    if (v.c8) hipLaunchKernelGGL(v.c8, dim3(r.grid), dim3(v.threads), 0, s, g, r.ty, r.tx, r.per, r.rem, 1);
+    else hipLaunchKernelGGL(v.tile, dim3(r.grid), dim3(v.threads), 0, s, g, src_bytes, r.ty, r.tx, r.per, r.rem);
+  } else if (v.dma) {
+    hipLaunchKernelGGL(v.dma, lin_grid, dim3(v.threads), 0, s, g, src_bytes);
+  } else {
+    hipLaunchKernelGGL(v.reg, lin_grid, dim3(v.threads), 0, s, g);
   }
   STF_CHECK_LAUNCH();
   if (g.ksplit > 1) {
@@ -2836,5 +2640,11 @@ static int igemm_launch(const stf_igemm_args* a, stf_stream_t stream) {
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3(tpg * (g.M / g.Mg)), dim3(NT), 0, s, g, tpg);
     STF_CHECK_LAUNCH();
   }
-  return 0;
+  if (!a->bnr || r.bnr_fused) return 0;
+  // unfused: one stf_bn_bwd_reduce pass over the stored dz (same partial layout)
+  const int groups = a->group_rows > 0 ? g.M / a->group_rows : 1;
+  return stf_bn_bwd_reduce(a->dst, a->dst_cstride, nullptr, a->bnr->y, a->bnr->y_cstride, c.N, c.Hd, c.Wd, a->Nout,
+                           groups, a->bnr->scale, a->bnr->shift, a->bnr->mean, a->bnr->invstd, a->bnr->relu ? 1 : 0,
+                           nullptr, 0, nullptr, a->bnr->partial, stream);
 }
+

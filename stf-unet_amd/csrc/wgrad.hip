@@ -701,9 +701,7 @@ bool big_tile(const stf_wgrad_args* a) { return a->Nout % 128 == 0 && a->g.Cs % 
 
 // fused-tap kernel: 3x3, stride 1, pad 1, 64-multiples of channels, W >= 8
 int fused_pw(const stf_wgrad_args* a) {
-  static const bool enabled = stf::ab_switch("STF_WGRAD_FUSED", 1) != 0;
   const stf_conv_geom& c = a->g;
-  if (!enabled) return 0;
   if (c.R != 3 || c.S != 3 || c.stride != 1 || c.pad != 1 || c.Hd != c.Hs || c.Wd != c.Ws) return 0;
   if (a->Nout % 64 || c.Cs % 64 || c.Wd < 8) return 0;
   return c.Wd >= 16 ? 16 : 8;
@@ -711,9 +709,8 @@ int fused_pw(const stf_wgrad_args* a) {
 
 // ConvT 2x2 / stride 2 fused-tap kernel (x = the 2x larger gradient tensor)
 int fused22_pw(const stf_wgrad_args* a) {
-  static const bool enabled = stf::ab_switch("STF_WGRAD_FUSED", 1) != 0;
   const stf_conv_geom& c = a->g;
-  if (!enabled || c.R != 2 || c.S != 2 || c.stride != 2 || c.pad != 0 || c.transposed) return 0;
+  if (c.R != 2 || c.S != 2 || c.stride != 2 || c.pad != 0 || c.transposed) return 0;
   if (c.Hs != 2 * c.Hd || c.Ws != 2 * c.Wd || a->Nout % 64 || c.Cs % 64 || c.Wd < 8) return 0;
   return c.Wd >= 16 ? 16 : 8;
 }
@@ -726,12 +723,10 @@ int fused22_nb(const stf_wgrad_args* a) {
   return (a->Nout % 128 == 0 && a->Nout >= 256) ? 2 : 1;
 }
 
-// the 8-channel-input 3x3 layer (conv3x3_c8_kernel's weight gradient; STF_WGRAD_C8=0: the
-// generic wgrad_kernel<64, 96, 64, true>, A/B)
+// the 8-channel-input 3x3 layer (conv3x3_c8_kernel's weight gradient)
 bool fused_c8(const stf_wgrad_args* a) {
-  static const bool enabled = stf::ab_switch("STF_WGRAD_C8", 1) != 0;
   const stf_conv_geom& c = a->g;
-  return enabled && c.R == 3 && c.S == 3 && c.stride == 1 && c.pad == 1 && c.Hd == c.Hs && c.Wd == c.Ws &&
+  return c.R == 3 && c.S == 3 && c.stride == 1 && c.pad == 1 && c.Hd == c.Hs && c.Wd == c.Ws &&
          c.Cs == 8 && c.src_cstride == 8 && a->Nout == 64 && !c.transposed;
 }
 
