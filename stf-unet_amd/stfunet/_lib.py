@@ -278,9 +278,6 @@ def check(rc, what=""):
         raise HipError(f"{what}: {msg} (code {rc})")
 
 
-_FN = {}
-
-
 def call(name, *args):
     f = _FN.get(name)
     if f is None:

@@ -9,6 +9,7 @@ Every wrapper validates shapes on the host before launching (a kernel that
 walks off a buffer can take the whole GPU down) and launches on torch's
 current stream.  Workspaces come from torch's caching allocator.
 """
+import contextlib
 import ctypes
 import os
 from dataclasses import dataclass
@@ -119,8 +120,9 @@ def timed_block(tag):
     t = TIMER
     if t is not None and t.only is None:
         return t.block(tag)
-    import contextlib
     return contextlib.nullcontext()
+
+
 _NAMES = {}    # launch signature -> device kernel name (stf_*_kernel_name)
 
 
@@ -305,7 +307,7 @@ def _pack_into(w, mode, cpad, out, launch=True):
     d0, d1, R, S = w.shape
     n = d0 * R * S * cpad if mode == 0 else d0 * d1 * R * S
     if out is None:
-        out = torch.empty(n, dtype=sdt(), device=w.device)
+        out = empty(n, sdt(), w.device)
     if launch:
         call("stf_pack_weight", _p(w), d0, d1, R, S, mode, cpad, _p(out), stream())
     return out
@@ -318,13 +320,17 @@ def pack_weight(w, mode, cpad=0, cache=True):
     address and would keep every dead temporary alive."""
     if cache and ACTIVE_PACKS is not None:
         return ACTIVE_PACKS.get(w, mode, cpad)
-    w = w.detach()
-    assert w.dtype == torch.float32 and w.is_contiguous()
-    d0, d1, R, S = w.shape
-    n = d0 * R * S * cpad if mode == 0 else d0 * d1 * R * S
-    out = empty(n, sdt(), w.device)
-    call("stf_pack_weight", _p(w), d0, d1, R, S, mode, cpad, _p(out), stream())
-    return out
+    return _pack_into(w.detach(), mode, cpad, None)
+
+
+def pad_weight(w, cpad):
+    """fp32 copy of the conv weight ``w`` [Cout][Cin][R][S] with its input channels zero padded to
+    ``cpad``, for the dgrad into a channel-padded source (the padded channels' gradient is
+    computed and dropped by the caller).  A per-call temporary: pack it with ``cache=False``."""
+    cout, cin, R, S = w.shape
+    wp = memset0(empty((cout, cpad, R, S), torch.float32, w.device))
+    copy_rows(w.detach(), cin * R * S, wp, cpad * R * S, cout, cin * R * S)
+    return wp
 
 
 # ------------------------------------------------------------------ implicit GEMM
@@ -396,36 +402,43 @@ def igemm(src: Feat, wgt, nout, dst: Feat, R, S, stride, pad, transposed=False, 
     if want_stats:
         stats = empty(groups * tiles * 2 * nout, torch.float32, dst.buf.device)
         a.stats = stats.data_ptr()
-    t = TIMER
-    if t is not None:
-        name = _kernel_name("stf_igemm_kernel_name", ("i", src.N, src.H, src.W, src.C, Hd, Wd, nout, R, S, stride,
-                                                      pad, transposed, scatter2x2, lstm is not None, groups,
-                                                      bnr is not None, want_stats), a)
-        if not t.wants(name):
-            t = None
     ws = None
     if nb:
         ws = empty(nb // 4, torch.float32, dst.buf.device)
         a.ws = ws.data_ptr()
-    ev = t.begin() if t is not None else None
-    if RECORDING:        # name the launch range for the plan's timed replays (bench roofline)
-        _plan_tag(a, "stf_igemm_kernel_name",
-                  ("i", src.N, src.H, src.W, src.C, Hd, Wd, nout, R, S, stride, pad, transposed, scatter2x2,
-                   lstm is not None, groups, bnr is not None, want_stats),
-                  2.0 * src.N * Hd * Wd * nout * R * S * src.C / (stride * stride if transposed else 1))
-    call("stf_igemm", ctypes.byref(a), stream())
-    if RECORDING:
-        call("stf_plan_tag_end")
-    if t is not None:
+
+    def info():
         macs = src.N * Hd * Wd * nout * R * S * src.C
-        t.end(ev, name, 2.0 * macs / (stride * stride if transposed else 1),
-              f"igemm M={src.N * Hd * Wd} N={nout} K={R * S * src.C} {R}x{S}/s{stride}{' T' if transposed else ''}"
-              f"{' lstm' if lstm is not None else ''}{' bnr' if bnr is not None else ''}")
+        return ("stf_igemm_kernel_name",
+                ("i", src.N, src.H, src.W, src.C, Hd, Wd, nout, R, S, stride, pad, transposed, scatter2x2,
+                 lstm is not None, groups, bnr is not None, want_stats),
+                2.0 * macs / (stride * stride if transposed else 1),
+                f"igemm M={src.N * Hd * Wd} N={nout} K={R * S * src.C} {R}x{S}/s{stride}{' T' if transposed else ''}"
+                f"{' lstm' if lstm is not None else ''}{' bnr' if bnr is not None else ''}")
+    _launch("stf_igemm", a, info)
     return stats, tiles
 
 
-def _plan_tag(a, fn, key, flops):
-    call("stf_plan_tag", _kernel_name(fn, key, a).encode(), float(flops))
+def _launch(fn, a, info):
+    """call(fn, &a, stream) for the two GEMM families, bracketed with ``TIMER``'s events and, while a
+    plan records, named for the plan's timed replays (bench roofline).  ``info()`` -> (kernel-name
+    query, its cache key, algorithmic FLOPs, description); asked only when one of the two wants it
+    (the kernel name does not depend on the workspace pointer, set by now)."""
+    t = TIMER
+    if t is None and not RECORDING:
+        return call(fn, ctypes.byref(a), stream())
+    name_fn, key, flops, desc = info()
+    name = _kernel_name(name_fn, key, a)
+    if t is not None and not t.wants(name):
+        t = None
+    ev = t.begin() if t is not None else None
+    if RECORDING:
+        call("stf_plan_tag", name.encode(), float(flops))
+    call(fn, ctypes.byref(a), stream())
+    if RECORDING:
+        call("stf_plan_tag_end")
+    if t is not None:
+        t.end(ev, name, flops, desc)
 
 
 def conv_dgrad(dy: Feat, w, dx: Feat, R, S, stride, pad, accumulate=False, bnr=None, cache=True, want_stats=False):
@@ -453,6 +466,7 @@ def rows(f: Feat, n0, n):
 
 WGRAD_STREAM = None   # set by a program: weight gradients run there, off the critical path
 _STREAMS = {}
+_SIDE_PRIO = int(os.environ.get("STF_SIDE_PRIO", "-1"))
 
 
 def side_stream(device, name):
@@ -470,9 +484,6 @@ def side_stream(device, name):
     if st is None:
         st = _STREAMS[key] = torch.cuda.Stream(device=dev, priority=_SIDE_PRIO)
     return st
-
-
-_SIDE_PRIO = int(os.environ.get("STF_SIDE_PRIO", "-1"))
 
 
 def wgrad_side_stream(device):
@@ -545,22 +556,19 @@ def _wgrad(dy: Feat, x: Feat, R, S, stride, pad, out, grid_blocks=0):
     ws = empty(nbytes // 4, torch.float32, out.device)
     a.ws = ws.data_ptr()
     a.splits = splits
-    t = TIMER
-    if t is not None:
-        name = _kernel_name("stf_wgrad_kernel_name", ("w", x.N, x.H, x.W, x.C, dy.H, dy.W, dy.C, R, S, stride, pad), a)
-        if not t.wants(name):
-            t = None
-    ev = t.begin() if t is not None else None
-    if RECORDING:
-        _plan_tag(a, "stf_wgrad_kernel_name", ("w", x.N, x.H, x.W, x.C, dy.H, dy.W, dy.C, R, S, stride, pad),
-                  2.0 * dy.M * dy.C * R * S * x.C)
-    call("stf_wgrad", ctypes.byref(a), stream())
-    if RECORDING:
-        call("stf_plan_tag_end")
-    if t is not None:
-        t.end(ev, name, 2.0 * dy.M * dy.C * R * S * x.C,
-              f"wgrad M={dy.M} N={dy.C} K={R * S * x.C} {R}x{S}/s{stride} splits={splits}")
+    _launch("stf_wgrad", a, lambda: (
+        "stf_wgrad_kernel_name", ("w", x.N, x.H, x.W, x.C, dy.H, dy.W, dy.C, R, S, stride, pad),
+        2.0 * dy.M * dy.C * R * S * x.C, f"wgrad M={dy.M} N={dy.C} K={R * S * x.C} {R}x{S}/s{stride} splits={splits}"))
     call("stf_wgrad_reduce", ws.data_ptr(), splits, dy.C, R, S, x.C, out.data_ptr(), stream())
+
+
+def wgrad_padded(dy: Feat, x: Feat, R, S, stride, pad, out, cin):
+    """Weight gradient over a source whose ``x.C`` channels are ``cin`` real ones and zero
+    padding, into ``out`` ([dy.C][cin][R][S]): computed at the padded width into a temporary that
+    is consumed right away on the current stream, then the padded columns are dropped."""
+    tmp = empty(dy.C * x.C * R * S, torch.float32, out.device)
+    wgrad(dy, x, R, S, stride, pad, tmp, defer=False)
+    copy_rows(tmp, x.C * R * S, out, cin * R * S, dy.C, cin * R * S)
 
 
 def stat_sums(stats, tiles, nout, c0, C, out):
@@ -763,12 +771,17 @@ def _bn_bwd_coef(y: Feat, st: BNState, bn, part, tiles, dgamma, dbeta):
     C, dev, G = y.C, y.buf.device, st.groups
     coef = empty(G * 3 * C, torch.float32, dev)
     if G > 1 and (dgamma is not None or dbeta is not None):
+        # grouped: the per-group sums stay parked; flush_bn_grads() adds them up for
+        # every pending BatchNorm in one launch
         _GSUM_PENDING.append((_GsumDesc(part.data_ptr(), dgamma.data_ptr() if dgamma is not None else None,
                                         dbeta.data_ptr() if dbeta is not None else None, tiles, G, C), part))
         dgamma = dbeta = None
     call("stf_bn_bwd_finalize", _p(part), tiles, G, C, y.M, bn.weight.data_ptr(), _p(st.mean),
          _p(st.invstd), _p(dgamma), _p(dbeta), _p(coef), stream())
     if not st.training:
+        # eval mode (running statistics are constants): dy = gamma * invstd * g, i.e. the
+        # apply pass's dy = A g + B y + C with B = C = 0; dgamma = sum g xhat and
+        # dbeta = sum g come out of the same partial sums as in training mode
         cv = coef.view(G, 3, C)
         cv[:, 0].copy_(bn.weight.detach() * st.invstd)
         cv[:, 1:].zero_()
@@ -789,22 +802,7 @@ def bn_backward_from_partial(g: Feat, y: Feat, st: BNState, bn, part, tiles, dga
         # gradient instead of summing the rounded dy (the reference's autograd returns
         # fp32 noise around 0 there)
         dbias = None
-    coef = empty(G * 3 * C, torch.float32, dev)
-    if G > 1 and (dgamma is not None or dbeta is not None):
-        # grouped: the per-group sums stay parked; flush_bn_grads() adds them up for
-        # every pending BatchNorm in one launch
-        _GSUM_PENDING.append((_GsumDesc(part.data_ptr(), dgamma.data_ptr() if dgamma is not None else None,
-                                        dbeta.data_ptr() if dbeta is not None else None, tiles, G, C), part))
-        dgamma = dbeta = None
-    call("stf_bn_bwd_finalize", _p(part), tiles, G, C, y.M, bn.weight.data_ptr(), _p(st.mean),
-         _p(st.invstd), _p(dgamma), _p(dbeta), _p(coef), stream())
-    if not st.training:
-        # eval mode (running statistics are constants): dy = gamma * invstd * g, i.e. the
-        # apply pass's dy = A g + B y + C with B = C = 0; dgamma = sum g xhat and
-        # dbeta = sum g come out of the same partial sums as in training mode
-        cv = coef.view(G, 3, C)
-        cv[:, 0].copy_(bn.weight.detach() * st.invstd)
-        cv[:, 1:].zero_()
+    coef = _bn_bwd_coef(y, st, bn, part, tiles, dgamma, dbeta)
     bpart = None
     if dbias is not None:
         bpart = empty(_lib.load().stf_bn_bwd_apply_tiles(y.M, C) * C, torch.float32, dev)
@@ -817,3 +815,33 @@ def bn_backward_from_partial(g: Feat, y: Feat, st: BNState, bn, part, tiles, dga
     call("stf_bn_bwd_apply", g.ptr(), g.cs, y.ptr(), y.cs, y.M, C, G, _p(st.scale) if mask_relu else None,
          _p(st.shift) if mask_relu else None, _p(coef), dst.ptr(), dst.cs, _p(bpart), _p(dbias), stream())
     return dst
+
+
+# ------------------------------------------------------------------ head
+def head_fwd(y: Feat, st: BNState, conv, logits):
+    """logits [N, K, H, W] fp32 = the 1x1 conv ``conv`` over relu(BN(y)), one pass (stf_head_fwd; ``st``
+    = the BatchNorm state of ``y``, or an identity state where the ReLU is already applied).
+    Returns the [K, C] weight view that head_bwd reads."""
+    y.check()
+    K = conv.out_channels
+    assert y.cs == y.C and y.off == 0 and tuple(logits.shape) == (y.N, K, y.H, y.W)
+    head_w = conv.weight.detach().reshape(K, -1).contiguous()
+    call("stf_head_fwd", y.ptr(), y.N, y.H, y.W, y.C, _p(st.scale), _p(st.shift), _p(head_w), _p(conv.bias.detach()),
+         K, _p(logits), stream())
+    return head_w
+
+
+def head_bwd(dlogits, y: Feat, st: BNState, head_w, dweight, dbias):
+    """Backward of head_fwd (stf_head_bwd): the 1x1 conv's weight / bias gradients into ``dweight`` /
+    ``dbias`` and g = the ReLU-masked gradient w.r.t. BN(y), with the BN-backward partial sums of
+    g reduced in the same pass.  Returns (g, partial sums, tiles) for bn_backward_from_partial."""
+    y.check()
+    K, C, dev = dlogits.shape[1], y.C, dlogits.device
+    assert dlogits.dtype == torch.float32 and dlogits.is_contiguous() and tuple(dlogits.shape) == (y.N, K, y.H, y.W)
+    tiles = _lib.load().stf_head_tiles(y.N, y.H, y.W, C)
+    g = new_feat(y.N, y.H, y.W, C, dev)
+    bnp = empty(tiles * 2 * C, torch.float32, dev)
+    hp = empty((tiles + 1) * K * (C + 1), torch.float32, dev)
+    call("stf_head_bwd", _p(dlogits), y.ptr(), y.N, y.H, y.W, C, _p(st.scale), _p(st.shift), _p(st.mean),
+         _p(st.invstd), _p(head_w), K, g.ptr(), _p(bnp), _p(hp), _p(dweight), _p(dbias), stream())
+    return g, bnp, tiles

@@ -9,7 +9,8 @@ SURVEY.md section 0), the module tree and therefore all ``state_dict`` keys:
 parameters), ``decoder4..2`` (``up``, ``fusion``, ``res_conv.conv_block``),
 ``upconv1``, ``final_res``, ``final``.
 
-Schedule (all NHWC bf16, fp32 statistics; ``STFProgram``):
+Schedule (all NHWC bf16, fp32 statistics; ``STFProgram``, on the ``Program`` base, autograd
+function and block steps of program.py):
   * the T time steps are one batch of T*B images, t-major; every BatchNorm of the
     encoder keeps per-time-step statistics (groups = T) and advances its running
     stats T times, as the reference's per-t loop does (:168-186);
@@ -31,9 +32,8 @@ import torch.nn as nn
 
 from . import _lib, nhwc
 from ._lib import LstmEpi, call, stream
-from .flat import FlatParams
 from .nhwc import BNState, Feat, _p, new_feat, rows, zeros_feat
-from .plan import StepRuntime
+from .program import Program, Saved as _S, conv_bn, conv_pair_backward, run_step
 
 
 # ------------------------------------------------------------------ module tree
@@ -89,10 +89,6 @@ class DecoderBlock(nn.Module):
         self.res_conv = ResidualConvBlock(out_channels, out_channels)
 
 
-class _S:
-    pass
-
-
 # ------------------------------------------------------------------ block programs
 class ResBlockProgram:
     """BasicBlock / ResidualConvBlock: out = relu(bn2(conv2(relu(bn1(conv1 x)))) + sc(x))."""
@@ -105,27 +101,16 @@ class ResBlockProgram:
 
     def forward(self, src: Feat, out: Feat, training, groups):
         dev, C, st = src.buf.device, self.cout, self.stride
-        Ho, Wo = (src.H - 1) // st + 1, (src.W - 1) // st + 1
         s = _S()
         s.src, s.out = src, out
-        y1 = new_feat(src.N, Ho, Wo, C, dev)
-        stats, tiles = nhwc.igemm(src, nhwc.pack_weight(self.conv1.weight, 0, src.C), C, y1, 3, 3, st, 1,
-                                  want_stats=training, groups=groups)
-        s.bn1 = nhwc.bn_finalize(stats, tiles, self.bn1, y1.M, training, groups)
-        a1 = new_feat(src.N, Ho, Wo, C, dev)
+        y1, s.bn1 = conv_bn(src, self.conv1, self.bn1, 3, st, 1, training, groups)
+        a1 = new_feat(src.N, y1.H, y1.W, C, dev)
         nhwc.bn_act(y1, s.bn1, a1)
-        y2 = new_feat(src.N, Ho, Wo, C, dev)
-        stats, tiles = nhwc.igemm(a1, nhwc.pack_weight(self.conv2.weight, 0, C), C, y2, 3, 3, 1, 1,
-                                  want_stats=training, groups=groups)
-        s.bn2 = nhwc.bn_finalize(stats, tiles, self.bn2, y2.M, training, groups)
+        y2, s.bn2 = conv_bn(a1, self.conv2, self.bn2, 3, 1, 1, training, groups)
         s.yd = s.bnd = None
         if self.sc_conv is not None:
-            yd = new_feat(src.N, Ho, Wo, C, dev)
-            stats, tiles = nhwc.igemm(src, nhwc.pack_weight(self.sc_conv.weight, 0, src.C), C, yd, 1, 1, st, 0,
-                                      want_stats=training, groups=groups)
-            s.bnd = nhwc.bn_finalize(stats, tiles, self.sc_bn, yd.M, training, groups)
-            s.yd = yd
-            nhwc.bn_act(y2, s.bn2, out, res=yd, res_st=s.bnd)
+            s.yd, s.bnd = conv_bn(src, self.sc_conv, self.sc_bn, 1, st, 0, training, groups)
+            nhwc.bn_act(y2, s.bn2, out, res=s.yd, res_st=s.bnd)
         else:
             nhwc.bn_act(y2, s.bn2, out, res=src)
         s.y1, s.a1, s.y2 = y1, a1, y2
@@ -142,14 +127,8 @@ class ResBlockProgram:
         else:
             dy2 = nhwc.bn_backward(s.y2, s.bn2, self.bn2, gv(self.bn2.weight), gv(self.bn2.bias), dz=g,
                                    relu=False, out=new_feat(g.N, g.H, g.W, g.C, g.buf.device))
-        nhwc.wgrad(dy2, s.a1, 3, 3, 1, 1, gv(self.conv2.weight))
-        da1 = new_feat(s.a1.N, s.a1.H, s.a1.W, self.cout, s.a1.buf.device)
-        part, tiles = nhwc.conv_dgrad(dy2, self.conv2.weight, da1, 3, 3, 1, 1, bnr=(s.y1, s.bn1, True))
+        dy1 = conv_pair_backward(s, gv, dy2, self.conv1, self.bn1, self.conv2, self.stride)
         del dy2
-        dy1 = nhwc.bn_backward_fused(da1, s.y1, s.bn1, self.bn1, part, tiles, gv(self.bn1.weight),
-                                     gv(self.bn1.bias))
-        del da1
-        nhwc.wgrad(dy1, src, 3, 3, self.stride, 1, gv(self.conv1.weight))
         if self.sc_conv is None:
             # identity shortcut: d_src = g + dgrad(conv1)
             if dsrc is not None:
@@ -330,14 +309,9 @@ class LSTMProgram:
 
 
 # ------------------------------------------------------------------ program
-class STFProgram:
+class STFProgram(Program):
     def __init__(self, m):
-        self.m = m
-        self.packs = nhwc.PackCache()
-        self.flat = FlatParams(m)
-        self.grad_ready_hook = None
-        self.want_dx = False           # set by _STFFunction.backward for an input that requires grad
-        self.dx = None
+        super().__init__(m)
         self.layers = []
         for layer in (m.layer1, m.layer2, m.layer3, m.layer4):
             progs = []
@@ -361,7 +335,6 @@ class STFProgram:
         self.err_word = None          # sticky device flag of the cooperative LSTM launches
         self._err_host = None         # its pinned host copy, issued at each step boundary
         self._err_event = None
-        self.runtime = StepRuntime(self)
 
     def plan_knobs(self):
         """Per-program scalars a recorded plan carries by value (part of its signature)."""
@@ -440,35 +413,22 @@ class STFProgram:
         the module's own backward have run: the hook gets those streams as dependencies, so the
         main stream never waits for a side stream on its account."""
         nhwc.flush_bn_grads()          # grouped BN dgamma/dbeta before the buckets read them
-        if self.grad_ready_hook is not None:
-            deps = tuple(s for s in (self._wstream, side) if s is not None)
-            first = next(module.parameters())
-            self.grad_ready_hook(self.flat.offsets[self.flat.index[id(first)]], deps)
-
-    # ------------------------------------------------------------------ forward
-    def forward(self, x, training, need_bwd):
-        """Refresh the packed weights (one launch) and run the forward schedule."""
-        self.packs.refresh()
-        nhwc.ACTIVE_PACKS = self.packs
-        try:
-            return self._forward(x, training, need_bwd)
-        finally:
-            nhwc.ACTIVE_PACKS = None
+        super()._done(module, tuple(s for s in (self._wstream, side) if s is not None))
 
     def backward(self, S, dlogits):
-        nhwc.ACTIVE_PACKS = self.packs
+        """Program.backward with the weight gradients on their side stream, joined at the end."""
         ws = self._wstream = nhwc.wgrad_side_stream(dlogits.device)
         nhwc.WGRAD_STREAM = ws
         nhwc.WGRAD_MAIN = torch.cuda.current_stream(dlogits.device)
         try:
-            return self._backward(S, dlogits)
+            return super().backward(S, dlogits)
         finally:
             nhwc.WGRAD_STREAM = nhwc.WGRAD_MAIN = None
             if ws is not None:
                 nhwc.wait(torch.cuda.current_stream(dlogits.device), ws)
             nhwc.flush_bn_grads()
-            nhwc.ACTIVE_PACKS = None
 
+    # ------------------------------------------------------------------ forward
     def _forward(self, x, training, need_bwd):
         m = self.m
         nhwc._NBT_PENDING.clear()
@@ -612,9 +572,7 @@ class STFProgram:
         K = m.final.out_channels
         logits = nhwc.empty((B, K, u1.H, u1.W), torch.float32, dev)
         S.ident = self._identity(fr_out.C, dev)
-        S.head_w = m.final.weight.detach().reshape(K, -1).contiguous()
-        call("stf_head_fwd", fr_out.ptr(), B, u1.H, u1.W, fr_out.C, _p(S.ident.scale), _p(S.ident.shift),
-             _p(S.head_w), _p(m.final.bias.detach()), K, _p(logits), stream())
+        S.head_w = nhwc.head_fwd(fr_out, S.ident, m.final, logits)
         nhwc.flush_batches_tracked()
         return logits, (S if need_bwd else None)
 
@@ -625,17 +583,8 @@ class STFProgram:
         dev = dlogits.device
         dlogits = dlogits.contiguous().float()
         B, T, P = S.B, S.T, S.P
-        fr_out = S.fr.out
-        K = dlogits.shape[1]
-        C = fr_out.C
-        lib = _lib.load()
-        tiles = lib.stf_head_tiles(B, fr_out.H, fr_out.W, C)
-        g = new_feat(B, fr_out.H, fr_out.W, C, dev)
-        bnp = nhwc.empty(tiles * 2 * C, torch.float32, dev)
-        hp = nhwc.empty((tiles + 1) * K * (C + 1), torch.float32, dev)
-        call("stf_head_bwd", _p(dlogits), fr_out.ptr(), B, fr_out.H, fr_out.W, C, _p(S.ident.scale),
-             _p(S.ident.shift), _p(S.ident.mean), _p(S.ident.invstd), _p(S.head_w), K, g.ptr(), _p(bnp), _p(hp),
-             _p(gv(m.final.weight)), _p(gv(m.final.bias)), stream())
+        # (no BatchNorm under the head here: its partial sums are not used)
+        g, _, _ = nhwc.head_bwd(dlogits, S.fr.out, S.ident, S.head_w, gv(m.final.weight), gv(m.final.bias))
         self._done(m.final)
         d_u1 = self.final_res.backward(S.fr, gv, g=g)
         self._done(m.final_res)
@@ -732,15 +681,11 @@ class STFProgram:
             call("stf_wgrad_reduce", _p(ws), grid, 64, 1, 1, 64, _p(tmp), stream())
             nhwc.copy_rows(tmp, 64, gv(w1), kreal, w1.shape[0], kreal)
         elif S.stem_gather:                    # 8-channel packed input, 7x7/s2 gather
-            tmp = nhwc.empty(w1.shape[0] * 8 * 49, torch.float32, dev)
-            nhwc.wgrad(dy0, S.xin, 7, 7, 2, 3, tmp, defer=False)
-            nhwc.copy_rows(tmp, 8 * 49, gv(w1), w1.shape[1] * 49, w1.shape[0], w1.shape[1] * 49)
+            nhwc.wgrad_padded(dy0, S.xin, 7, 7, 2, 3, gv(w1), w1.shape[1])
         elif S.xin.C == kreal:
             nhwc.wgrad(dy0, S.xin, 1, 1, 1, 0, gv(w1))
         else:
-            tmp = nhwc.empty(w1.shape[0] * S.xin.C, torch.float32, dev)
-            nhwc.wgrad(dy0, S.xin, 1, 1, 1, 0, tmp, defer=False)
-            nhwc.copy_rows(tmp, S.xin.C, gv(w1), kreal, w1.shape[0], kreal)
+            nhwc.wgrad_padded(dy0, S.xin, 1, 1, 1, 0, gv(w1), kreal)
 
     def _input_grad(self, S, dy0, w1, B, T, P, dev):
         """d(loss)/d(x) for x [B, T + P, Cf, H, W]: the stem conv's input gradient over its Cf + P input
@@ -772,19 +717,13 @@ class STFProgram:
     def _pk_fusion_backward(self, S, k, de: Feat, gv):
         fus = getattr(self.m, f"pk_fusion{k + 1}")
         pkb = S.pkbuf[k]
-        C = de.C
-        tmp = nhwc.empty(C * pkb.C, torch.float32, de.buf.device)
-        nhwc.wgrad(de, pkb, 1, 1, 1, 0, tmp, defer=False)
-        cin = fus.in_channels
-        nhwc.copy_rows(tmp, pkb.C, gv(fus.weight), cin, C, cin)
+        nhwc.wgrad_padded(de, pkb, 1, 1, 1, 0, gv(fus.weight), fus.in_channels)
         nhwc.channel_sum(de, gv(fus.bias))
         dpk = new_feat(pkb.N, pkb.H, pkb.W, pkb.C, de.buf.device)
-        w = nhwc.memset0(nhwc.empty((C, pkb.C, 1, 1), torch.float32, de.buf.device))
-        nhwc.copy_rows(fus.weight.detach(), cin, w, pkb.C, C, cin)
-        nhwc.conv_dgrad(de, w, dpk, 1, 1, 1, 0, cache=False)
+        nhwc.conv_dgrad(de, nhwc.pad_weight(fus.weight, pkb.C), dpk, 1, 1, 1, 0, cache=False)
         if self.want_dx:                  # the resized PK maps' share, for _input_grad
             S.dpk_parts.append(dpk)
-        return dpk.slice(0, C)
+        return dpk.slice(0, de.C)
 
 
 _STEM_DIRECT = os.environ.get("STF_STEM_DIRECT", "1") != "0"     # (A/B: 0 = im2col + 1x1 GEMM)
@@ -802,43 +741,6 @@ def _check_input_shape(shape, P):
         raise ValueError(f"STFLSTMUNet: {Ttot} input frames leave no time steps after {P} PK maps")
     if H < 32 or W < 32:
         raise ValueError(f"STFLSTMUNet needs H, W >= 32 (got {H}x{W})")
-
-
-class _STFFunction(torch.autograd.Function):
-    """``res`` = (logits, saved state) of the forward STFLSTMUNet.forward already enqueued: the GPU
-    starts on the step while autograd processes the ~160 parameter inputs of this call (~100 us of
-    host time at every synced step boundary); or None (input gradients: the eager forward runs
-    here)."""
-    @staticmethod
-    def forward(ctx, x, prog, storage, res, *params):
-        ctx.need_dx = ctx.needs_input_grad[0]
-        if res is not None:
-            logits, saved = res
-            prog.runtime.own(saved, ctx)
-        else:
-            need_bwd = any(ctx.needs_input_grad[4:]) or ctx.need_dx
-            with _lib.storage(storage):
-                logits, saved = prog.forward(x, prog.m.training, need_bwd)
-        ctx.storage = storage
-        ctx.prog, ctx.saved = prog, saved
-        return logits.detach()        # the plan's static logits: a fresh tensor object per step
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        prog = ctx.prog
-        dlogits = dlogits.float().contiguous()     # autocast / GradScaler callers: any float dtype
-        prog.flat.fresh_grad()
-        prog.want_dx, prog.dx = ctx.need_dx, None
-        try:
-            with _lib.storage(ctx.storage):
-                prog.runtime.backward(ctx.saved, dlogits)
-        finally:
-            prog.want_dx = False
-        ctx.saved = None
-        if prog.grad_ready_hook is not None:
-            prog.grad_ready_hook(0, ())
-        dx, prog.dx = prog.dx, None
-        return (dx, None, None, None, *prog.flat.grad_views())
 
 
 class STFLSTMUNet(nn.Module):
@@ -885,22 +787,9 @@ class STFLSTMUNet(nn.Module):
     def forward(self, x, pk_maps=None):
         # pk_maps is ignored, as in the reference (PK maps ride on the T axis, :146-156)
         _check_input_shape(x.shape, self.pk_channels if self.use_pk_maps else 0)
-        if not x.is_cuda:
-            raise RuntimeError("stfunet.STFLSTMUNet runs on the gfx950 HIP kernels only; move the model and "
-                               "input to a ROCm device (no CPU fallback)")
-        prog = self.program
-        prog.check_device_errors(x.device)       # step boundary: an earlier step's LSTM timeout raises
-        prog.flat.ensure()
-        grad = torch.is_grad_enabled()
-        storage = _lib.storage_for(self.storage_dtype)
-        res = None
-        if grad and x.requires_grad:
-            # the input gradient (reference autograd returns it, src/stf_lstm_unet.py:139-256): the
-            # eager forward inside the autograd Function, the stem's input gradient in the backward
-            # (with PK maps also their fusion branches' gradient through the resize)
-            pass
-        else:
-            need_bwd = grad and prog.flat.any_requires_grad()
-            with _lib.storage(storage), torch.no_grad():    # (as inside autograd.Function.forward)
-                res = prog.runtime.forward(x, self.training, need_bwd)      # launched before autograd's bookkeeping
-        return {"out": _STFFunction.apply(x, prog, storage, res, *prog.flat.params)}
+        if x.is_cuda:                            # (a CPU input: run_step refuses it)
+            self.program.check_device_errors(x.device)       # step boundary: an earlier step's LSTM timeout raises
+        # with an input that requires grad (reference autograd returns it, src/stf_lstm_unet.py:139-256)
+        # the backward adds the stem's input gradient (_input_grad; with PK maps also their fusion
+        # branches' gradient through the resize)
+        return run_step(self, x)

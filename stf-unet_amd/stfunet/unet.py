@@ -9,7 +9,9 @@ ReLU)``) and therefore the 136 ``state_dict`` keys and PyTorch's default init,
 and ``forward(x) -> {"out": logits}`` with logits [B, classes, H, W] fp32.
 
 What runs is not those modules' forward: ``forward`` hands the input and every
-parameter to ``_UNetFunction``, an explicit schedule over NHWC bf16 buffers:
+parameter to ``program.run_step`` (the autograd function, the plan runtime and the
+``Program`` base are in program.py), which runs ``UNetProgram``'s explicit schedule over
+NHWC bf16 buffers:
 
   forward, per DoubleConv (src/unet.py:10-18):
     igemm conv3x3 (+bias, +BN partial sums) -> bn_finalize -> bn_act
@@ -25,10 +27,9 @@ parameter to ``_UNetFunction``, an explicit schedule over NHWC bf16 buffers:
 import torch
 import torch.nn as nn
 
-from . import _lib, nhwc
-from .flat import FlatParams
+from . import nhwc
 from .nhwc import Feat, new_feat
-from .plan import StepRuntime
+from .program import Program, Saved as _Saved, conv_bn, conv_pair_backward, run_step
 
 
 def _double_conv(cin, cout):
@@ -39,10 +40,6 @@ def _double_conv(cin, cout):
 
 def _cpad(c):
     return (c + 7) // 8 * 8
-
-
-class _Saved:
-    pass
 
 
 class DoubleConvProgram:
@@ -67,16 +64,10 @@ class DoubleConvProgram:
         C, dev = self.cout, src.buf.device
         s = _Saved()
         s.src = src
-        y1 = new_feat(src.N, src.H, src.W, C, dev)
-        w1 = nhwc.pack_weight(conv1.weight, 0, src.C)
-        st, tiles = nhwc.igemm(src, w1, C, y1, 3, 3, 1, 1, bias=conv1.bias.detach(), want_stats=training)
-        s.bn1 = nhwc.bn_finalize(st, tiles, bn1, y1.M, training)
+        y1, s.bn1 = conv_bn(src, conv1, bn1, 3, 1, 1, training)
         a1 = new_feat(src.N, src.H, src.W, C, dev)
         nhwc.bn_act(y1, s.bn1, a1)
-        y2 = new_feat(src.N, src.H, src.W, C, dev)
-        w2 = nhwc.pack_weight(conv2.weight, 0, C)
-        st, tiles = nhwc.igemm(a1, w2, C, y2, 3, 3, 1, 1, bias=conv2.bias.detach(), want_stats=training)
-        s.bn2 = nhwc.bn_finalize(st, tiles, bn2, y2.M, training)
+        y2, s.bn2 = conv_bn(a1, conv2, bn2, 3, 1, 1, training)
         if out is not None:
             nhwc.bn_act(y2, s.bn2, out, pooled=pooled)
         s.y1, s.a1, s.y2 = y1, a1, y2
@@ -93,14 +84,7 @@ class DoubleConvProgram:
         if dy2 is None:
             dy2 = nhwc.bn_backward(s.y2, s.bn2, bn2, gv(bn2.weight), gv(bn2.bias), dz=dz, dpool=dpool,
                                    dbias=gv(conv2.bias))
-        nhwc.wgrad(dy2, s.a1, 3, 3, 1, 1, gv(conv2.weight))
-        da1 = new_feat(s.a1.N, s.a1.H, s.a1.W, self.cout, s.a1.buf.device)
-        # dgrad of conv2 also reduces BN1's backward sums (fused epilogue)
-        part, tiles = nhwc.conv_dgrad(dy2, conv2.weight, da1, 3, 3, 1, 1, bnr=(s.y1, s.bn1, True))
-        dy1 = nhwc.bn_backward_fused(da1, s.y1, s.bn1, bn1, part, tiles, gv(bn1.weight), gv(bn1.bias),
-                                     dbias=gv(conv1.bias))
-        del da1
-        self._wgrad_conv1(dy1, s.src, gv(conv1.weight))
+        dy1 = conv_pair_backward(s, gv, dy2, conv1, bn1, conv2, dbias1=gv(conv1.bias))
         if not need_dsrc:
             return None
         dsrc = new_feat(s.src.N, s.src.H, s.src.W, s.src.C, s.src.buf.device)
@@ -108,70 +92,30 @@ class DoubleConvProgram:
         if s.src.C != w1.shape[1]:
             # zero-padded input channels (in_channels % 8 != 0): the weight padded the same way, so the
             # padded channels' gradient is computed and dropped by the caller
-            cin = w1.shape[1]
-            wp = nhwc.memset0(nhwc.empty((self.cout, s.src.C, 3, 3), torch.float32, w1.device))
-            nhwc.copy_rows(w1.detach(), cin * 9, wp, s.src.C * 9, self.cout, cin * 9)
-            w1 = wp
+            w1 = nhwc.pad_weight(w1, s.src.C)
         st, tiles = nhwc.conv_dgrad(dy1, w1, dsrc, 3, 3, 1, 1, cache=w1 is conv1.weight, want_stats=dsrc_stats)
         return (dsrc, st, tiles) if dsrc_stats else dsrc
 
-    def _wgrad_conv1(self, dy1, src, out):
-        cin = self.blk[0].in_channels
-        if src.C == cin:
-            nhwc.wgrad(dy1, src, 3, 3, 1, 1, out)
-        else:   # zero-padded input channels (in_channels % 8 != 0): drop the padded columns
-            tmp = nhwc.empty(self.cout * src.C * 9, torch.float32, out.device)
-            nhwc.wgrad(dy1, src, 3, 3, 1, 1, tmp, defer=False)
-            nhwc.copy_rows(tmp, src.C * 9, out, cin * 9, self.cout, cin * 9)
 
-
-class UNetProgram:
+class UNetProgram(Program):
     def __init__(self, model):
-        self.m = model
-        self.packs = nhwc.PackCache()
+        super().__init__(model)
         self.levels = [DoubleConvProgram(b, f"enc{i}") for i, b in
                        enumerate((model.enc1, model.enc2, model.enc3, model.enc4), start=1)]
         self.bott = DoubleConvProgram(model.bottleneck, "bottleneck")
         self.ups = [model.up4, model.up3, model.up2, model.up1]
         self.decs = [DoubleConvProgram(b, f"dec{i}") for i, b in
                      zip((4, 3, 2, 1), (model.dec4, model.dec3, model.dec2, model.dec1))]
-        self.flat = FlatParams(model)
-        # grad_ready_hook(begin): flat-gradient elements [begin, numel) are final.  Backward
-        # finishes blocks in exactly the reverse of registration (= flat) order, so the
-        # finished gradients always form a suffix of the flat buffer (DDP buckets).
-        self.grad_ready_hook = None
-        # set by _UNetFunction for the backward in flight: also return d(loss)/d(input)
-        self.want_dx = False
-        self.dx = None
-        self.runtime = StepRuntime(self)
 
     def _done(self, module):
-        if self.grad_ready_hook is not None:
-            # (with weight gradients on a side stream, the bucket waits for that stream too)
-            deps = (nhwc.WGRAD_STREAM,) if nhwc.WGRAD_STREAM is not None else ()
-            first = next(module.parameters())
-            self.grad_ready_hook(self.flat.offsets[self.flat.index[id(first)]], deps)
+        # (with weight gradients on a side stream, the bucket waits for that stream too)
+        super()._done(module, (nhwc.WGRAD_STREAM,) if nhwc.WGRAD_STREAM is not None else ())
+
+    # Program.backward as it is: weight gradients stay on the current stream here: a side stream
+    # (as in the STF program) measured +1.2 / -0.3..-3.8 % at cfg2 (full / one-per-CU grid, round 5) and
+    # makes every concurrent kernel's duration a shared-machine number; the variant was removed
 
     # ------------------------------------------------------------------ forward
-    def forward(self, x, training, need_bwd):
-        """Refresh the packed weights (one launch) and run the forward schedule."""
-        self.packs.refresh()
-        nhwc.ACTIVE_PACKS = self.packs
-        try:
-            return self._forward(x, training, need_bwd)
-        finally:
-            nhwc.ACTIVE_PACKS = None
-
-    def backward(self, S, dlogits):
-        # weight gradients stay on the current stream here: a side stream (as in the STF
-        # program) measured +1.2 / -0.3..-3.8 % at cfg2 (full / one-per-CU grid, round 5) and makes
-        # every concurrent kernel's duration a shared-machine number; the variant was removed
-        nhwc.ACTIVE_PACKS = self.packs
-        try:
-            return self._backward(S, dlogits)
-        finally:
-            nhwc.ACTIVE_PACKS = None
-
     def _forward(self, x, training, need_bwd):
         m = self.m
         nhwc._NBT_PENDING.clear()
@@ -213,9 +157,7 @@ class UNetProgram:
         s = S.dec[-1]
         K = m.out_conv.out_channels
         logits = nhwc.empty((N, K, H, W), torch.float32, dev)
-        S.head_w = m.out_conv.weight.detach().reshape(K, -1).contiguous()
-        nhwc.call("stf_head_fwd", s.y2.ptr(), N, H, W, s.y2.C, nhwc._p(s.bn2.scale), nhwc._p(s.bn2.shift),
-                  nhwc._p(S.head_w), nhwc._p(m.out_conv.bias.detach()), K, nhwc._p(logits), nhwc.stream())
+        S.head_w = nhwc.head_fwd(s.y2, s.bn2, m.out_conv, logits)
         if not need_bwd:
             S.enc = S.cats = S.dec = None
         nhwc.flush_batches_tracked()
@@ -229,17 +171,7 @@ class UNetProgram:
         dlogits = dlogits.contiguous().float()
         # head + dec1's last BN+ReLU
         s = S.dec[-1]
-        N, K, H, W = dlogits.shape
-        C = s.y2.C
-        lib = nhwc._lib.load()
-        tiles = lib.stf_head_tiles(N, H, W, C)
-        g = new_feat(N, H, W, C, dev)
-        bnp = nhwc.empty(tiles * 2 * C, torch.float32, dev)
-        hp = nhwc.empty((tiles + 1) * K * (C + 1), torch.float32, dev)
-        nhwc.call("stf_head_bwd", nhwc._p(dlogits), s.y2.ptr(), N, H, W, C, nhwc._p(s.bn2.scale),
-                  nhwc._p(s.bn2.shift), nhwc._p(s.bn2.mean), nhwc._p(s.bn2.invstd), nhwc._p(S.head_w), K,
-                  g.ptr(), nhwc._p(bnp), nhwc._p(hp), nhwc._p(gv(m.out_conv.weight)),
-                  nhwc._p(gv(m.out_conv.bias)), nhwc.stream())
+        g, bnp, tiles = nhwc.head_bwd(dlogits, s.y2, s.bn2, S.head_w, gv(m.out_conv.weight), gv(m.out_conv.bias))
         dec1 = self.decs[3]
         dy2 = nhwc.bn_backward_from_partial(g, s.y2, s.bn2, dec1.blk[4], bnp, tiles, gv(dec1.blk[4].weight),
                                             gv(dec1.blk[4].bias), gv(dec1.blk[3].bias))
@@ -280,43 +212,6 @@ class UNetProgram:
             self.dx = dpool.dense()[:, : m.in_channels].contiguous()
 
 
-class _UNetFunction(torch.autograd.Function):
-    """``res``: (logits, saved state) of the plan-cached forward UNet.forward already enqueued (the
-    GPU starts while autograd processes the parameter inputs), or None (input gradients: the eager
-    forward runs here)."""
-    @staticmethod
-    def forward(ctx, x, prog, storage, res, *params):
-        ctx.need_dx = ctx.needs_input_grad[0]
-        if res is not None:
-            logits, saved = res
-            prog.runtime.own(saved, ctx)
-        else:
-            need_bwd = any(ctx.needs_input_grad[4:]) or ctx.need_dx
-            with _lib.storage(storage):
-                logits, saved = prog.forward(x, prog.m.training, need_bwd)
-        ctx.storage = storage
-        ctx.prog = prog
-        ctx.saved = saved
-        return logits.detach()        # the plan's static logits: a fresh tensor object per step
-
-    @staticmethod
-    def backward(ctx, dlogits):
-        prog = ctx.prog
-        dlogits = dlogits.float().contiguous()     # autocast / GradScaler callers: any float dtype
-        prog.flat.fresh_grad()
-        prog.want_dx, prog.dx = ctx.need_dx, None
-        try:
-            with _lib.storage(ctx.storage):
-                prog.runtime.backward(ctx.saved, dlogits)
-        finally:
-            prog.want_dx = False
-        ctx.saved = None
-        if prog.grad_ready_hook is not None:
-            prog.grad_ready_hook(0, ())
-        dx, prog.dx = prog.dx, None
-        return (dx, None, None, None, *prog.flat.grad_views())
-
-
 class UNet(nn.Module):
     input_format = "flat_channels"  # [B, T*C, H, W], train_and_eval.py:12-14
 
@@ -350,16 +245,4 @@ class UNet(nn.Module):
         return self._program
 
     def forward(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("stfunet.UNet runs on the gfx950 HIP kernels only; move the model and input "
-                               "to a ROCm device (no CPU fallback)")
-        prog = self.program
-        prog.flat.ensure()
-        storage = _lib.storage_for(self.storage_dtype)
-        grad = torch.is_grad_enabled()
-        res = None
-        if not (grad and x.requires_grad):
-            need_bwd = grad and prog.flat.any_requires_grad()
-            with _lib.storage(storage), torch.no_grad():   # (as inside autograd.Function.forward)
-                res = prog.runtime.forward(x, self.training, need_bwd)   # launched before autograd's bookkeeping
-        return {"out": _UNetFunction.apply(x, prog, storage, res, *prog.flat.params)}
+        return run_step(self, x)
