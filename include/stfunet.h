@@ -271,27 +271,28 @@ int stf_head_tiles(int N, int H, int W, int C);
  * multiclass Dice loss on softmax (train_utils/dice_coefficient_loss.py:5-55),
  * branch-free empty-set rule.  terms: stf_loss_scratch_floats() floats; its
  * first N*classes*3 + 1 hold (sum p*t, sum p, sum t) per (image, class) and the
- * CE sum after stf_loss_fwd; loss: device scalar. */
+ * CE sum after stf_loss_fwd; loss: device scalar.  This is the formula below with w = 1, m = 1 and
+ * Dice on (the reference's default configuration). */
 int stf_loss_scratch_floats(int N, int classes);
 int stf_loss_fwd(const float* logits, const int64_t* target, int N, int H, int W,
                  int classes, float* terms, float* loss, stf_stream_t stream);
 int stf_loss_bwd(const float* logits, const int64_t* target, int N, int H, int W,
                  int classes, const float* terms, const float* grad_out, float* dlogits,
                  stf_stream_t stream);
-/* The same criterion with the reference's options (additive: the ABI version stays 17).
- * class_weight: [classes] fp32 or NULL (all ones); ignore_index < 0: none, otherwise pixels whose
- * target equals it are masked (m = 0); dice: 0 drops the Dice term.
- *   CE   = sum m w[t] (-log p_t) / sum m w[t]          (F.cross_entropy(weight, ignore_index))
+/* The criterion above with the reference's options (additive: the ABI version stays 17); terms and
+ * loss as there, with stf_loss_opt_scratch_floats() floats and N*classes*3 + 2 leading ones: Wsum =
+ * sum m w[t] follows the (now weighted) CE sum.  class_weight: [classes] fp32 or NULL (all ones);
+ * ignore_index < 0: none, otherwise pixels whose target equals it are masked (m = 0); dice: 0 drops
+ * the Dice term.
+ *   CE   = sum m w[t] (-log p_t) / Wsum                (F.cross_entropy(weight, ignore_index))
  *   Dice = per (image, class) over the pixels with m = 1; an image with none has D = 1; the class
  *          weights do not enter it
  *   loss = CE + (dice ? 1 - mean_k mean_b D : 0)
- * terms: stf_loss_opt_scratch_floats() floats; the first N*classes*3 + 2 hold (sum p*t, sum p,
- * sum t) per (image, class), the weighted CE numerator and Wsum = sum m w[t] after the forward.
  * The backward stores an exact 0 at masked pixels (dlogits may arrive uninitialised).  A batch
  * with every pixel masked has Wsum = 0: the loss is NaN, as F.cross_entropy gives.  A target
  * outside [0, classes) other than ignore_index weighs 0 in CE and counts in no class.
  * STF_EINVAL (nothing launched) for classes outside 1..4 or 0 <= ignore_index < classes.
- * Deterministic (fixed summation order, no atomics), no host read-back. */
+ * Both families: deterministic (fixed summation order, no atomics), no host read-back. */
 int stf_loss_opt_scratch_floats(int N, int classes);
 int stf_loss_opt_fwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
                      const float* class_weight, int ignore_index, int dice, float* terms,

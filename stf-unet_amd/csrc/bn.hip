@@ -27,12 +27,6 @@ namespace {
 
 constexpr int NT = 256;
 
-STF_DEV void load_affine(const float* p, int c, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p + c);
-  const float4 b = *reinterpret_cast<const float4*>(p + c + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
-
 int tiles_per_group(long units_per_group, int groups) {
   long t = (units_per_group + NT - 1) / NT;
   const long cap = (1024 + groups - 1) / groups;    // <= FOLD16_ROWS partial rows per group
@@ -149,8 +143,8 @@ __global__ void bn_act_kernel(const uint16_t* __restrict__ y, int ycs, long N, i
     if (!POOL) {
       const int g = (int)(pix / Mg);
       float sc[8], sh[8], v[8];
-      load_affine(scale + (size_t)g * C, cg * 8, sc);
-      load_affine(shift + (size_t)g * C, cg * 8, sh);
+      load8f(scale + (size_t)g * C, cg * 8, sc);
+      load8f(shift + (size_t)g * C, cg * 8, sh);
       unpack8(*reinterpret_cast<const uint4*>(y + pix * ycs + cg * 8), v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = v[j] * sc[j] + sh[j];
@@ -159,8 +153,8 @@ __global__ void bn_act_kernel(const uint16_t* __restrict__ y, int ycs, long N, i
         unpack8(*reinterpret_cast<const uint4*>(res + pix * rcs + cg * 8), r);
         if (res_mode == 2) {
           float rs[8], rh[8];
-          load_affine(rscale + (size_t)g * C, cg * 8, rs);
-          load_affine(rshift + (size_t)g * C, cg * 8, rh);
+          load8f(rscale + (size_t)g * C, cg * 8, rs);
+          load8f(rshift + (size_t)g * C, cg * 8, rh);
 #pragma unroll
           for (int j = 0; j < 8; ++j) r[j] = r[j] * rs[j] + rh[j];
         }
@@ -179,8 +173,8 @@ __global__ void bn_act_kernel(const uint16_t* __restrict__ y, int ycs, long N, i
       const int py = rem / Wp, px = rem - py * Wp;
       const int g = (int)(n * H * W / Mg);
       float sc[8], sh[8], mx[8];
-      load_affine(scale + (size_t)g * C, cg * 8, sc);
-      load_affine(shift + (size_t)g * C, cg * 8, sh);
+      load8f(scale + (size_t)g * C, cg * 8, sc);
+      load8f(shift + (size_t)g * C, cg * 8, sh);
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
         const long p = (n * H + 2 * py + (d >> 1)) * W + 2 * px + (d & 1);
@@ -218,10 +212,10 @@ __global__ void bn_bwd_reduce_kernel(const uint16_t* __restrict__ dz, int dzcs, 
   const long gt = (long)tile * NT + threadIdx.x;
   const int cg = (int)(gt % CG);                 // constant: tpg*NT is a multiple of CG
   float sc[8], sh[8], mu[8], is[8];
-  load_affine(scale + (size_t)g * C, cg * 8, sc);
-  load_affine(shift + (size_t)g * C, cg * 8, sh);
-  load_affine(mean + (size_t)g * C, cg * 8, mu);
-  load_affine(invstd + (size_t)g * C, cg * 8, is);
+  load8f(scale + (size_t)g * C, cg * 8, sc);
+  load8f(shift + (size_t)g * C, cg * 8, sh);
+  load8f(mean + (size_t)g * C, cg * 8, mu);
+  load8f(invstd + (size_t)g * C, cg * 8, is);
   float sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sgx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (long u = gt; u < upg; u += (long)tpg * NT) {
     const long pix = u / CG + g * ppg;
@@ -334,10 +328,10 @@ __global__ __launch_bounds__(PNT) void bn_bwd_reduce_pool_kernel(const uint16_t*
   const int d = (int)(gt & 3);
   const int cg = (int)((gt >> 2) % CG);
   float sc[8], sh[8], mu[8], is[8];
-  load_affine(scale + (size_t)g * C, cg * 8, sc);
-  load_affine(shift + (size_t)g * C, cg * 8, sh);
-  load_affine(mean + (size_t)g * C, cg * 8, mu);
-  load_affine(invstd + (size_t)g * C, cg * 8, is);
+  load8f(scale + (size_t)g * C, cg * 8, sc);
+  load8f(shift + (size_t)g * C, cg * 8, sh);
+  load8f(mean + (size_t)g * C, cg * 8, mu);
+  load8f(invstd + (size_t)g * C, cg * 8, is);
   const bool relu = mask_mode == 1;
   float sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sgx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // 32-bit index math (a 64-bit division is a long emulated sequence per unit): every
@@ -498,12 +492,12 @@ __global__ void bn_bwd_apply_kernel(const uint16_t* g, int gcs, const uint16_t* 
     const int grp = (int)(pix / Mg);
     if (grp != cur_g) {
       cur_g = grp;
-      load_affine(coef + (size_t)grp * 3 * C, cg * 8, A);
-      load_affine(coef + (size_t)grp * 3 * C + C, cg * 8, B);
-      load_affine(coef + (size_t)grp * 3 * C + 2 * C, cg * 8, Cc);
+      load8f(coef + (size_t)grp * 3 * C, cg * 8, A);
+      load8f(coef + (size_t)grp * 3 * C + C, cg * 8, B);
+      load8f(coef + (size_t)grp * 3 * C + 2 * C, cg * 8, Cc);
       if (mscale) {
-        load_affine(mscale + (size_t)grp * C, cg * 8, ms);
-        load_affine(mshift + (size_t)grp * C, cg * 8, mh);
+        load8f(mscale + (size_t)grp * C, cg * 8, ms);
+        load8f(mshift + (size_t)grp * C, cg * 8, mh);
       }
     }
     float gv[8], yv[8];
@@ -552,11 +546,11 @@ __global__ __launch_bounds__(NT) void bn_act_g_kernel(const uint16_t* __restrict
   const int u0 = blockIdx.x * NT * UPT + threadIdx.x;
   const int cg = threadIdx.x & ((1 << cgs) - 1);
   float sc[8], sh[8], rs[8], rh[8];
-  load_affine(scale + (size_t)g * C, cg * 8, sc);
-  load_affine(shift + (size_t)g * C, cg * 8, sh);
+  load8f(scale + (size_t)g * C, cg * 8, sc);
+  load8f(shift + (size_t)g * C, cg * 8, sh);
   if (RES && res_mode == 2) {
-    load_affine(rscale + (size_t)g * C, cg * 8, rs);
-    load_affine(rshift + (size_t)g * C, cg * 8, rh);
+    load8f(rscale + (size_t)g * C, cg * 8, rs);
+    load8f(rshift + (size_t)g * C, cg * 8, rh);
   }
   const size_t p0 = (size_t)g * Mg;
   for (int u = u0; u < upg; u += S) {
@@ -614,11 +608,11 @@ __global__ __launch_bounds__(NT) void bn_bwd_reduce_g_kernel(const uint16_t* __r
   const int cg = threadIdx.x & (CG - 1);
   float sc[8], sh[8], mu[8], is[8];
   if (MASK == 1) {
-    load_affine(scale + (size_t)g * C, cg * 8, sc);
-    load_affine(shift + (size_t)g * C, cg * 8, sh);
+    load8f(scale + (size_t)g * C, cg * 8, sc);
+    load8f(shift + (size_t)g * C, cg * 8, sh);
   }
-  load_affine(mean + (size_t)g * C, cg * 8, mu);
-  load_affine(invstd + (size_t)g * C, cg * 8, is);
+  load8f(mean + (size_t)g * C, cg * 8, mu);
+  load8f(invstd + (size_t)g * C, cg * 8, is);
   float sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sgx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const size_t p0 = (size_t)g * Mg;
   for (int u = u0; u < upg; u += S) {
@@ -680,12 +674,12 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_g_kernel(const uint16_t* g_in
   const int u0 = blockIdx.x * NT * UPT + threadIdx.x;
   const int cg = threadIdx.x & (CG - 1);
   float A[8], B[8], Cc[8], ms[8], mh[8];
-  load_affine(coef + (size_t)g * 3 * C, cg * 8, A);
-  load_affine(coef + (size_t)g * 3 * C + C, cg * 8, B);
-  load_affine(coef + (size_t)g * 3 * C + 2 * C, cg * 8, Cc);
+  load8f(coef + (size_t)g * 3 * C, cg * 8, A);
+  load8f(coef + (size_t)g * 3 * C + C, cg * 8, B);
+  load8f(coef + (size_t)g * 3 * C + 2 * C, cg * 8, Cc);
   if (MASK) {
-    load_affine(mscale + (size_t)g * C, cg * 8, ms);
-    load_affine(mshift + (size_t)g * C, cg * 8, mh);
+    load8f(mscale + (size_t)g * C, cg * 8, ms);
+    load8f(mshift + (size_t)g * C, cg * 8, mh);
   }
   float sb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const size_t p0 = (size_t)g * Mg;
@@ -757,15 +751,15 @@ __global__ __launch_bounds__(NT) void bn_bwd_pool3_kernel(const uint8_t* __restr
   const int u0 = blockIdx.x * NT + threadIdx.x;
   const int cg = threadIdx.x & (CG - 1);
   float sc[8], sh[8], mu[8], is[8], A[8], B[8], Cc[8];
-  load_affine(scale + (size_t)g * C, cg * 8, sc);
-  load_affine(shift + (size_t)g * C, cg * 8, sh);
+  load8f(scale + (size_t)g * C, cg * 8, sc);
+  load8f(shift + (size_t)g * C, cg * 8, sh);
   if (APPLY) {
-    load_affine(coef + (size_t)g * 3 * C, cg * 8, A);
-    load_affine(coef + (size_t)g * 3 * C + C, cg * 8, B);
-    load_affine(coef + (size_t)g * 3 * C + 2 * C, cg * 8, Cc);
+    load8f(coef + (size_t)g * 3 * C, cg * 8, A);
+    load8f(coef + (size_t)g * 3 * C + C, cg * 8, B);
+    load8f(coef + (size_t)g * 3 * C + 2 * C, cg * 8, Cc);
   } else {
-    load_affine(mean + (size_t)g * C, cg * 8, mu);
-    load_affine(invstd + (size_t)g * C, cg * 8, is);
+    load8f(mean + (size_t)g * C, cg * 8, mu);
+    load8f(invstd + (size_t)g * C, cg * 8, is);
   }
   float sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sgx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // U units per iteration, all their loads issued before any use (the reduce runs <= 1024

@@ -78,6 +78,13 @@ STF_DEV uint4 pack8(const float (&f)[8]) {
 
 STF_DEV float round_e(float v) { return e2f(f2e(v)); }
 
+// eight consecutive fp32 at p + c (one channel group's scale, shift, ...; 16-B aligned) as two 16-B loads
+STF_DEV void load8f(const float* p, int c, float (&v)[8]) {
+  const float4 a = *reinterpret_cast<const float4*>(p + c);
+  const float4 b = *reinterpret_cast<const float4*>(p + c + 4);
+  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+}
+
 // LSTM activations on the hardware transcendental units (v_exp_f32, v_rcp_f32): ~1e-7
 // absolute error, far below the bf16 storage of h.  The forward cell, the backward's
 // gate recompute and the cell backward all use these, so the recomputed gates equal

@@ -3,12 +3,22 @@
 //
 // Head: a = relu(y*scale + shift) is never materialised -- 8 lanes per pixel
 // each take 8 channels, form partial logits and reduce them with xor shuffles.
-// Loss (train_and_eval.py:299-313, dice_coefficient_loss.py:5-55), per image b
-// and class k with p = softmax(logits), t = one_hot(target):
-//   I = sum p t, S = sum p + sum t, D = (2I + eps)/(S + eps)  (S == 0 -> D = 1),
-//   loss = mean CE + 1 - mean_k mean_b D.
-// Backward: dz = go * [ (p - t)/Npix + p (G - sum_j p_j G_j) ],
-//   G_k = -(1/(K*B)) dD/dp = -(1/(K*B)) (2 t/(S+eps) - (2I+eps)/(S+eps)^2).
+// Loss (train_and_eval.py:299-313, dice_coefficient_loss.py:5-55): one kernel family
+// <K, OPT> (forward partials, finalize, backward).  Per image b and class k with
+// p = softmax(logits), t = one_hot(target), class weights w (ones when absent), a pixel mask
+// m = (ignore >= 0 ? target != ignore : 1) and a Dice switch:
+//   CE = sum m w[t] (-log p_t) / Wsum, Wsum = sum m w[t]   (torch's weighted mean with ignore_index)
+//   I = sum m p t, S = sum m p + sum t, D = (2I + eps)/(S + eps)  (S == 0 -> D = 1); no weights in Dice
+//   loss = CE + (dice ? 1 - mean_k mean_b D : 0)
+// Backward: dz_k = go * [ m w[t] (p_k - t_k)/Wsum + m p_k (G_k - sum_j p_j G_j) ],
+//   G_k = -(1/(K*B)) dD/dp = -(1/(K*B)) (2 t/(S+eps) - (2I+eps)/(S+eps)^2), G = 0 with Dice off;
+//   an ignored pixel gets a stored 0 (dlogits arrives uninitialised).
+// OPT=true (stf_loss_opt_*) is that formula.  w[t] is a sum of selects over k, never an indexed read, so a
+// target outside [0, K) that is not the ignore value reads nothing and weighs 0.  A batch with every pixel
+// ignored has Wsum = 0 and the loss is 0/0 = NaN, as F.cross_entropy.
+// OPT=false (stf_loss_*, the reference's default configuration) fixes w = 1, m = 1, Dice on and Wsum = N*HW
+// in its own statements: no weight multiply, no mask select, no Wsum partial (3K+1 values per chunk, not
+// 3K+2), the target cast unchecked -- the code the default kernels had before the two families were merged.
 #include "common.h"
 #include "../../include/stfunet.h"
 #include "reduce.h"
@@ -19,12 +29,6 @@ constexpr int NT = 256;
 constexpr int MAXK = 4;          // classes supported by the fused kernels
 constexpr int LCHUNK = 64;       // loss partial chunks per image
 constexpr float DICE_EPS = 1e-6f;
-
-STF_DEV void load8f(const float* p, float (&v)[8]) {
-  const float4 a = *reinterpret_cast<const float4*>(p);
-  const float4 b = *reinterpret_cast<const float4*>(p + 4);
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-}
 
 // sum over the CG adjacent lanes of a pixel (CG a power of two <= 64), every lane gets it: DPP
 // inside a 16-lane row (quad swaps, half-row and row mirrors -- VALU, no LDS), ds_bpermute
@@ -58,10 +62,10 @@ __global__ void head_fwd_kernel(const uint16_t* __restrict__ y, long P, int HW, 
   const int units = (int)(P * CG);
   const int cg = (int)((blockIdx.x * NT + threadIdx.x) & (CG - 1));
   float sc[8], sh[8], wk[K][8], bk[K];
-  load8f(scale + cg * 8, sc);
-  load8f(shift + cg * 8, sh);
+  load8f(scale, cg * 8, sc);
+  load8f(shift, cg * 8, sh);
 #pragma unroll
-  for (int k = 0; k < K; ++k) { load8f(w + k * C + cg * 8, wk[k]); bk[k] = bias[k]; }
+  for (int k = 0; k < K; ++k) { load8f(w + k * C, cg * 8, wk[k]); bk[k] = bias[k]; }
   const int stride = gridDim.x * NT;
   for (int u0 = blockIdx.x * NT; u0 < units; u0 += stride * U) {
     uint4 raw[U];
@@ -107,12 +111,12 @@ __global__ void head_bwd_kernel(const float* __restrict__ dlogits, const uint16_
   const int gt = blockIdx.x * NT + threadIdx.x;
   const int cg = gt & (CG - 1);
   float sc[8], sh[8], mu[8], is[8], wk[K][8];
-  load8f(scale + cg * 8, sc);
-  load8f(shift + cg * 8, sh);
-  load8f(mean + cg * 8, mu);
-  load8f(invstd + cg * 8, is);
+  load8f(scale, cg * 8, sc);
+  load8f(shift, cg * 8, sh);
+  load8f(mean, cg * 8, mu);
+  load8f(invstd, cg * 8, is);
 #pragma unroll
-  for (int k = 0; k < K; ++k) load8f(w + k * C + cg * 8, wk[k]);
+  for (int k = 0; k < K; ++k) load8f(w + k * C, cg * 8, wk[k]);
   float sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sgx[8] = {0, 0, 0, 0, 0, 0, 0, 0}, dw[K][8], db[K];
 #pragma unroll
   for (int k = 0; k < K; ++k) {
@@ -193,147 +197,24 @@ __global__ void head_bwd_kernel(const float* __restrict__ dlogits, const uint16_
 }
 
 // ------------------------------------------------------------------ loss
-template <int K>
+// The option values.  The forward and the backward take them as trailing parameters O... = (cw, ignore,
+// dice); OPT=false takes none (Dice is on), so its kernels keep the default kernels' argument layout.
+template <bool OPT> struct LossOpt { static constexpr int dice = 1; };
+template <> struct LossOpt<true> { const float* cw; int ignore, dice; };
+
+template <int K, bool OPT, class... O>
 __global__ void loss_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, int HW,
-                                float* __restrict__ part) {
-  // grid (LCHUNK, N): partial[n][chunk][3K + 1]
-  constexpr int NV = 3 * K + 1;
-  __shared__ float red[NT / 64][NV];
-  const int n = blockIdx.y;
-  float s[NV];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) s[i] = 0.f;
-  for (int hw = blockIdx.x * NT + threadIdx.x; hw < HW; hw += gridDim.x * NT) {
-    float z[K], e[K], mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < K; ++k) { z[k] = logits[((long)n * K + k) * HW + hw]; mx = fmaxf(mx, z[k]); }
-    float se = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) { e[k] = expf(z[k] - mx); se += e[k]; }
-    const int t = (int)target[(long)n * HW + hw];
-    const float inv = 1.f / se, lse = logf(se);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const float p = e[k] * inv;
-      const float tk = t == k ? 1.f : 0.f;
-      s[3 * k] += p * tk;
-      s[3 * k + 1] += p;
-      s[3 * k + 2] += tk;
-      if (t == k) s[3 * K] += lse - (z[k] - mx);   // -log_softmax, stable when p underflows
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < NV; ++i) s[i] = wave_sum(s[i]);
-  if ((threadIdx.x & 63) == 0)
-#pragma unroll
-    for (int i = 0; i < NV; ++i) red[threadIdx.x >> 6][i] = s[i];
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    float a = 0.f;
-    for (int wv = 0; wv < NT / 64; ++wv) a += red[wv][threadIdx.x];
-    part[((size_t)n * gridDim.x + blockIdx.x) * NV + threadIdx.x] = a;
-  }
-}
-
-template <int K>
-__global__ void loss_finalize_kernel(const float* __restrict__ part, int N, int HW, float* __restrict__ terms,
-                                     float* __restrict__ loss) {
-  constexpr int NV = 3 * K + 1;
-  // one thread per (n, value), fixed summation order over chunks
-  __shared__ double acc[64][NV];
-  double ce = 0.0, dsum = 0.0;
-  for (int base = 0; base < N; base += 64) {
-    const int n = base + (int)threadIdx.x;
-    if (threadIdx.x < 64) {
-      for (int i = 0; i < NV; ++i) {
-        double a = 0.0;
-        if (n < N)
-          for (int c = 0; c < LCHUNK; ++c) a += part[((size_t)n * LCHUNK + c) * NV + i];
-        acc[threadIdx.x][i] = a;
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      for (int r = 0; r < 64 && base + r < N; ++r) {
-        for (int k = 0; k < K; ++k) {
-          const double I = acc[r][3 * k], S = acc[r][3 * k + 1] + acc[r][3 * k + 2];
-          const float If = (float)I, Sf = (float)S;
-          const float setsum = Sf == 0.f ? 2.f * If : Sf;
-          dsum += (double)((2.f * If + DICE_EPS) / (setsum + DICE_EPS));
-          terms[((size_t)(base + r) * K + k) * 3 + 0] = If;
-          terms[((size_t)(base + r) * K + k) * 3 + 1] = (float)acc[r][3 * k + 1];
-          terms[((size_t)(base + r) * K + k) * 3 + 2] = (float)acc[r][3 * k + 2];
-        }
-        ce += acc[r][3 * K];
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    terms[(size_t)N * K * 3] = (float)ce;
-    loss[0] = (float)(ce / ((double)N * HW) + 1.0 - dsum / ((double)N * K));
-  }
-}
-
-template <int K>
-__global__ void loss_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, int N, int HW,
-                                const float* __restrict__ terms, const float* __restrict__ grad_out,
-                                float* __restrict__ dlogits) {
-  const long P = (long)N * HW;
-  const float go = grad_out ? grad_out[0] : 1.f;
-  const float inv_pix = 1.f / (float)P;
-  const float dscale = -1.f / (float)(K * N);
-  for (long i = blockIdx.x * (long)NT + threadIdx.x; i < P; i += (long)gridDim.x * NT) {
-    const long n = i / HW, hw = i - n * HW;
-    float z[K], mx = -INFINITY;
-#pragma unroll
-    for (int k = 0; k < K; ++k) { z[k] = logits[(n * K + k) * HW + hw]; mx = fmaxf(mx, z[k]); }
-    float se = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) { z[k] = expf(z[k] - mx); se += z[k]; }
-    const int t = (int)target[i];
-    float p[K], G[K], pg = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      p[k] = z[k] / se;
-      const float I = terms[(n * K + k) * 3], S = terms[(n * K + k) * 3 + 1] + terms[(n * K + k) * 3 + 2];
-      const float tk = t == k ? 1.f : 0.f;
-      float dd = 0.f;
-      if (S != 0.f) {
-        const float den = S + DICE_EPS;
-        dd = 2.f * tk / den - (2.f * I + DICE_EPS) / (den * den);
-      }
-      G[k] = dscale * dd;
-      pg += p[k] * G[k];
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const float tk = t == k ? 1.f : 0.f;
-      dlogits[(n * K + k) * HW + hw] = go * ((p[k] - tk) * inv_pix + p[k] * (G[k] - pg));
-    }
-  }
-}
-
-// ------------------------------------------------------------------ loss with options
-// The same three kernels with class weights w (ones when absent), a pixel mask
-// m = (ignore >= 0 ? t != ignore : 1) and a Dice switch (stf_loss_opt_*):
-//   CE = sum m w[t] (-log p_t) / sum m w[t]        (torch's weighted mean with ignore_index)
-//   I, S as above over the pixels with m = 1 only; weights do not enter Dice
-//   loss = CE + (dice ? 1 - mean_k mean_b D : 0)
-// Backward: dz_k = go * [ m w[t] (p_k - [t=k]) / Wsum + m p_k (G_k - sum_j p_j G_j) ], G = 0 with
-// Dice off; an ignored pixel gets a stored 0.  w[t] is a sum of selects over k, never an indexed
-// read, so a target outside [0, K) that is not the ignore value reads nothing and weighs 0.
-// A batch with every pixel ignored has Wsum = 0 and the loss is 0/0 = NaN, as F.cross_entropy.
-template <int K>
-__global__ void loss_opt_fwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, int HW,
-                                    const float* __restrict__ cw, int ignore, float* __restrict__ part) {
-  // grid (LCHUNK, N): partial[n][chunk][3K + 2] = (I, sum p, sum t) per class, CE numerator, Wsum
-  constexpr int NV = 3 * K + 2;
+                                float* __restrict__ part, O... opt) {
+  // grid (LCHUNK, N): partial[n][chunk][NV] = (I, sum p, sum t) per class, CE numerator[, Wsum]
+  constexpr int NV = 3 * K + 1 + OPT;
+  const LossOpt<OPT> o{opt...};
   __shared__ float red[NT / 64][NV];
   const int n = blockIdx.y;
   float w[K];
+  if constexpr (OPT) {
 #pragma unroll
-  for (int k = 0; k < K; ++k) w[k] = cw ? cw[k] : 1.f;
+    for (int k = 0; k < K; ++k) w[k] = o.cw ? o.cw[k] : 1.f;
+  }
   float s[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) s[i] = 0.f;
@@ -344,20 +225,26 @@ __global__ void loss_opt_fwd_kernel(const float* __restrict__ logits, const int6
     float se = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) { e[k] = expf(z[k] - mx); se += e[k]; }
-    const int64_t t64 = target[(long)n * HW + hw];
-    const bool keep = !(ignore >= 0 && t64 == (int64_t)ignore);
-    const int t = (t64 >= 0 && t64 < K) ? (int)t64 : -1;
+    int t = (int)target[(long)n * HW + hw];
+    bool keep = true;
+    if constexpr (OPT) {              // class -1 outside [0, K): the ignore value is no class, tk = 0 there
+      const int64_t t64 = target[(long)n * HW + hw];
+      keep = !(o.ignore >= 0 && t64 == (int64_t)o.ignore);
+      t = (t64 >= 0 && t64 < K) ? (int)t64 : -1;
+    }
     const float inv = 1.f / se, lse = logf(se);
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      const float p = keep ? e[k] * inv : 0.f;
-      const float tk = t == k ? 1.f : 0.f;     // the ignore value is outside [0, K): tk = 0 there
+      float p = e[k] * inv;
+      if constexpr (OPT) p = keep ? p : 0.f;
+      const float tk = t == k ? 1.f : 0.f;
       s[3 * k] += p * tk;
       s[3 * k + 1] += p;
       s[3 * k + 2] += tk;
       if (t == k) {
-        s[3 * K] += w[k] * (lse - (z[k] - mx));
-        s[3 * K + 1] += w[k];
+        const float nll = lse - (z[k] - mx);       // -log_softmax, stable when p underflows
+        if constexpr (OPT) { s[3 * K] += w[k] * nll; s[3 * K + 1] += w[k]; }
+        else s[3 * K] += nll;
       }
     }
   }
@@ -374,10 +261,11 @@ __global__ void loss_opt_fwd_kernel(const float* __restrict__ logits, const int6
   }
 }
 
-template <int K>
-__global__ void loss_opt_finalize_kernel(const float* __restrict__ part, int N, int dice, float* __restrict__ terms,
-                                         float* __restrict__ loss) {
-  constexpr int NV = 3 * K + 2;
+// hw_or_dice: HW for OPT=false (the CE denominator is N*HW), the Dice switch for OPT=true (it is Wsum)
+template <int K, bool OPT>
+__global__ void loss_finalize_kernel(const float* __restrict__ part, int N, int hw_or_dice, float* __restrict__ terms,
+                                     float* __restrict__ loss) {
+  constexpr int NV = 3 * K + 1 + OPT;
   // one thread per (n, value), fixed summation order over chunks
   __shared__ double acc[64][NV];
   double ce = 0.0, wsum = 0.0, dsum = 0.0;
@@ -397,37 +285,44 @@ __global__ void loss_opt_finalize_kernel(const float* __restrict__ part, int N, 
         for (int k = 0; k < K; ++k) {
           const double I = acc[r][3 * k], S = acc[r][3 * k + 1] + acc[r][3 * k + 2];
           const float If = (float)I, Sf = (float)S;
-          const float setsum = Sf == 0.f ? 2.f * If : Sf;     // an image with every pixel ignored: D = 1
+          const float setsum = Sf == 0.f ? 2.f * If : Sf;     // also an image with every pixel ignored: D = 1
           dsum += (double)((2.f * If + DICE_EPS) / (setsum + DICE_EPS));
           terms[((size_t)(base + r) * K + k) * 3 + 0] = If;
           terms[((size_t)(base + r) * K + k) * 3 + 1] = (float)acc[r][3 * k + 1];
           terms[((size_t)(base + r) * K + k) * 3 + 2] = (float)acc[r][3 * k + 2];
         }
         ce += acc[r][3 * K];
-        wsum += acc[r][3 * K + 1];
+        if constexpr (OPT) wsum += acc[r][3 * K + 1];
       }
     }
     __syncthreads();
   }
   if (threadIdx.x == 0) {
     terms[(size_t)N * K * 3] = (float)ce;
-    terms[(size_t)N * K * 3 + 1] = (float)wsum;
-    loss[0] = (float)(ce / wsum + (dice ? 1.0 - dsum / ((double)N * K) : 0.0));
+    if constexpr (OPT) {
+      terms[(size_t)N * K * 3 + 1] = (float)wsum;
+      loss[0] = (float)(ce / wsum + (hw_or_dice ? 1.0 - dsum / ((double)N * K) : 0.0));
+    } else {
+      loss[0] = (float)(ce / ((double)N * hw_or_dice) + 1.0 - dsum / ((double)N * K));
+    }
   }
 }
 
-template <int K>
-__global__ void loss_opt_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, int N,
-                                    int HW, const float* __restrict__ cw, int ignore, int dice,
-                                    const float* __restrict__ terms, const float* __restrict__ grad_out,
-                                    float* __restrict__ dlogits) {
+template <int K, bool OPT, class... O>
+__global__ void loss_bwd_kernel(const float* __restrict__ logits, const int64_t* __restrict__ target, int N, int HW,
+                                const float* __restrict__ terms, const float* __restrict__ grad_out,
+                                float* __restrict__ dlogits, O... opt) {
+  const LossOpt<OPT> o{opt...};
   const long P = (long)N * HW;
   const float go = grad_out ? grad_out[0] : 1.f;
-  const float inv_w = 1.f / terms[(size_t)N * K * 3 + 1];
+  float inv_den = 1.f / (float)P;      // 1 / the CE denominator: the pixel count, or Wsum
+  if constexpr (OPT) inv_den = 1.f / terms[(size_t)N * K * 3 + 1];
   const float dscale = -1.f / (float)(K * N);
   float w[K];
+  if constexpr (OPT) {
 #pragma unroll
-  for (int k = 0; k < K; ++k) w[k] = cw ? cw[k] : 1.f;
+    for (int k = 0; k < K; ++k) w[k] = o.cw ? o.cw[k] : 1.f;
+  }
   for (long i = blockIdx.x * (long)NT + threadIdx.x; i < P; i += (long)gridDim.x * NT) {
     const long n = i / HW, hw = i - n * HW;
     float z[K], mx = -INFINITY;
@@ -436,17 +331,21 @@ __global__ void loss_opt_bwd_kernel(const float* __restrict__ logits, const int6
     float se = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) { z[k] = expf(z[k] - mx); se += z[k]; }
-    const int64_t t64 = target[i];
-    const bool keep = !(ignore >= 0 && t64 == (int64_t)ignore);
-    const int t = (t64 >= 0 && t64 < K) ? (int)t64 : -1;
+    int t = (int)target[i];
+    bool keep = true;
+    if constexpr (OPT) {              // class -1 outside [0, K): the ignore value is no class, tk = 0 there
+      const int64_t t64 = target[i];
+      keep = !(o.ignore >= 0 && t64 == (int64_t)o.ignore);
+      t = (t64 >= 0 && t64 < K) ? (int)t64 : -1;
+    }
     float p[K], G[K], pg = 0.f, wt = 0.f;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       p[k] = z[k] / se;
       const float tk = t == k ? 1.f : 0.f;
-      wt += tk * w[k];
+      if constexpr (OPT) wt += tk * w[k];
       float dd = 0.f;
-      if (dice) {
+      if (o.dice) {
         const float I = terms[(n * K + k) * 3], S = terms[(n * K + k) * 3 + 1] + terms[(n * K + k) * 3 + 2];
         if (S != 0.f) {
           const float den = S + DICE_EPS;
@@ -456,12 +355,14 @@ __global__ void loss_opt_bwd_kernel(const float* __restrict__ logits, const int6
       G[k] = dscale * dd;
       pg += p[k] * G[k];
     }
-    const float cs = wt * inv_w;
+    float cs = inv_den;
+    if constexpr (OPT) cs = wt * inv_den;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
       const float tk = t == k ? 1.f : 0.f;
       const float g = go * ((p[k] - tk) * cs + p[k] * (G[k] - pg));
-      dlogits[(n * K + k) * HW + hw] = keep ? g : 0.f;     // dlogits arrives uninitialised
+      if constexpr (OPT) dlogits[(n * K + k) * HW + hw] = keep ? g : 0.f;
+      else dlogits[(n * K + k) * HW + hw] = g;
     }
   }
 }
@@ -527,67 +428,66 @@ extern "C" int stf_head_bwd(const float* dlogits, const void* y, int N, int H, i
   return 0;
 }
 
-extern "C" int stf_loss_scratch_floats(int N, int classes) {
-  return N * classes * 3 + 1 + N * LCHUNK * (3 * classes + 1);
+// terms = [N][K][3] Dice sums, the CE numerator[, Wsum], then the forward's [N][LCHUNK][NV] partials
+static int loss_scratch_floats(int N, int K, bool opt) {
+  return N * K * 3 + 1 + opt + N * LCHUNK * (3 * K + 1 + opt);
 }
 
-extern "C" int stf_loss_fwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
-                            float* terms, float* loss, stf_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  float* part = terms + N * classes * 3 + 1;
+template <bool OPT, class... O>
+static int loss_fwd(const float* logits, const int64_t* target, int N, int HW, int classes, float* terms, float* loss,
+                    hipStream_t s, O... opt) {
+  float* part = terms + N * classes * 3 + 1 + OPT;
+  const int hw_or_dice = OPT ? LossOpt<OPT>{opt...}.dice : HW;
   STF_KDISPATCH(classes, {
-    hipLaunchKernelGGL(loss_fwd_kernel<KK>, dim3(LCHUNK, N), dim3(NT), 0, s, logits, target, H * W, part);
-    hipLaunchKernelGGL(loss_finalize_kernel<KK>, dim3(1), dim3(64), 0, s, part, N, H * W, terms, loss);
+    hipLaunchKernelGGL((loss_fwd_kernel<KK, OPT, O...>), dim3(LCHUNK, N), dim3(NT), 0, s, logits, target, HW, part,
+                       opt...);
+    hipLaunchKernelGGL((loss_finalize_kernel<KK, OPT>), dim3(1), dim3(64), 0, s, part, N, hw_or_dice, terms, loss);
   });
   STF_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int stf_loss_bwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
-                            const float* terms, const float* grad_out, float* dlogits, stf_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const long P = (long)N * H * W;
+template <bool OPT, class... O>
+static int loss_bwd(const float* logits, const int64_t* target, int N, int HW, int classes, const float* terms,
+                    const float* grad_out, float* dlogits, hipStream_t s, O... opt) {
+  const long P = (long)N * HW;
   long blocks = (P + NT - 1) / NT;
   if (blocks > 8192) blocks = 8192;
-  STF_KDISPATCH(classes, hipLaunchKernelGGL(loss_bwd_kernel<KK>, dim3(blocks), dim3(NT), 0, s, logits, target, N,
-                                            H * W, terms, grad_out, dlogits));
+  STF_KDISPATCH(classes, hipLaunchKernelGGL((loss_bwd_kernel<KK, OPT, O...>), dim3(blocks), dim3(NT), 0, s, logits,
+                                            target, N, HW, terms, grad_out, dlogits, opt...));
   STF_CHECK_LAUNCH();
   return 0;
-}
-
-extern "C" int stf_loss_opt_scratch_floats(int N, int classes) {
-  return N * classes * 3 + 2 + N * LCHUNK * (3 * classes + 2);
 }
 
 static bool loss_opt_ok(int classes, int ignore_index) {
   return classes >= 1 && classes <= MAXK && !(ignore_index >= 0 && ignore_index < classes);
 }
 
+extern "C" int stf_loss_scratch_floats(int N, int classes) { return loss_scratch_floats(N, classes, false); }
+extern "C" int stf_loss_opt_scratch_floats(int N, int classes) { return loss_scratch_floats(N, classes, true); }
+
+extern "C" int stf_loss_fwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
+                            float* terms, float* loss, stf_stream_t stream) {
+  return loss_fwd<false>(logits, target, N, H * W, classes, terms, loss, (hipStream_t)stream);
+}
+
+extern "C" int stf_loss_bwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
+                            const float* terms, const float* grad_out, float* dlogits, stf_stream_t stream) {
+  return loss_bwd<false>(logits, target, N, H * W, classes, terms, grad_out, dlogits, (hipStream_t)stream);
+}
+
 extern "C" int stf_loss_opt_fwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
                                 const float* class_weight, int ignore_index, int dice, float* terms, float* loss,
                                 stf_stream_t stream) {
   if (!loss_opt_ok(classes, ignore_index)) return STF_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  float* part = terms + N * classes * 3 + 2;
-  STF_KDISPATCH(classes, {
-    hipLaunchKernelGGL(loss_opt_fwd_kernel<KK>, dim3(LCHUNK, N), dim3(NT), 0, s, logits, target, H * W, class_weight,
-                       ignore_index, part);
-    hipLaunchKernelGGL(loss_opt_finalize_kernel<KK>, dim3(1), dim3(64), 0, s, part, N, dice, terms, loss);
-  });
-  STF_CHECK_LAUNCH();
-  return 0;
+  return loss_fwd<true>(logits, target, N, H * W, classes, terms, loss, (hipStream_t)stream, class_weight,
+                        ignore_index, dice);
 }
 
 extern "C" int stf_loss_opt_bwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
                                 const float* class_weight, int ignore_index, int dice, const float* terms,
                                 const float* grad_out, float* dlogits, stf_stream_t stream) {
   if (!loss_opt_ok(classes, ignore_index)) return STF_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const long P = (long)N * H * W;
-  long blocks = (P + NT - 1) / NT;
-  if (blocks > 8192) blocks = 8192;
-  STF_KDISPATCH(classes, hipLaunchKernelGGL(loss_opt_bwd_kernel<KK>, dim3(blocks), dim3(NT), 0, s, logits, target, N,
-                                            H * W, class_weight, ignore_index, dice, terms, grad_out, dlogits));
-  STF_CHECK_LAUNCH();
-  return 0;
+  return loss_bwd<true>(logits, target, N, H * W, classes, terms, grad_out, dlogits, (hipStream_t)stream,
+                        class_weight, ignore_index, dice);
 }

@@ -29,32 +29,8 @@ from ._lib import call, stream
 
 
 class _CEDice(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, logits, target):
-        logits = logits.detach().contiguous().float()
-        target = target.contiguous()
-        if target.dtype != torch.int64:
-            target = target.long()
-        N, K, H, W = logits.shape
-        assert target.shape == (N, H, W), f"target {tuple(target.shape)} vs logits {tuple(logits.shape)}"
-        terms = torch.empty(_lib.load().stf_loss_scratch_floats(N, K), dtype=torch.float32, device=logits.device)
-        loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        call("stf_loss_fwd", _p(logits), _p(target), N, H, W, K, _p(terms), _p(loss), stream())
-        ctx.save_for_backward(logits, target, terms)
-        return loss
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        logits, target, terms = ctx.saved_tensors
-        N, K, H, W = logits.shape
-        go = grad_out.detach().float().contiguous().reshape(1)
-        dl = torch.empty_like(logits)
-        call("stf_loss_bwd", _p(logits), _p(target), N, H, W, K, _p(terms), _p(go), _p(dl), stream())
-        return dl, None
-
-
-class _CEDiceOpt(torch.autograd.Function):
-    """CE + Dice with class weights, an ignored target value and the Dice switch."""
+    """CE + Dice.  The reference's default configuration (no class weights, no ignored target value,
+    Dice on) calls the default entry points, anything else the option ones."""
 
     @staticmethod
     def forward(ctx, logits, target, weight, ignore_index, dice):
@@ -64,14 +40,16 @@ class _CEDiceOpt(torch.autograd.Function):
             target = target.long()
         N, K, H, W = logits.shape
         assert target.shape == (N, H, W), f"target {tuple(target.shape)} vs logits {tuple(logits.shape)}"
-        terms = torch.empty(_lib.load().stf_loss_opt_scratch_floats(N, K), dtype=torch.float32,
-                            device=logits.device)
+        if weight is None and dice and ignore_index < 0:
+            scratch, fwd, ctx.bwd, ctx.opts = "stf_loss_scratch_floats", "stf_loss_fwd", "stf_loss_bwd", ()
+        else:
+            scratch, fwd, ctx.bwd = "stf_loss_opt_scratch_floats", "stf_loss_opt_fwd", "stf_loss_opt_bwd"
+            ctx.opts = (_p(weight) if weight is not None else None, ignore_index, int(dice))
+            ctx.weight = weight                 # keeps the pointer in ctx.opts alive
+        terms = torch.empty(getattr(_lib.load(), scratch)(N, K), dtype=torch.float32, device=logits.device)
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
-        wp = _p(weight) if weight is not None else None
-        call("stf_loss_opt_fwd", _p(logits), _p(target), N, H, W, K, wp, ignore_index, int(dice), _p(terms),
-             _p(loss), stream())
+        call(fwd, _p(logits), _p(target), N, H, W, K, *ctx.opts, _p(terms), _p(loss), stream())
         ctx.save_for_backward(logits, target, terms)
-        ctx.weight, ctx.ignore_index, ctx.dice = weight, ignore_index, int(dice)
         return loss
 
     @staticmethod
@@ -80,9 +58,7 @@ class _CEDiceOpt(torch.autograd.Function):
         N, K, H, W = logits.shape
         go = grad_out.detach().float().contiguous().reshape(1)
         dl = torch.empty_like(logits)
-        wp = _p(ctx.weight) if ctx.weight is not None else None
-        call("stf_loss_opt_bwd", _p(logits), _p(target), N, H, W, K, wp, ctx.ignore_index, ctx.dice, _p(terms),
-             _p(go), _p(dl), stream())
+        call(ctx.bwd, _p(logits), _p(target), N, H, W, K, *ctx.opts, _p(terms), _p(go), _p(dl), stream())
         return dl, None, None, None, None
 
 
@@ -112,9 +88,7 @@ def ce_dice_loss(logits, target, weight=None, ignore_index=-100, dice=True):
     weight = _class_weight(weight, K, logits.device)
     if not logits.is_cuda:
         raise RuntimeError("stfunet loss kernels need a ROCm device (no CPU fallback)")
-    if weight is None and dice and ignore_index < 0:
-        return _CEDice.apply(logits, target)
-    return _CEDiceOpt.apply(logits, target, weight, ignore_index, bool(dice))
+    return _CEDice.apply(logits, target, weight, ignore_index, bool(dice))
 
 
 def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool = True, ignore_index: int = -100):

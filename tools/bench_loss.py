@@ -1,14 +1,16 @@
-"""Loss-kernel pair timing at the cfg2 shape (64 x 2 x 256 x 256 logits): the option kernels
-(stf_loss_opt_fwd + stf_loss_opt_bwd: class weights, ignore_index 255, Dice on) against the
-default pair (stf_loss_fwd + stf_loss_bwd) on the same logits and target, and once more on a
-target with a padded band of 255; interleaved in one process, HIP events over --reps launches
-per round after warm-up.
+"""Loss-kernel pair timing at the cfg2 shape (64 x 2 x 256 x 256 logits): the option entry points
+(stf_loss_opt_fwd + stf_loss_opt_bwd, the OPT=true kernels: class weights, ignore_index 255, Dice
+on) against the default pair (stf_loss_fwd + stf_loss_bwd, OPT=false) on the same logits and
+target, and once more on a target with a padded band of 255; interleaved in one process, HIP
+events over --reps launches per round after warm-up.
 
     python tools/bench_loss.py [--base-lib PATH] [--reps 100] [--rounds 7] [--out FILE]
 
---base-lib: take the default pair from another build of the library (e.g. the parent commit's
-libstfunet_hip.so) instead of the one in the tree.  Prints per-round times, then one JSON line
-with the medians and minima (us per fwd + bwd pair) and their ratio."""
+--base-lib: another build of the library (e.g. the parent commit's libstfunet_hip.so).  Its
+default pair and its option pair are timed in the same rounds beside this tree's, so each pair
+is compared like for like against the base build's own round-to-round spread.  Prints per-round
+times, then one JSON line with the medians, minima and spreads (us per fwd + bwd pair) and the
+ratios."""
 import argparse
 import ctypes
 import json
@@ -37,7 +39,8 @@ lib = _lib.load()
 base = lib
 if args.base_lib:
     base = ctypes.CDLL(os.path.abspath(args.base_lib))
-    for name in ("stf_loss_scratch_floats", "stf_loss_fwd", "stf_loss_bwd"):
+    for name in ("stf_loss_scratch_floats", "stf_loss_fwd", "stf_loss_bwd", "stf_loss_opt_scratch_floats",
+                 "stf_loss_opt_fwd", "stf_loss_opt_bwd"):
         getattr(base, name).restype, getattr(base, name).argtypes = _lib._SIGS[name]
 
 g = torch.Generator(device=dev).manual_seed(0)
@@ -46,7 +49,7 @@ target = (torch.rand(N, H, W, device=dev, generator=g) > 0.9).long()
 padded = target.clone()
 padded[:, :, W - W // 8:] = 255                       # a collate-padded band
 weight = torch.linspace(0.5, 2.0, K, device=dev)
-terms = torch.empty(max(lib.stf_loss_opt_scratch_floats(N, K), base.stf_loss_scratch_floats(N, K)), device=dev)
+terms = torch.empty(max(lib.stf_loss_opt_scratch_floats(N, K), base.stf_loss_opt_scratch_floats(N, K)), device=dev)
 loss, go, dl = torch.empty(1, device=dev), torch.ones(1, device=dev), torch.empty_like(logits)
 
 
@@ -55,24 +58,32 @@ def check(rc):
         raise RuntimeError(f"launch failed: {rc}")
 
 
+def default_on(l):
+    s = stream()
+    check(l.stf_loss_fwd(_p(logits), _p(target), N, H, W, K, _p(terms), _p(loss), s))
+    check(l.stf_loss_bwd(_p(logits), _p(target), N, H, W, K, _p(terms), _p(go), _p(dl), s))
+
+
+def opt_on(l, t):
+    s = stream()
+    check(l.stf_loss_opt_fwd(_p(logits), _p(t), N, H, W, K, _p(weight), 255, 1, _p(terms), _p(loss), s))
+    check(l.stf_loss_opt_bwd(_p(logits), _p(t), N, H, W, K, _p(weight), 255, 1, _p(terms), _p(go), _p(dl), s))
+
+
 def base_pair():
-    s = stream()
-    check(base.stf_loss_fwd(_p(logits), _p(target), N, H, W, K, _p(terms), _p(loss), s))
-    check(base.stf_loss_bwd(_p(logits), _p(target), N, H, W, K, _p(terms), _p(go), _p(dl), s))
-
-
-def opt_on(t):
-    s = stream()
-    check(lib.stf_loss_opt_fwd(_p(logits), _p(t), N, H, W, K, _p(weight), 255, 1, _p(terms), _p(loss), s))
-    check(lib.stf_loss_opt_bwd(_p(logits), _p(t), N, H, W, K, _p(weight), 255, 1, _p(terms), _p(go), _p(dl), s))
+    default_on(base)
 
 
 def opt_pair():            # the default pair's own target: like for like
-    opt_on(target)
+    opt_on(lib, target)
 
 
 def opt_pair_padded():     # a W/8 band of 255, as a collated mixed-size batch has
-    opt_on(padded)
+    opt_on(lib, padded)
+
+
+# with --base-lib: this tree's default pair and the base build's option pair, for the per-pair A/B
+EXTRA = {"new_default_pair_us": lambda: default_on(lib), "base_option_pair_us": lambda: opt_on(base, target)}
 
 
 def timeit(fn):
@@ -85,22 +96,34 @@ def timeit(fn):
     return e0.elapsed_time(e1) / args.reps * 1e3     # us per pair
 
 
-for fn in (base_pair, opt_pair, opt_pair_padded):
+extra = EXTRA if args.base_lib else {}
+for fn in (base_pair, opt_pair, opt_pair_padded, *extra.values()):
     for _ in range(20):
         fn()
 torch.cuda.synchronize()
-tb, to, tp = [], [], []
+tb, to, tp, tx = [], [], [], {k: [] for k in extra}
 for r in range(args.rounds):
     tb.append(timeit(base_pair))
     to.append(timeit(opt_pair))
     tp.append(timeit(opt_pair_padded))
+    for k, fn in extra.items():
+        tx[k].append(timeit(fn))
     print(f"round {r}: default pair {tb[-1]:8.2f} us   option pair {to[-1]:8.2f} us   "
-          f"option pair, padded target {tp[-1]:8.2f} us", flush=True)
+          f"option pair, padded target {tp[-1]:8.2f} us" +
+          "".join(f"   {k[:-3].replace('_', ' ')} {v[-1]:8.2f} us" for k, v in tx.items()), flush=True)
 res = {"shape": [N, K, H, W], "reps": args.reps, "rounds": args.rounds, "base_lib": args.base_lib or "in-tree",
        "default_pair_us": {"median": statistics.median(tb), "min": min(tb)},
        "option_pair_us": {"median": statistics.median(to), "min": min(to)},
        "option_pair_padded_us": {"median": statistics.median(tp), "min": min(tp)},
        "ratio_median": statistics.median(to) / statistics.median(tb)}
+if extra:           # new / base per pair, and the base build's own spread (max - min) / median over the rounds
+    def spread(t):
+        return (max(t) - min(t)) / statistics.median(t)
+    res.update({k: {"median": statistics.median(v), "min": min(v), "spread": spread(v)} for k, v in tx.items()})
+    res["default_pair_us"]["spread"] = spread(tb)
+    res["option_pair_us"]["spread"] = spread(to)
+    res["default_new_over_base"] = statistics.median(tx["new_default_pair_us"]) / statistics.median(tb)
+    res["option_new_over_base"] = statistics.median(to) / statistics.median(tx["base_option_pair_us"])
 line = json.dumps(res)
 print(line)
 if args.out:
