@@ -300,6 +300,29 @@ int stf_loss_opt_fwd(const float* logits, const int64_t* target, int N, int H, i
 int stf_loss_opt_bwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
                      const float* class_weight, int ignore_index, int dice, const float* terms,
                      const float* grad_out, float* dlogits, stf_stream_t stream);
+/* Head and criterion for 1..16 classes (additive: the ABI version stays 17).  Arguments, layouts
+ * and formulas are those of stf_head_fwd / stf_head_bwd and of stf_loss_opt_fwd / stf_loss_opt_bwd
+ * (stf_loss_mc_scratch_floats = N*classes*3 + 2 + N*64*(3*classes + 2), 0 for classes outside
+ * 1..16); the kernels take the class count at run time, keep the head's weights in LDS and spill
+ * nothing.  The entry points above stay as they are for classes <= 4 (their results are pinned bit
+ * for bit); the Python package sends classes >= 5 here.  STF_EINVAL (nothing launched) for classes
+ * outside 1..16, 0 <= ignore_index < classes, a C that stf_head_fwd refuses, N > 65535 images in
+ * the criterion, a NULL required pointer (class_weight and grad_out may be NULL).  Deterministic. */
+int stf_head_mc_fwd(const void* y, int N, int H, int W, int C, const float* scale,
+                    const float* shift, const float* w, const float* bias, int classes,
+                    float* logits, stf_stream_t stream);
+int stf_head_mc_bwd(const float* dlogits, const void* y, int N, int H, int W, int C,
+                    const float* scale, const float* shift, const float* mean,
+                    const float* invstd, const float* w, int classes, void* g_out,
+                    float* bn_partial, float* head_partial, float* dw, float* db,
+                    stf_stream_t stream);
+int stf_loss_mc_scratch_floats(int N, int classes);
+int stf_loss_mc_fwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
+                    const float* class_weight, int ignore_index, int dice, float* terms,
+                    float* loss, stf_stream_t stream);
+int stf_loss_mc_bwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
+                    const float* class_weight, int ignore_index, int dice, const float* terms,
+                    const float* grad_out, float* dlogits, stf_stream_t stream);
 
 /* ---------------------------------------------------------------- optimizer
  * torch.optim.AdamW(lr, betas, eps, weight_decay) (train.py:230-237) over one

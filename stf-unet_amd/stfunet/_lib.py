@@ -136,6 +136,11 @@ _SIGS = {
     "stf_loss_opt_scratch_floats": (c_int, [c_int, c_int]),
     "stf_loss_opt_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
     "stf_loss_opt_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P]),
+    "stf_head_mc_fwd": (c_int, [P, c_int, c_int, c_int, c_int, P, P, P, P, c_int, P, P]),
+    "stf_head_mc_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P, P, P, P, P, c_int, P, P, P, P, P, P]),
+    "stf_loss_mc_scratch_floats": (c_int, [c_int, c_int]),
+    "stf_loss_mc_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
+    "stf_loss_mc_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P]),
     "stf_adamw": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float,
                           P]),
     "stf_adamw_dev": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, P]),

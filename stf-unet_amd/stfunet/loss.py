@@ -20,17 +20,21 @@ The reference's three options run on the device as well (``stf_loss_opt_fwd`` /
   empty-set rule); a batch whose pixels are all ignored has a NaN loss, as
   ``F.cross_entropy`` gives -- not special-cased.
 * ``dice=False``: cross-entropy only.
+
+Logits of 5 to 16 classes take the many-class kernels (``stf_loss_mc_fwd`` / ``stf_loss_mc_bwd``:
+the same formula, the options as run-time arguments); more than 16 is a ValueError.
 """
 import torch
 
 from . import _lib
-from .nhwc import _p
+from .nhwc import _p, check_num_classes
 from ._lib import call, stream
 
 
 class _CEDice(torch.autograd.Function):
-    """CE + Dice.  The reference's default configuration (no class weights, no ignored target value,
-    Dice on) calls the default entry points, anything else the option ones."""
+    """CE + Dice.  Up to four classes: the reference's default configuration (no class weights, no
+    ignored target value, Dice on) calls the default entry points, anything else the option ones.
+    Five to sixteen classes: the many-class entry points in every configuration."""
 
     @staticmethod
     def forward(ctx, logits, target, weight, ignore_index, dice):
@@ -40,10 +44,13 @@ class _CEDice(torch.autograd.Function):
             target = target.long()
         N, K, H, W = logits.shape
         assert target.shape == (N, H, W), f"target {tuple(target.shape)} vs logits {tuple(logits.shape)}"
-        if weight is None and dice and ignore_index < 0:
+        if K > 4:
+            scratch, fwd, ctx.bwd = "stf_loss_mc_scratch_floats", "stf_loss_mc_fwd", "stf_loss_mc_bwd"
+        elif weight is None and dice and ignore_index < 0:
             scratch, fwd, ctx.bwd, ctx.opts = "stf_loss_scratch_floats", "stf_loss_fwd", "stf_loss_bwd", ()
         else:
             scratch, fwd, ctx.bwd = "stf_loss_opt_scratch_floats", "stf_loss_opt_fwd", "stf_loss_opt_bwd"
+        if ctx.bwd != "stf_loss_bwd":
             ctx.opts = (_p(weight) if weight is not None else None, ignore_index, int(dice))
             ctx.weight = weight                 # keeps the pointer in ctx.opts alive
         terms = torch.empty(getattr(_lib.load(), scratch)(N, K), dtype=torch.float32, device=logits.device)
@@ -84,6 +91,7 @@ def _check_ignore(ignore_index, num_classes):
 def ce_dice_loss(logits, target, weight=None, ignore_index=-100, dice=True):
     ignore_index = int(ignore_index)
     K = logits.shape[1]
+    check_num_classes(K)
     _check_ignore(ignore_index, K)
     weight = _class_weight(weight, K, logits.device)
     if not logits.is_cuda:
@@ -101,6 +109,7 @@ def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool
     is not ``num_classes``.  A weight that is not yet a tensor on the logits' device is copied
     there on every call; a training loop converts it once (``engine.train_one_epoch`` does).
     """
+    check_num_classes(num_classes)
     _check_ignore(int(ignore_index), num_classes)
     loss_weight = _class_weight(loss_weight, num_classes)
     losses = {name: ce_dice_loss(x, target, loss_weight, ignore_index, dice) for name, x in inputs.items()}

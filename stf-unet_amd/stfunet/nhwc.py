@@ -818,21 +818,37 @@ def bn_backward_from_partial(g: Feat, y: Feat, st: BNState, bn, part, tiles, dga
 
 
 # ------------------------------------------------------------------ head
+MAX_CLASSES = 16
+
+
+def check_num_classes(K):
+    """ValueError unless the head and criterion kernels take K classes (the models call it at construction)."""
+    if not 1 <= K <= MAX_CLASSES:
+        raise ValueError(f"num_classes={K}: the head and criterion kernels take 1 to {MAX_CLASSES} classes")
+
+
+def _head_entry(name, K):
+    """The head's entry point for K classes: up to four the kernels with the class count as a template
+    argument, five to sixteen the many-class ones (same arguments, outputs and buffer sizes)."""
+    check_num_classes(K)
+    return f"stf_head_mc_{name}" if K > 4 else f"stf_head_{name}"
+
+
 def head_fwd(y: Feat, st: BNState, conv, logits):
-    """logits [N, K, H, W] fp32 = the 1x1 conv ``conv`` over relu(BN(y)), one pass (stf_head_fwd; ``st``
+    """logits [N, K, H, W] fp32 = the 1x1 conv ``conv`` over relu(BN(y)), one pass (_head_entry; ``st``
     = the BatchNorm state of ``y``, or an identity state where the ReLU is already applied).
     Returns the [K, C] weight view that head_bwd reads."""
     y.check()
     K = conv.out_channels
     assert y.cs == y.C and y.off == 0 and tuple(logits.shape) == (y.N, K, y.H, y.W)
     head_w = conv.weight.detach().reshape(K, -1).contiguous()
-    call("stf_head_fwd", y.ptr(), y.N, y.H, y.W, y.C, _p(st.scale), _p(st.shift), _p(head_w), _p(conv.bias.detach()),
+    call(_head_entry("fwd", K), y.ptr(), y.N, y.H, y.W, y.C, _p(st.scale), _p(st.shift), _p(head_w), _p(conv.bias.detach()),
          K, _p(logits), stream())
     return head_w
 
 
 def head_bwd(dlogits, y: Feat, st: BNState, head_w, dweight, dbias):
-    """Backward of head_fwd (stf_head_bwd): the 1x1 conv's weight / bias gradients into ``dweight`` /
+    """Backward of head_fwd (_head_entry): the 1x1 conv's weight / bias gradients into ``dweight`` /
     ``dbias`` and g = the ReLU-masked gradient w.r.t. BN(y), with the BN-backward partial sums of
     g reduced in the same pass.  Returns (g, partial sums, tiles) for bn_backward_from_partial."""
     y.check()
@@ -842,6 +858,6 @@ def head_bwd(dlogits, y: Feat, st: BNState, head_w, dweight, dbias):
     g = new_feat(y.N, y.H, y.W, C, dev)
     bnp = empty(tiles * 2 * C, torch.float32, dev)
     hp = empty((tiles + 1) * K * (C + 1), torch.float32, dev)
-    call("stf_head_bwd", _p(dlogits), y.ptr(), y.N, y.H, y.W, C, _p(st.scale), _p(st.shift), _p(st.mean),
+    call(_head_entry("bwd", K), _p(dlogits), y.ptr(), y.N, y.H, y.W, C, _p(st.scale), _p(st.shift), _p(st.mean),
          _p(st.invstd), _p(head_w), K, g.ptr(), _p(bnp), _p(hp), _p(dweight), _p(dbias), stream())
     return g, bnp, tiles

@@ -746,6 +746,7 @@ def _check_input_shape(shape, P):
 class STFLSTMUNet(nn.Module):
     def __init__(self, in_channels=1, num_classes=2, time_steps=8, use_pk_maps=False, pk_channels=3):
         super().__init__()
+        nhwc.check_num_classes(num_classes)
         self.time_steps = time_steps
         self.use_pk_maps = use_pk_maps
         self.pk_channels = pk_channels if use_pk_maps else 0

@@ -217,6 +217,7 @@ class UNet(nn.Module):
 
     def __init__(self, in_channels=8, num_classes=2, base_c=64):
         super().__init__()
+        nhwc.check_num_classes(num_classes)
         self.in_channels = in_channels
         self.enc1 = _double_conv(in_channels, base_c)
         self.enc2 = _double_conv(base_c, base_c * 2)

@@ -10,7 +10,15 @@ events over --reps launches per round after warm-up.
 default pair and its option pair are timed in the same rounds beside this tree's, so each pair
 is compared like for like against the base build's own round-to-round spread.  Prints per-round
 times, then one JSON line with the medians, minima and spreads (us per fwd + bwd pair) and the
-ratios."""
+ratios.
+
+    python tools/bench_loss.py --classes 4,8,16 [--channels 64] [--base-lib PATH] [--out FILE]
+
+--classes: the four full-resolution passes of the many-class kernels instead (stf_loss_mc_fwd, stf_loss_mc_bwd,
+stf_head_mc_fwd, stf_head_mc_bwd) at the shape's N, H, W and --channels head inputs, one JSON line per class
+count with us per launch and TB/s on algorithmic bytes (loss fwd 4K+8, loss bwd 8K+8, head fwd 2C+4K, head bwd
+4C+4K bytes per pixel).  For K <= 4 the templated siblings (stf_loss_fwd/bwd, stf_head_fwd/bwd; of --base-lib
+when given) are timed in the same rounds and the line carries the four mc / sibling ratios."""
 import argparse
 import ctypes
 import json
@@ -31,6 +39,8 @@ ap.add_argument("--reps", type=int, default=100)
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--shape", default="64,2,256,256")
 ap.add_argument("--out", default=None)
+ap.add_argument("--classes", default=None, help="comma-separated class counts: time the many-class passes")
+ap.add_argument("--channels", type=int, default=64)
 args = ap.parse_args()
 
 N, K, H, W = (int(v) for v in args.shape.split(","))
@@ -42,6 +52,77 @@ if args.base_lib:
     for name in ("stf_loss_scratch_floats", "stf_loss_fwd", "stf_loss_bwd", "stf_loss_opt_scratch_floats",
                  "stf_loss_opt_fwd", "stf_loss_opt_bwd"):
         getattr(base, name).restype, getattr(base, name).argtypes = _lib._SIGS[name]
+
+
+
+def many_class_passes(K):
+    """Median us per launch of the four passes at K classes, mc and (K <= 4) templated sibling, interleaved."""
+    C, P = args.channels, N * H * W
+    gen = torch.Generator(device=dev).manual_seed(K)
+    x = torch.randn(N, K, H, W, device=dev, generator=gen) * 2
+    t = torch.randint(0, K, (N, H, W), device=dev, generator=gen)
+    y = torch.randn(P * C, device=dev, generator=gen).to(torch.bfloat16)
+    vec = [torch.rand(C, device=dev, generator=gen) + 0.5 for _ in range(4)]       # scale, shift, mean, invstd
+    w, b = torch.randn(K * C, device=dev, generator=gen) / 8, torch.randn(K, device=dev, generator=gen)
+    trm = torch.empty(lib.stf_loss_mc_scratch_floats(N, K), device=dev)
+    out1, one, dx = torch.empty(1, device=dev), torch.ones(1, device=dev), torch.empty_like(x)
+    tiles = lib.stf_head_tiles(N, H, W, C)
+    gout = torch.empty(P * C, device=dev, dtype=torch.bfloat16)
+    bnp, hp = torch.empty(tiles * 2 * C, device=dev), torch.empty((tiles + 1) * K * (C + 1), device=dev)
+    dw, db = torch.empty(K * C, device=dev), torch.empty(K, device=dev)
+    sc, sh, mu, iv = (_p(v) for v in vec)
+    head_b = (_p(dx), _p(y), N, H, W, C, sc, sh, mu, iv, _p(w), K, _p(gout), _p(bnp), _p(hp), _p(dw), _p(db))
+    passes = {
+        "loss_fwd": (lambda: lib.stf_loss_mc_fwd(_p(x), _p(t), N, H, W, K, None, -100, 1, _p(trm), _p(out1), stream()),
+                     lambda: base.stf_loss_fwd(_p(x), _p(t), N, H, W, K, _p(trm), _p(out1), stream()), 4 * K + 8),
+        "loss_bwd": (lambda: lib.stf_loss_mc_bwd(_p(x), _p(t), N, H, W, K, None, -100, 1, _p(trm), _p(one), _p(dx),
+                                                 stream()),
+                     lambda: base.stf_loss_bwd(_p(x), _p(t), N, H, W, K, _p(trm), _p(one), _p(dx), stream()),
+                     8 * K + 8),
+        "head_fwd": (lambda: lib.stf_head_mc_fwd(_p(y), N, H, W, C, sc, sh, _p(w), _p(b), K, _p(x), stream()),
+                     lambda: base.stf_head_fwd(_p(y), N, H, W, C, sc, sh, _p(w), _p(b), K, _p(x), stream()),
+                     2 * C + 4 * K),
+        "head_bwd": (lambda: lib.stf_head_mc_bwd(*head_b, stream()), lambda: base.stf_head_bwd(*head_b, stream()),
+                     4 * C + 4 * K),
+    }
+
+    def timeit(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            rc = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        if rc != 0:
+            raise RuntimeError(f"launch failed: {rc}")
+        return e0.elapsed_time(e1) / args.reps * 1e3
+
+    sib = K <= 4
+    res = {"shape": [N, K, H, W], "channels": C, "reps": args.reps, "rounds": args.rounds,
+           "base_lib": args.base_lib or "in-tree"}
+    for name, (mc, old, bpp) in passes.items():      # loss_fwd first: it writes the terms loss_bwd reads
+        fns = [mc, old] if sib else [mc]
+        for fn in fns:
+            timeit(fn)
+        times = [[timeit(fn) for fn in fns] for _ in range(args.rounds)]
+        m = statistics.median(r[0] for r in times)
+        res[name] = {"mc_us": m, "mc_min_us": min(r[0] for r in times), "TBps": bpp * P / m * 1e-6}
+        if sib:
+            o = statistics.median(r[1] for r in times)
+            res[name].update({"sibling_us": o, "sibling_min_us": min(r[1] for r in times), "mc_over_sibling": m / o})
+    return res
+
+
+if args.classes:
+    for name in ("stf_head_fwd", "stf_head_bwd"):
+        getattr(base, name).restype, getattr(base, name).argtypes = _lib._SIGS[name]
+    lines = [json.dumps(many_class_passes(int(k))) for k in args.classes.split(",")]
+    print("\n".join(lines))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 
 g = torch.Generator(device=dev).manual_seed(0)
 logits = torch.randn(N, K, H, W, device=dev, generator=g) * 2
