@@ -503,6 +503,17 @@ int stf_bilinear_ac_bwd(const void* dy, int N, int h, int w, int C, int dy_cstri
  * c*out_cstride + y*W + x] (x [B][T+P][1][H][W]: out = &x[0][T], strides (T+P)*H*W and H*W). */
 int stf_bilinear_ac_bwd_tsum(const void* dy, int T, int B, int h, int w, int dy_cstride, int P, float* out,
                              int64_t out_bstride, int64_t out_cstride, int H, int W, stf_stream_t stream);
+/* Full-resolution logits (ABI v17, additive): F.interpolate(mode="bilinear", align_corners=False,
+ * size=(H, W)) of `planes` = N*K contiguous fp32 planes x [planes][h][w] (the NCHW logits of
+ * stf_head_fwd and the loss kernels) to y [planes][H][W], PyTorch's fp32 coordinate arithmetic
+ * (scale = in / out, src = scale (dst + 0.5) - 0.5 clamped at 0); and its backward, dx [planes][h][w]
+ * = the gather of dy [planes][H][W] (no atomics: each source pixel sums the outputs that read it in
+ * ascending (row, column) order, through the forward's own index function; dx is fully overwritten).
+ * Upsampling only; equal sizes copy bit for bit.  STF_EINVAL without a launch for a NULL pointer, a
+ * size < 1, H < h or W < w, or planes*H*W >= 2^31 (32-bit index math).  The coordinates are fp32, as
+ * PyTorch's: exact index ranges for axes up to 2^22.  The same fp32 kernels in both libraries. */
+int stf_resize_bilinear_fwd(const float* x, int planes, int h, int w, float* y, int H, int W, stf_stream_t stream);
+int stf_resize_bilinear_bwd(const float* dy, int planes, int H, int W, float* dx, int h, int w, stf_stream_t stream);
 /* dwcat [4C][2C] / dbias [4C] (interleaved) -> torch-layout dW_ih, dW_hh, db_ih, db_hh. */
 int stf_lstm_unpack_grad(const float* dwcat, const float* dbias, int C, float* dw_ih,
                          float* dw_hh, float* db_ih, float* db_hh, stf_stream_t stream);

@@ -9,7 +9,9 @@ from . import _lib  # noqa: F401
 from . import predict  # noqa: F401  (the module; its loop is stfunet.predict.predict)
 from .loss import criterion  # noqa: F401
 from .predict import image_metrics, overlay, predict_masks  # noqa: F401
+from .resize import upsample_logits  # noqa: F401
 from .stf_lstm_unet import STFLSTMUNet  # noqa: F401
 from .unet import UNet  # noqa: F401
 
-__all__ = ["STFLSTMUNet", "UNet", "criterion", "image_metrics", "overlay", "predict", "predict_masks"]
+__all__ = ["STFLSTMUNet", "UNet", "criterion", "image_metrics", "overlay", "predict", "predict_masks",
+           "upsample_logits"]

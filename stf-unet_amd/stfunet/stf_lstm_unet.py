@@ -3,7 +3,8 @@
 Surface kept: ``STFLSTMUNet(in_channels=1, num_classes=2, time_steps=8,
 use_pk_maps=False, pk_channels=3)``, ``forward(x, pk_maps=None) -> {"out": logits}``
 with x [B, T(+P), C, H, W] and logits at H/2 x W/2 (the reference's output size,
-SURVEY.md section 0), the module tree and therefore all ``state_dict`` keys:
+SURVEY.md section 0; the keyword-only addition ``output_size="input"`` resizes them to H x W
+as the program's last op, resize.py), the module tree and therefore all ``state_dict`` keys:
 ``conv1``/``bn1``/``layer1..4`` (torchvision ResNet-34 names, BasicBlock
 ``conv1,bn1,conv2,bn2,downsample``), ``pk_fusion1..4``, ``lstm1..4`` (nn.LSTM
 parameters), ``decoder4..2`` (``up``, ``fusion``, ``res_conv.conv_block``),
@@ -30,7 +31,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib, nhwc
+from . import _lib, nhwc, resize
 from ._lib import LstmEpi, call, stream
 from .nhwc import BNState, Feat, _p, new_feat, rows, zeros_feat
 from .program import Program, Saved as _S, conv_bn, conv_pair_backward, run_step
@@ -338,7 +339,7 @@ class STFProgram(Program):
 
     def plan_knobs(self):
         """Per-program scalars a recorded plan carries by value (part of its signature)."""
-        return tuple((lp.spin_limit, lp.max_wg) for lp in self.lstm_progs)
+        return tuple((lp.spin_limit, lp.max_wg) for lp in self.lstm_progs) + (self.m.output_size,)
 
     def check_device_errors(self, dev=None, block=False):
         """Raise if a cooperative LSTM launch of an earlier step timed out in its in-launch
@@ -573,6 +574,11 @@ class STFProgram(Program):
         logits = nhwc.empty((B, K, u1.H, u1.W), torch.float32, dev)
         S.ident = self._identity(fr_out.C, dev)
         S.head_w = nhwc.head_fwd(fr_out, S.ident, m.final, logits)
+        S.low = None
+        if m.output_size == "input":
+            # the last op: the head's half-resolution logits resized to the frames' H x W
+            S.low = (u1.H, u1.W)
+            logits = resize.resize_fwd(logits, (H, W))
         nhwc.flush_batches_tracked()
         return logits, (S if need_bwd else None)
 
@@ -583,6 +589,8 @@ class STFProgram(Program):
         dev = dlogits.device
         dlogits = dlogits.contiguous().float()
         B, T, P = S.B, S.T, S.P
+        if S.low is not None:                  # output_size="input": back through the resize first
+            dlogits = resize.resize_bwd(dlogits, S.low)
         # (no BatchNorm under the head here: its partial sums are not used)
         g, _, _ = nhwc.head_bwd(dlogits, S.fr.out, S.ident, S.head_w, gv(m.final.weight), gv(m.final.bias))
         self._done(m.final)
@@ -744,9 +752,16 @@ def _check_input_shape(shape, P):
 
 
 class STFLSTMUNet(nn.Module):
-    def __init__(self, in_channels=1, num_classes=2, time_steps=8, use_pk_maps=False, pk_channels=3):
+    def __init__(self, in_channels=1, num_classes=2, time_steps=8, use_pk_maps=False, pk_channels=3, *,
+                 output_size="half"):
         super().__init__()
         nhwc.check_num_classes(num_classes)
+        if output_size not in ("half", "input"):
+            raise ValueError(f"output_size={output_size!r}: 'half' (the reference's H/2 x W/2 logits) or 'input' "
+                             "(resized to the input frames' H x W)")
+        # "input": the program ends with a bilinear resize of the logits to H x W (resize.py) -- an
+        # addition, the reference has none; no parameters or buffers, the state_dict is unchanged
+        self.output_size = output_size
         self.time_steps = time_steps
         self.use_pk_maps = use_pk_maps
         self.pk_channels = pk_channels if use_pk_maps else 0
