@@ -213,7 +213,9 @@ int stf_bn_act(const void* y, int y_cstride, int N, int H, int W, int C, int gro
  * may be NULL), g = da masked by mask_mode (0 none, 1 ReLU recomputed from
  * y*scale+shift, 2 mask_src > 0: ReLU after a residual add), written to g_out
  * [M][C]; partial [groups][tiles][2][C] = (sum g, sum g*xhat), tiles from
- * stf_bn_bwd_tiles. */
+ * stf_bn_bwd_tiles.  C / 8 must divide 256.  Without dpool a statistics group
+ * must hold fewer than 2^31 16-byte units ((M / groups) * (C / 8); a 32 GiB
+ * tensor per group): STF_EINVAL otherwise, nothing is launched. */
 int stf_bn_bwd_tiles(int N, int H, int W, int C, int groups, int pooled);
 int stf_bn_bwd_reduce(const void* dz, int dz_cstride, const void* dpool, const void* y,
                       int y_cstride, int N, int H, int W, int C, int groups,
@@ -242,7 +244,9 @@ int stf_bn_groupsum_batch(const stf_bn_gsum_desc* descs, int count, stf_stream_t
  * recomputed from y: g' = g where y*scale+shift > 0 else 0 -- then g is the raw
  * incoming gradient (any channel stride) and stf_bn_bwd_reduce ran with
  * g_out = NULL.  Optional per-tile column sums of dy for the bias of the
- * producing conv (bias_partial [stf_bn_bwd_apply_tiles][C]) reduced into dbias. */
+ * producing conv (bias_partial [stf_bn_bwd_apply_tiles][C]) reduced into dbias.
+ * C / 8 must divide 256 and a statistics group must hold fewer than 2^31
+ * 16-byte units ((M / groups) * (C / 8)): STF_EINVAL otherwise, nothing is launched. */
 int stf_bn_bwd_apply_tiles(int64_t M, int C);
 int stf_bn_bwd_apply(const void* g, int g_cstride, const void* y, int y_cstride, int64_t M,
                      int C, int groups, const float* mask_scale, const float* mask_shift,

@@ -127,6 +127,101 @@ STF_DEV void bn_fin_bwd_out(float* base, int g, int c, int G, int C, long Mg, do
   }
 }
 
+// ------------------------------------------------------------------ per-unit arithmetic
+// A unit is 8 consecutive channels (chunk cg) of one pixel: one 16-B load per tensor.  Every
+// streaming kernel below finds its units its own way and calls these for what it does with one.
+
+// chunk cg of group g of two [G][C] vectors: (scale, shift), (mean, invstd), the residual's affine
+STF_DEV void load_pair(const float* a, const float* b, int g, int C, int cg, float (&va)[8], float (&vb)[8]) {
+  load8f(a + (size_t)g * C, cg * 8, va);
+  load8f(b + (size_t)g * C, cg * 8, vb);
+}
+// chunk cg of group g of coef [G][3][C]
+STF_DEV void load_coef(const float* coef, int g, int C, int cg, float (&A)[8], float (&B)[8], float (&Cc)[8]) {
+  load8f(coef + (size_t)g * 3 * C, cg * 8, A);
+  load8f(coef + (size_t)g * 3 * C + C, cg * 8, B);
+  load8f(coef + (size_t)g * 3 * C + 2 * C, cg * 8, Cc);
+}
+
+// forward: v = act(v*sc + sh [+ r | + r*rs + rh]), r = the unit at *rq; res_mode 0: none, 1: + r,
+// 2: + r's own affine
+STF_DEV void bn_affine8(float (&v)[8], const float (&sc)[8], const float (&sh)[8], int relu, int res_mode,
+                        const uint4* rq, const float (&rs)[8], const float (&rh)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) v[j] = v[j] * sc[j] + sh[j];
+  if (res_mode) {
+    float r[8];
+    unpack8(*rq, r);
+    if (res_mode == 2) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[j] = r[j] * rs[j] + rh[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] += r[j];
+  }
+  if (relu) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
+  }
+}
+
+// backward reduce: d becomes the masked gradient g' (mask 0: d, 1: d where y*sc + sh > 0, 2: d where
+// mk > 0; else 0), sg += g', sgx += g' * xhat
+STF_DEV void bn_acc8(int mask, float (&d)[8], const float (&y)[8], const float (&sc)[8], const float (&sh)[8],
+                     const float* mk, const float (&mu)[8], const float (&is)[8], float (&sg)[8], float (&sgx)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    bool keep = true;
+    if (mask == 1) keep = y[j] * sc[j] + sh[j] > 0.f;
+    else if (mask == 2) keep = mk[j] > 0.f;
+    const float gj = keep ? d[j] : 0.f;
+    d[j] = gj;
+    sg[j] += gj;
+    sgx[j] += gj * (y[j] - mu[j]) * is[j];
+  }
+}
+
+// backward apply: gv = dy = A*g' + B*y + C with g' = gv, or with mask the ReLU mask recomputed from y
+// (g' = gv where y*ms + mh > 0, else 0); sb += dy (the bias gradient of the producing conv)
+STF_DEV void bn_dy8(bool mask, float (&gv)[8], const float (&y)[8], const float (&ms)[8], const float (&mh)[8],
+                    const float (&A)[8], const float (&B)[8], const float (&Cc)[8], float (&sb)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float gj = (mask && !(y[j] * ms[j] + mh[j] > 0.f)) ? 0.f : gv[j];
+    gv[j] = A[j] * gj + B[j] * y[j] + Cc[j];
+    sb[j] += gv[j];
+  }
+}
+
+// Block fold of the threads' chunk sums into the block's row of out [rows][H][C], H = (RW - 1) / 8 sums
+// per channel (s0 | s1, or s0 alone): every thread parks its 8 H floats in red; channel c's total is
+// the sum over the threads that hold chunk c / 8 -- Q consecutive threads, repeating every `stride`
+// threads -- in ascending thread order.  Row = gy * gridDim.x + blockIdx.x: gy = the group (blockIdx.y)
+// in the group-major grids, 0 in the flat ones.
+template <int Q = 1, int NTH, int RW>
+STF_DEV void bn_block_fold(float (&red)[NTH][RW], const float (&s0)[8], const float (&s1)[8], int C, int stride,
+                           int gy, float* __restrict__ out) {
+  constexpr int H = (RW - 1) / 8;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    red[threadIdx.x][j] = s0[j];
+    if (H == 2) red[threadIdx.x][8 + j] = s1[j];
+  }
+  __syncthreads();
+  const size_t row = (size_t)gy * gridDim.x + blockIdx.x;
+  for (int c = threadIdx.x; c < C; c += NTH) {
+    const int gg = c >> 3, j = c & 7;
+    float a = 0.f, b = 0.f;
+    for (int t = Q * gg; t < NTH; t += stride)
+      for (int q = 0; q < Q; ++q) {
+        a += red[t + q][j];
+        if (H == 2) b += red[t + q][8 + j];
+      }
+    out[row * H * C + c] = a;
+    if (H == 2) out[row * H * C + C + c] = b;
+  }
+}
+
 // ------------------------------------------------------------------ apply
 // res_mode 0: none, 1: + res tensor, 2: + (res*rscale[g] + rshift[g])
 template <bool POOL>
@@ -142,9 +237,9 @@ __global__ void bn_act_kernel(const uint16_t* __restrict__ y, int ycs, long N, i
     const long pix = u / CG;
     if (!POOL) {
       const int g = (int)(pix / Mg);
+      // (inline, not bn_affine8: this kernel loads the residual and its affine only when asked)
       float sc[8], sh[8], v[8];
-      load8f(scale + (size_t)g * C, cg * 8, sc);
-      load8f(shift + (size_t)g * C, cg * 8, sh);
+      load_pair(scale, shift, g, C, cg, sc, sh);
       unpack8(*reinterpret_cast<const uint4*>(y + pix * ycs + cg * 8), v);
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = v[j] * sc[j] + sh[j];
@@ -153,8 +248,7 @@ __global__ void bn_act_kernel(const uint16_t* __restrict__ y, int ycs, long N, i
         unpack8(*reinterpret_cast<const uint4*>(res + pix * rcs + cg * 8), r);
         if (res_mode == 2) {
           float rs[8], rh[8];
-          load8f(rscale + (size_t)g * C, cg * 8, rs);
-          load8f(rshift + (size_t)g * C, cg * 8, rh);
+          load_pair(rscale, rshift, g, C, cg, rs, rh);
 #pragma unroll
           for (int j = 0; j < 8; ++j) r[j] = r[j] * rs[j] + rh[j];
         }
@@ -173,8 +267,7 @@ __global__ void bn_act_kernel(const uint16_t* __restrict__ y, int ycs, long N, i
       const int py = rem / Wp, px = rem - py * Wp;
       const int g = (int)(n * H * W / Mg);
       float sc[8], sh[8], mx[8];
-      load8f(scale + (size_t)g * C, cg * 8, sc);
-      load8f(shift + (size_t)g * C, cg * 8, sh);
+      load_pair(scale, shift, g, C, cg, sc, sh);
 #pragma unroll
       for (int d = 0; d < 4; ++d) {
         const long p = (n * H + 2 * py + (d >> 1)) * W + 2 * px + (d & 1);
@@ -195,105 +288,76 @@ __global__ void bn_act_kernel(const uint16_t* __restrict__ y, int ycs, long N, i
 }
 
 // ------------------------------------------------------------------ backward reduce
-// mask_mode 0: none, 1: relu(y*scale+shift) > 0, 2: mask_src > 0
-template <bool POOL>
-__global__ void bn_bwd_reduce_kernel(const uint16_t* __restrict__ dz, int dzcs, const uint16_t* __restrict__ dpool,
-                                     const uint16_t* __restrict__ y, int ycs, long N, int H, int W, int C, int G,
-                                     int tpg, const float* __restrict__ scale, const float* __restrict__ shift,
-                                     const float* __restrict__ mean, const float* __restrict__ invstd,
-                                     int mask_mode, const uint16_t* __restrict__ msrc, int mcs,
-                                     uint16_t* __restrict__ g_out, float* __restrict__ partial) {
+// The pooled reduce with one thread per 2x2 WINDOW and channel chunk, for the chunk counts the DPP
+// kernel below does not take (64 % (C / 8) != 0: C = 1024, 2048).  mask_mode 0: none,
+// 1: relu(y*scale+shift) > 0 (2 has no pooled form: the mask-source parameters are unused).
+__global__ void bn_bwd_reduce_win_kernel(const uint16_t* __restrict__ dz, int dzcs,
+                                         const uint16_t* __restrict__ dpool, const uint16_t* __restrict__ y, int ycs,
+                                         long N, int H, int W, int C, int G, int tpg,
+                                         const float* __restrict__ scale, const float* __restrict__ shift,
+                                         const float* __restrict__ mean, const float* __restrict__ invstd,
+                                         int mask_mode, const uint16_t* __restrict__ msrc, int mcs,
+                                         uint16_t* __restrict__ g_out, float* __restrict__ partial) {
   __shared__ float red[NT][17];
   const int CG = C / 8;
   const int g = blockIdx.x / tpg, tile = blockIdx.x - g * tpg;
-  const long Ng = N / G;
-  const long ppg = POOL ? Ng * (H / 2) * (W / 2) : Ng * H * W;            // pixels (or windows) per group
-  const long upg = ppg * CG;
+  const long wpg = (N / G) * (H / 2) * (W / 2);                           // windows per group
+  const long upg = wpg * CG;
   const long gt = (long)tile * NT + threadIdx.x;
   const int cg = (int)(gt % CG);                 // constant: tpg*NT is a multiple of CG
   float sc[8], sh[8], mu[8], is[8];
-  load8f(scale + (size_t)g * C, cg * 8, sc);
-  load8f(shift + (size_t)g * C, cg * 8, sh);
-  load8f(mean + (size_t)g * C, cg * 8, mu);
-  load8f(invstd + (size_t)g * C, cg * 8, is);
+  load_pair(scale, shift, g, C, cg, sc, sh);
+  load_pair(mean, invstd, g, C, cg, mu, is);
   float sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sgx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   for (long u = gt; u < upg; u += (long)tpg * NT) {
-    const long pix = u / CG + g * ppg;
-    if (!POOL) {
-      float v[8], d[8];
-      unpack8(*reinterpret_cast<const uint4*>(y + pix * ycs + cg * 8), v);
-      unpack8(*reinterpret_cast<const uint4*>(dz + pix * dzcs + cg * 8), d);
-      float mk[8];
-      if (mask_mode == 2) unpack8(*reinterpret_cast<const uint4*>(msrc + pix * mcs + cg * 8), mk);
+    const long pix = u / CG + g * wpg;
+    const int Wp = W / 2, Hp = H / 2;
+    const long n = pix / ((long)Hp * Wp);
+    const int rem = (int)(pix - n * Hp * Wp);
+    const int py = rem / Wp, px = rem - py * Wp;
+    float v[4][8], a[4][8];
+    long p[4];
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      p[d] = (n * H + 2 * py + (d >> 1)) * W + 2 * px + (d & 1);
+      unpack8(*reinterpret_cast<const uint4*>(y + p[d] * ycs + cg * 8), v[d]);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        bool keep = true;
-        if (mask_mode == 1) keep = v[j] * sc[j] + sh[j] > 0.f;
-        else if (mask_mode == 2) keep = mk[j] > 0.f;
-        const float gj = keep ? d[j] : 0.f;
-        d[j] = gj;
-        sg[j] += gj;
-        sgx[j] += gj * (v[j] - mu[j]) * is[j];
-      }
-      if (g_out) *reinterpret_cast<uint4*>(g_out + pix * C + cg * 8) = pack8(d);
-    } else {
-      const int Wp = W / 2, Hp = H / 2;
-      const long n = pix / ((long)Hp * Wp);
-      const int rem = (int)(pix - n * Hp * Wp);
-      const int py = rem / Wp, px = rem - py * Wp;
-      float v[4][8], a[4][8];
-      long p[4];
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        p[d] = (n * H + 2 * py + (d >> 1)) * W + 2 * px + (d & 1);
-        unpack8(*reinterpret_cast<const uint4*>(y + p[d] * ycs + cg * 8), v[d]);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float t = v[d][j] * sc[j] + sh[j];
-          if (mask_mode == 1) t = fmaxf(t, 0.f);
-          a[d][j] = round_e(t);
-        }
-      }
-      float dp[8];
-      unpack8(*reinterpret_cast<const uint4*>(dpool + pix * C + cg * 8), dp);
-      int am[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        am[j] = 0;
-        float best = a[0][j];
-#pragma unroll
-        for (int d = 1; d < 4; ++d) if (a[d][j] > best) { best = a[d][j]; am[j] = d; }
-      }
-#pragma unroll
-      for (int d = 0; d < 4; ++d) {
-        float gd[8];
-        if (dz) unpack8(*reinterpret_cast<const uint4*>(dz + p[d] * dzcs + cg * 8), gd);
-        else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) gd[j] = 0.f;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float t = gd[j] + (am[j] == d ? dp[j] : 0.f);
-          if (mask_mode == 1 && !(v[d][j] * sc[j] + sh[j] > 0.f)) t = 0.f;
-          gd[j] = t;
-          sg[j] += t;
-          sgx[j] += t * (v[d][j] - mu[j]) * is[j];
-        }
-        *reinterpret_cast<uint4*>(g_out + p[d] * C + cg * 8) = pack8(gd);
+        float t = v[d][j] * sc[j] + sh[j];
+        if (mask_mode == 1) t = fmaxf(t, 0.f);
+        a[d][j] = round_e(t);
       }
     }
-  }
+    float dp[8];
+    unpack8(*reinterpret_cast<const uint4*>(dpool + pix * C + cg * 8), dp);
+    int am[8];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) { red[threadIdx.x][j] = sg[j]; red[threadIdx.x][8 + j] = sgx[j]; }
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += NT) {
-    const int gg = c / 8, j = c - gg * 8;
-    float a = 0.f, b = 0.f;
-    for (int t = gg; t < NT; t += CG) { a += red[t][j]; b += red[t][8 + j]; }
-    partial[(size_t)blockIdx.x * 2 * C + c] = a;
-    partial[(size_t)blockIdx.x * 2 * C + C + c] = b;
+    for (int j = 0; j < 8; ++j) {
+      am[j] = 0;
+      float best = a[0][j];
+#pragma unroll
+      for (int d = 1; d < 4; ++d) if (a[d][j] > best) { best = a[d][j]; am[j] = d; }
+    }
+#pragma unroll
+    for (int d = 0; d < 4; ++d) {
+      float gd[8];
+      if (dz) unpack8(*reinterpret_cast<const uint4*>(dz + p[d] * dzcs + cg * 8), gd);
+      else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) gd[j] = 0.f;
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {           // (inline, not bn_acc8: the routed dpool joins in the same pass)
+        float t = gd[j] + (am[j] == d ? dp[j] : 0.f);
+        if (mask_mode == 1 && !(v[d][j] * sc[j] + sh[j] > 0.f)) t = 0.f;
+        gd[j] = t;
+        sg[j] += t;
+        sgx[j] += t * (v[d][j] - mu[j]) * is[j];
+      }
+      *reinterpret_cast<uint4*>(g_out + p[d] * C + cg * 8) = pack8(gd);
+    }
   }
+  bn_block_fold(red, sg, sgx, C, CG, 0, partial);
 }
 
 // The pooled reduce with one lane per PIXEL (the 4 pixels of a 2x2 window in the 4
@@ -328,10 +392,8 @@ __global__ __launch_bounds__(PNT) void bn_bwd_reduce_pool_kernel(const uint16_t*
   const int d = (int)(gt & 3);
   const int cg = (int)((gt >> 2) % CG);
   float sc[8], sh[8], mu[8], is[8];
-  load8f(scale + (size_t)g * C, cg * 8, sc);
-  load8f(shift + (size_t)g * C, cg * 8, sh);
-  load8f(mean + (size_t)g * C, cg * 8, mu);
-  load8f(invstd + (size_t)g * C, cg * 8, is);
+  load_pair(scale, shift, g, C, cg, sc, sh);
+  load_pair(mean, invstd, g, C, cg, mu, is);
   const bool relu = mask_mode == 1;
   float sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sgx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // 32-bit index math (a 64-bit division is a long emulated sequence per unit): every
@@ -365,7 +427,7 @@ __global__ __launch_bounds__(PNT) void bn_bwd_reduce_pool_kernel(const uint16_t*
       float c = a == m ? (float)d : 4.f;                       // first maximum of the window
       c = fminf(c, quad_xor1(c));
       c = fminf(c, quad_xor2(c));
-      float gj = gd[j] + (c == (float)d ? dp[j] : 0.f);
+      float gj = gd[j] + (c == (float)d ? dp[j] : 0.f);    // (inline, not bn_acc8: t is already at hand)
       if (relu && !(t > 0.f)) gj = 0.f;
       gd[j] = gj;
       sg[j] += gj;
@@ -391,17 +453,7 @@ __global__ __launch_bounds__(PNT) void bn_bwd_reduce_pool_kernel(const uint16_t*
     unit(p0, w0, y0, z0, q0);
     if (two) unit(p1, w1, y1, z1, q1);
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { red[threadIdx.x][j] = sg[j]; red[threadIdx.x][8 + j] = sgx[j]; }
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += PNT) {
-    const int gg = c / 8, j = c - gg * 8;
-    float a = 0.f, b = 0.f;
-    for (int t = 4 * gg; t < PNT; t += 4 * CG)               // threads holding chunk gg: (t >> 2) % CG == gg
-      for (int q = 0; q < 4; ++q) { a += red[t + q][j]; b += red[t + q][8 + j]; }
-    partial[(size_t)blockIdx.x * 2 * C + c] = a;
-    partial[(size_t)blockIdx.x * 2 * C + C + c] = b;
-  }
+  bn_block_fold<4>(red, sg, sgx, C, 4 * CG, 0, partial);   // threads holding chunk gg: (t >> 2) % CG == gg
 }
 
 // partial: [G][T][2][C] (first S rows per group folded).  coef: [G][3][C].
@@ -473,60 +525,10 @@ __global__ void bn_bwd_groupsum_kernel(const float* __restrict__ partial, int T,
   if (dbeta) dbeta[c] = (float)db;
 }
 
-// dy = A*g' + B*y + C, g' = g (already masked) or, with mscale != NULL, the ReLU
-// mask recomputed from y: g' = (y*mscale+mshift > 0) ? g : 0 (saves the masked copy)
-__global__ void bn_bwd_apply_kernel(const uint16_t* g, int gcs, const uint16_t* __restrict__ y, int ycs, long M,
-                                    int C, long Mg, const float* __restrict__ coef, const float* __restrict__ mscale,
-                                    const float* __restrict__ mshift, uint16_t* dy, int dycs,
-                                    float* __restrict__ bias_partial) {
-  __shared__ float red[NT][9];
-  const int CG = C / 8;
-  const long units = M * CG;
-  const long gt = blockIdx.x * (long)NT + threadIdx.x;
-  const int cg = (int)(gt % CG);
-  float sb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  int cur_g = -1;
-  float A[8], B[8], Cc[8], ms[8], mh[8];
-  for (long u = gt; u < units; u += (long)gridDim.x * NT) {
-    const long pix = u / CG;
-    const int grp = (int)(pix / Mg);
-    if (grp != cur_g) {
-      cur_g = grp;
-      load8f(coef + (size_t)grp * 3 * C, cg * 8, A);
-      load8f(coef + (size_t)grp * 3 * C + C, cg * 8, B);
-      load8f(coef + (size_t)grp * 3 * C + 2 * C, cg * 8, Cc);
-      if (mscale) {
-        load8f(mscale + (size_t)grp * C, cg * 8, ms);
-        load8f(mshift + (size_t)grp * C, cg * 8, mh);
-      }
-    }
-    float gv[8], yv[8];
-    unpack8(*reinterpret_cast<const uint4*>(g + pix * gcs + cg * 8), gv);
-    unpack8(*reinterpret_cast<const uint4*>(y + pix * ycs + cg * 8), yv);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float gj = (mscale && !(yv[j] * ms[j] + mh[j] > 0.f)) ? 0.f : gv[j];
-      gv[j] = A[j] * gj + B[j] * yv[j] + Cc[j];
-      sb[j] += gv[j];
-    }
-    *reinterpret_cast<uint4*>(dy + pix * dycs + cg * 8) = pack8(gv);
-  }
-  if (!bias_partial) return;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) red[threadIdx.x][j] = sb[j];
-  __syncthreads();
-  for (int c = threadIdx.x; c < C; c += NT) {
-    const int gg = c / 8, j = c - gg * 8;
-    float a = 0.f;
-    for (int t = gg; t < NT; t += CG) a += red[t][j];
-    bias_partial[(size_t)blockIdx.x * C + c] = a;
-  }
-}
-
 // ------------------------------------------------------------------ group-major streaming passes
-// The same three element-wise passes with the grid split by statistics group (blockIdx.y = g):
+// The three element-wise passes with the grid split by statistics group (blockIdx.y = g):
 // a thread's channel chunk and its group's affine / coefficient vectors are fixed, so the loop
-// carries no per-unit division (the kernels above divide 64-bit unit and pixel indices by C/8
+// carries no per-unit division (bn_act_kernel divides 64-bit unit and pixel indices by C/8
 // and by the group size for every 16-B unit), and every thread issues the loads of UPT units
 // (a block covers UPT x 256 consecutive units per iteration)
 // before it uses any (UPT x 2-3 16-B loads in flight per lane: the STF encoder's 8-67 MB tensors
@@ -546,12 +548,8 @@ __global__ __launch_bounds__(NT) void bn_act_g_kernel(const uint16_t* __restrict
   const int u0 = blockIdx.x * NT * UPT + threadIdx.x;
   const int cg = threadIdx.x & ((1 << cgs) - 1);
   float sc[8], sh[8], rs[8], rh[8];
-  load8f(scale + (size_t)g * C, cg * 8, sc);
-  load8f(shift + (size_t)g * C, cg * 8, sh);
-  if (RES && res_mode == 2) {
-    load8f(rscale + (size_t)g * C, cg * 8, rs);
-    load8f(rshift + (size_t)g * C, cg * 8, rh);
-  }
+  load_pair(scale, shift, g, C, cg, sc, sh);
+  if (RES && res_mode == 2) load_pair(rscale, rshift, g, C, cg, rs, rh);
   const size_t p0 = (size_t)g * Mg;
   for (int u = u0; u < upg; u += S) {
     uint4 yv[UPT], rv[UPT];
@@ -570,28 +568,13 @@ __global__ __launch_bounds__(NT) void bn_act_g_kernel(const uint16_t* __restrict
       if (uk >= upg) break;
       float v[8];
       unpack8(yv[k], v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = v[j] * sc[j] + sh[j];
-      if (RES) {
-        float r[8];
-        unpack8(rv[k], r);
-        if (res_mode == 2) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) r[j] = r[j] * rs[j] + rh[j];
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] += r[j];
-      }
-      if (relu) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j], 0.f);
-      }
+      bn_affine8(v, sc, sh, relu, RES ? (res_mode == 2 ? 2 : 1) : 0, &rv[k], rs, rh);
       *reinterpret_cast<uint4*>(out + (p0 + (uk >> cgs)) * ocs + cg * 8) = pack8(v);
     }
   }
 }
 
-// mask_mode 0: none, 1: relu(y*scale+shift) > 0, 2: mask_src > 0; same sums as bn_bwd_reduce_kernel
+// MASK 0: none, 1: relu(y*scale+shift) > 0, 2: mask_src > 0
 template <int MASK>
 __global__ __launch_bounds__(NT) void bn_bwd_reduce_g_kernel(const uint16_t* __restrict__ dz, int dzcs,
                                                              const uint16_t* __restrict__ y, int ycs, int Mg,
@@ -607,12 +590,8 @@ __global__ __launch_bounds__(NT) void bn_bwd_reduce_g_kernel(const uint16_t* __r
   const int u0 = blockIdx.x * NT * UPT + threadIdx.x;
   const int cg = threadIdx.x & (CG - 1);
   float sc[8], sh[8], mu[8], is[8];
-  if (MASK == 1) {
-    load8f(scale + (size_t)g * C, cg * 8, sc);
-    load8f(shift + (size_t)g * C, cg * 8, sh);
-  }
-  load8f(mean + (size_t)g * C, cg * 8, mu);
-  load8f(invstd + (size_t)g * C, cg * 8, is);
+  if (MASK == 1) load_pair(scale, shift, g, C, cg, sc, sh);
+  load_pair(mean, invstd, g, C, cg, mu, is);
   float sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sgx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const size_t p0 = (size_t)g * Mg;
   for (int u = u0; u < upg; u += S) {
@@ -635,33 +614,15 @@ __global__ __launch_bounds__(NT) void bn_bwd_reduce_g_kernel(const uint16_t* __r
       unpack8(yv[k], v);
       unpack8(zv[k], d);
       if (MASK == 2) unpack8(mv[k], mk);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        bool keep = true;
-        if (MASK == 1) keep = v[j] * sc[j] + sh[j] > 0.f;
-        else if (MASK == 2) keep = mk[j] > 0.f;
-        const float gj = keep ? d[j] : 0.f;
-        d[j] = gj;
-        sg[j] += gj;
-        sgx[j] += gj * (v[j] - mu[j]) * is[j];
-      }
+      bn_acc8(MASK, d, v, sc, sh, mk, mu, is, sg, sgx);
       if (g_out) *reinterpret_cast<uint4*>(g_out + (p0 + (uk >> cgs)) * C + cg * 8) = pack8(d);
     }
   }
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { red[threadIdx.x][j] = sg[j]; red[threadIdx.x][8 + j] = sgx[j]; }
-  __syncthreads();
-  const size_t row = (size_t)g * gridDim.x + blockIdx.x;
-  for (int c = threadIdx.x; c < C; c += NT) {
-    const int gg = c >> 3, j = c & 7;
-    float a = 0.f, b = 0.f;
-    for (int t = gg; t < NT; t += CG) { a += red[t][j]; b += red[t][8 + j]; }
-    partial[row * 2 * C + c] = a;
-    partial[row * 2 * C + C + c] = b;
-  }
+  bn_block_fold(red, sg, sgx, C, CG, g, partial);
 }
 
-// dy = A*g' + B*y + C (as bn_bwd_apply_kernel); bias_partial rows = g * gridDim.x + blockIdx.x
+// dy = A*g' + B*y + C, g' = g (already masked) or, with MASK, the ReLU mask recomputed from y:
+// g' = (y*mscale+mshift > 0) ? g : 0 (saves the masked copy); bias_partial rows = g * gridDim.x + blockIdx.x
 template <bool MASK>
 __global__ __launch_bounds__(NT) void bn_bwd_apply_g_kernel(const uint16_t* g_in, int gcs,
                                                             const uint16_t* __restrict__ y, int ycs, int Mg, int cgs,
@@ -674,13 +635,8 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_g_kernel(const uint16_t* g_in
   const int u0 = blockIdx.x * NT * UPT + threadIdx.x;
   const int cg = threadIdx.x & (CG - 1);
   float A[8], B[8], Cc[8], ms[8], mh[8];
-  load8f(coef + (size_t)g * 3 * C, cg * 8, A);
-  load8f(coef + (size_t)g * 3 * C + C, cg * 8, B);
-  load8f(coef + (size_t)g * 3 * C + 2 * C, cg * 8, Cc);
-  if (MASK) {
-    load8f(mscale + (size_t)g * C, cg * 8, ms);
-    load8f(mshift + (size_t)g * C, cg * 8, mh);
-  }
+  load_coef(coef, g, C, cg, A, B, Cc);
+  if (MASK) load_pair(mscale, mshift, g, C, cg, ms, mh);
   float sb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   const size_t p0 = (size_t)g * Mg;
   for (int u = u0; u < upg; u += S) {
@@ -701,26 +657,12 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_g_kernel(const uint16_t* g_in
       float gv[8], yv[8];
       unpack8(gq[k], gv);
       unpack8(yq[k], yv);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float gj = (MASK && !(yv[j] * ms[j] + mh[j] > 0.f)) ? 0.f : gv[j];
-        gv[j] = A[j] * gj + B[j] * yv[j] + Cc[j];
-        sb[j] += gv[j];
-      }
+      bn_dy8(MASK, gv, yv, ms, mh, A, B, Cc, sb);
       *reinterpret_cast<uint4*>(dy + (p0 + (uk >> cgs)) * dycs + cg * 8) = pack8(gv);
     }
   }
   if (!bias_partial) return;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) red[threadIdx.x][j] = sb[j];
-  __syncthreads();
-  const size_t row = (size_t)g * gridDim.x + blockIdx.x;
-  for (int c = threadIdx.x; c < C; c += NT) {
-    const int gg = c >> 3, j = c & 7;
-    float a = 0.f;
-    for (int t = gg; t < NT; t += CG) a += red[t][j];
-    bias_partial[row * C + c] = a;
-  }
+  bn_block_fold(red, sb, sb, C, CG, g, bias_partial);
 }
 
 // ------------------------------------------------------------------ stem: BN backward through MaxPool(3,2,1)
@@ -751,16 +693,9 @@ __global__ __launch_bounds__(NT) void bn_bwd_pool3_kernel(const uint8_t* __restr
   const int u0 = blockIdx.x * NT + threadIdx.x;
   const int cg = threadIdx.x & (CG - 1);
   float sc[8], sh[8], mu[8], is[8], A[8], B[8], Cc[8];
-  load8f(scale + (size_t)g * C, cg * 8, sc);
-  load8f(shift + (size_t)g * C, cg * 8, sh);
-  if (APPLY) {
-    load8f(coef + (size_t)g * 3 * C, cg * 8, A);
-    load8f(coef + (size_t)g * 3 * C + C, cg * 8, B);
-    load8f(coef + (size_t)g * 3 * C + 2 * C, cg * 8, Cc);
-  } else {
-    load8f(mean + (size_t)g * C, cg * 8, mu);
-    load8f(invstd + (size_t)g * C, cg * 8, is);
-  }
+  load_pair(scale, shift, g, C, cg, sc, sh);
+  if (APPLY) load_coef(coef, g, C, cg, A, B, Cc);
+  else load_pair(mean, invstd, g, C, cg, mu, is);
   float sg[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sgx[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   // U units per iteration, all their loads issued before any use (the reduce runs <= 1024
   // blocks -- the finalize's row budget -- so it needs the memory-level parallelism per thread)
@@ -830,43 +765,25 @@ __global__ __launch_bounds__(NT) void bn_bwd_pool3_kernel(const uint8_t* __restr
             }
           }
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float gr = round_e(gq[j]);
-            const float gj = (v[j] * sc[j] + sh[j] > 0.f) ? gr : 0.f;
-            if (APPLY) gq[j] = A[j] * gj + B[j] * v[j] + Cc[j];
-            else {
-              sg[j] += gj;
-              sgx[j] += gj * (v[j] - mu[j]) * is[j];
-            }
-          }
-          if (APPLY)
+          for (int j = 0; j < 8; ++j) gq[j] = round_e(gq[j]);
+          if (APPLY) {
+            bn_dy8(true, gq, v, sc, sh, A, B, Cc, sg);                  // (sg: no bias sum here, unused)
             *reinterpret_cast<uint4*>(dy + (((size_t)n * H + iy) * W + ix) * C + cg * 8) = pack8(gq);
+          } else {
+            bn_acc8(1, gq, v, sc, sh, nullptr, mu, is, sg, sgx);
+          }
         }
     }
   }
-  if (APPLY) return;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { red[threadIdx.x][j] = sg[j]; red[threadIdx.x][8 + j] = sgx[j]; }
-  __syncthreads();
-  const size_t row = (size_t)g * gridDim.x + blockIdx.x;
-  for (int c = threadIdx.x; c < C; c += NT) {
-    const int gg = c >> 3, j = c & 7;
-    float a = 0.f, b = 0.f;
-    for (int t = gg; t < NT; t += CG) { a += red[t][j]; b += red[t][8 + j]; }
-    partial[row * 2 * C + c] = a;
-    partial[row * 2 * C + C + c] = b;
-  }
+  if constexpr (!APPLY) bn_block_fold(red, sg, sgx, C, CG, g, partial);
 }
 
 }  // namespace
 
-// the group-major kernels (STF_BN_G=0: the per-unit-division kernels, A/B); usable when C / 8 is
-// a power of two dividing the block and a group's units fit 32-bit indices
-static bool bn_g_ok(long Mg, int C) {
-  static const bool on = stf::ab_switch("STF_BN_G", 1) != 0;
-  const int CG = C / 8;
-  return on && C % 8 == 0 && CG > 0 && (CG & (CG - 1)) == 0 && NT % CG == 0 && Mg * CG < (1L << 31);
-}
+// the backward kernels keep a thread's channel chunk fixed: C / 8 divides the block (so it is a power of two)
+static bool cg_ok(int C) { return C >= 8 && C % 8 == 0 && NT % (C / 8) == 0; }
+// the group-major kernels: that, and a group's units fit 32-bit indices
+static bool bn_g_ok(long Mg, int C) { return cg_ok(C) && Mg * (C / 8) < (1L << 31); }
 static int log2i(int v) { return 31 - __builtin_clz(v); }
 // blocks per group: about UPT units per thread, at least one, the whole grid <= cap blocks
 static int g_tiles(long upg, int groups, long cap) {
@@ -886,8 +803,6 @@ __global__ __launch_bounds__(stf::FOLD_NT) void stf_tile_sum_kernel(const float*
   const double s = stf::fold16_finish(stf::fold16_partial(partial, tiles, C, c, cok), red);
   if (cok && (threadIdx.x >> 4) == 0) out[c] = (float)s;
 }
-
-static bool cg_ok(int C) { return C % 8 == 0 && NT % (C / 8) == 0; }
 
 extern "C" int stf_bn_finalize(float* stats, int tiles, int groups, int C, int64_t M, const float* gamma,
                                const float* beta, float momentum, float eps, float* running_mean,
@@ -926,25 +841,22 @@ extern "C" int stf_bn_act(const void* y, int y_cstride, int N, int H, int W, int
   if (!pooled && bn_g_ok(Mg, C)) {
     const int cgs = log2i(C / 8);
     const dim3 grid(g_tiles(Mg * (C / 8), groups, 8192), groups);
-    if (res)
-      hipLaunchKernelGGL((bn_act_g_kernel<true>), grid, dim3(NT), 0, s, (const uint16_t*)y, y_cstride,
-                         (int)Mg, cgs, scale, shift, relu, res_mode, (const uint16_t*)res, res_cstride, res_scale,
-                         res_shift, (uint16_t*)out, out_cstride);
-    else
-      hipLaunchKernelGGL((bn_act_g_kernel<false>), grid, dim3(NT), 0, s, (const uint16_t*)y, y_cstride,
-                         (int)Mg, cgs, scale, shift, relu, 0, (const uint16_t*)nullptr, 0, (const float*)nullptr,
-                         (const float*)nullptr, (uint16_t*)out, out_cstride);
+#define STF_AG(RES) hipLaunchKernelGGL(bn_act_g_kernel<RES>, grid, dim3(NT), 0, s, (const uint16_t*)y, y_cstride,   \
+                                       (int)Mg, cgs, scale, shift, relu, res_mode, (const uint16_t*)res, res_cstride, \
+                                       res_scale, res_shift, (uint16_t*)out, out_cstride)
+    if (res) STF_AG(true);
+    else STF_AG(false);
+#undef STF_AG
     STF_CHECK_LAUNCH();
     return 0;
   }
-  if (pooled)
-    hipLaunchKernelGGL((bn_act_kernel<true>), dim3(blocks), dim3(NT), 0, s, (const uint16_t*)y, y_cstride,
-                       (long)N, H, W, C, Mg, scale, shift, relu, 0, (const uint16_t*)nullptr, 0,
-                       (const float*)nullptr, (const float*)nullptr, (uint16_t*)out, out_cstride, (uint16_t*)pooled);
-  else
-    hipLaunchKernelGGL((bn_act_kernel<false>), dim3(blocks), dim3(NT), 0, s, (const uint16_t*)y, y_cstride,
-                       (long)N, H, W, C, Mg, scale, shift, relu, res_mode, (const uint16_t*)res, res_cstride,
-                       res_scale, res_shift, (uint16_t*)out, out_cstride, (uint16_t*)nullptr);
+  // (res and pooled exclude each other: checked above)
+#define STF_A(POOL) hipLaunchKernelGGL(bn_act_kernel<POOL>, dim3(blocks), dim3(NT), 0, s, (const uint16_t*)y, y_cstride, \
+                                       (long)N, H, W, C, Mg, scale, shift, relu, res_mode, (const uint16_t*)res,         \
+                                       res_cstride, res_scale, res_shift, (uint16_t*)out, out_cstride, (uint16_t*)pooled)
+  if (pooled) STF_A(true);
+  else STF_A(false);
+#undef STF_A
   STF_CHECK_LAUNCH();
   return 0;
 }
@@ -964,11 +876,11 @@ extern "C" int stf_bn_bwd_reduce(const void* dz, int dz_cstride, const void* dpo
   if (!g_out && dpool) return STF_EINVAL;            // the pooled routing must be materialized
   if (dpool && (((H | W) & 1) || mask_mode == 2)) return STF_EINVAL;
   if (mask_mode == 2 && (!mask_src || mask_cstride % 8)) return STF_EINVAL;
+  const long Mgp = (long)N * H * W / groups;
+  if (!dpool && !bn_g_ok(Mgp, C)) return STF_EINVAL;   // >= 2^31 units in a group
   const int tpg = stf_bn_bwd_tiles(N, H, W, C, groups, dpool != nullptr);
   hipStream_t s = (hipStream_t)stream;
-  const dim3 grid(tpg * groups);
-  const long Mgp = (long)N * H * W / groups;
-  if (!dpool && bn_g_ok(Mgp, C)) {
+  if (!dpool) {
     const dim3 g2(tpg, groups);
     const int cgs = log2i(C / 8);
 #define STF_RG(MM) hipLaunchKernelGGL(bn_bwd_reduce_g_kernel<MM>, g2, dim3(NT), 0, s, (const uint16_t*)dz, dz_cstride, \
@@ -981,20 +893,16 @@ extern "C" int stf_bn_bwd_reduce(const void* dz, int dz_cstride, const void* dpo
     STF_CHECK_LAUNCH();
     return 0;
   }
-  if (dpool && 64 % (C / 8) == 0 && mask_mode != 2 && (long)N * H * W < (1L << 31))
+  const dim3 grid(tpg * groups);
+  if (64 % (C / 8) == 0 && (long)N * H * W < (1L << 31))     // (mask_mode 2 has no pooled form: refused above)
     hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel, grid, dim3(PNT), 0, s, (const uint16_t*)dz, dz_cstride,
                        (const uint16_t*)dpool, (const uint16_t*)y, y_cstride, (long)N, H, W, C, groups, tpg, scale,
                        shift, mean, invstd, mask_mode, (uint16_t*)g_out, partial);
-  else if (dpool)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<true>, grid, dim3(NT), 0, s, (const uint16_t*)dz, dz_cstride,
+  else
+    hipLaunchKernelGGL(bn_bwd_reduce_win_kernel, grid, dim3(NT), 0, s, (const uint16_t*)dz, dz_cstride,
                        (const uint16_t*)dpool, (const uint16_t*)y, y_cstride, (long)N, H, W, C, groups, tpg, scale,
                        shift, mean, invstd, mask_mode, (const uint16_t*)mask_src, mask_cstride, (uint16_t*)g_out,
                        partial);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<false>, grid, dim3(NT), 0, s, (const uint16_t*)dz, dz_cstride,
-                       (const uint16_t*)nullptr, (const uint16_t*)y, y_cstride, (long)N, H, W, C, groups, tpg,
-                       scale, shift, mean, invstd, mask_mode, (const uint16_t*)mask_src, mask_cstride,
-                       (uint16_t*)g_out, partial);
   STF_CHECK_LAUNCH();
   return 0;
 }
@@ -1056,31 +964,22 @@ extern "C" int stf_bn_bwd_apply(const void* g, int g_cstride, const void* y, int
                                 void* dy, int dy_cstride, float* bias_partial, float* dbias, stf_stream_t stream) {
   if (!cg_ok(C) || y_cstride % 8 || dy_cstride % 8 || g_cstride % 8 || groups < 1 || M % groups) return STF_EINVAL;
   if ((mask_scale == nullptr) != (mask_shift == nullptr)) return STF_EINVAL;
-  int tiles = stf_bn_bwd_apply_tiles(M, C);
-  hipStream_t s = (hipStream_t)stream;
   const long Mg = M / groups;
-  if (bn_g_ok(Mg, C)) {
-    // bias_partial rows: groups x tpg <= stf_bn_bwd_apply_tiles (the caller's allocation)
-    const int tpg = g_tiles(Mg * (C / 8), groups, bias_partial ? tiles : 8192);
-    const dim3 grid(tpg, groups);
-    const int cgs = log2i(C / 8);
-    if (mask_scale)
-      hipLaunchKernelGGL((bn_bwd_apply_g_kernel<true>), grid, dim3(NT), 0, s, (const uint16_t*)g, g_cstride,
-                         (const uint16_t*)y, y_cstride, (int)Mg, cgs, coef, mask_scale, mask_shift, (uint16_t*)dy,
-                         dy_cstride, bias_partial);
-    else
-      hipLaunchKernelGGL((bn_bwd_apply_g_kernel<false>), grid, dim3(NT), 0, s, (const uint16_t*)g, g_cstride,
-                         (const uint16_t*)y, y_cstride, (int)Mg, cgs, coef, mask_scale, mask_shift, (uint16_t*)dy,
-                         dy_cstride, bias_partial);
-    tiles = tpg * groups;
-  } else {
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(tiles), dim3(NT), 0, s, (const uint16_t*)g, g_cstride,
-                       (const uint16_t*)y, y_cstride, (long)M, C, (long)(M / groups), coef, mask_scale, mask_shift,
-                       (uint16_t*)dy, dy_cstride, bias_partial);
-  }
+  if (!bn_g_ok(Mg, C)) return STF_EINVAL;              // >= 2^31 units in a group
+  hipStream_t s = (hipStream_t)stream;
+  // bias_partial rows: groups x tpg <= stf_bn_bwd_apply_tiles (the caller's allocation)
+  const int tpg = g_tiles(Mg * (C / 8), groups, bias_partial ? stf_bn_bwd_apply_tiles(M, C) : 8192);
+  const dim3 grid(tpg, groups);
+  const int cgs = log2i(C / 8);
+#define STF_AP(MM) hipLaunchKernelGGL(bn_bwd_apply_g_kernel<MM>, grid, dim3(NT), 0, s, (const uint16_t*)g, g_cstride, \
+                                      (const uint16_t*)y, y_cstride, (int)Mg, cgs, coef, mask_scale, mask_shift,     \
+                                      (uint16_t*)dy, dy_cstride, bias_partial)
+  if (mask_scale) STF_AP(true);
+  else STF_AP(false);
+#undef STF_AP
   STF_CHECK_LAUNCH();
   if (bias_partial && dbias) {
-    const int S = stf::colsum_stage1(bias_partial, tiles, C, s, 1, stf::FOLD16_ROWS);
+    const int S = stf::colsum_stage1(bias_partial, tpg * groups, C, s, 1, stf::FOLD16_ROWS);
     hipLaunchKernelGGL(stf_tile_sum_kernel, dim3((C + 15) / 16), dim3(stf::FOLD_NT), 0, s, bias_partial, S, C, dbias);
     STF_CHECK_LAUNCH();
   }

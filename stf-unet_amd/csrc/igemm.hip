@@ -2450,7 +2450,7 @@ struct Route {
 //     bias, statistics or BN reduce) skip the tap-less classes.
 // 12. plain gathers on the upper-case DMA tiles that would leave the chip under-filled (small M: STF
 //     layer4 at 8 x 8, LSTM backward GEMMs) split K: slices until ~256 workgroups, each keeping >= 8
-//     K steps, at most 8.  STF_SPLITK=0 disables it.
+//     K steps, at most 8.
 Route route_of(const stf_igemm_args* a, bool with_stats) {
   const stf_conv_geom& c = a->g;
   Route r;
@@ -2537,8 +2537,7 @@ Route route_of(const stf_igemm_args* a, bool with_stats) {
     }
     r.tpg = (int)blocks;
   }
-  static const bool splitk_on = stf::ab_switch("STF_SPLITK", 1) != 0;
-  if (splitk_on && plain && c.Cs != 8 && k >= 'A' && k <= 'F' && a->Nout % 8 == 0 && NT % (a->Nout / 8) == 0 &&
+  if (plain && c.Cs != 8 && k >= 'A' && k <= 'F' && a->Nout % 8 == 0 && NT % (a->Nout / 8) == 0 &&
       a->dst_cstride % 8 == 0 && ((uintptr_t)a->dst & 15) == 0) {
     const Cfg t = cfg_of(k);
     const long blocks = (M / Mg) * ((Mg + t.bm - 1) / t.bm) * ((a->Nout + t.bn - 1) / t.bn);

@@ -156,11 +156,6 @@ int stf::ablation_env(const char* name) {
   return 0;
 }
 
-int stf::ab_switch(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && e[0]) ? atoi(e) : dflt;
-}
-
 char stf::ab_letter(const char* name) {
   const char* e = getenv(name);
   return e ? e[0] : 0;

@@ -388,7 +388,7 @@ def test_bn_act_pool_bitwise(n, C, H, W, groups):
     assert torch.equal(pooled.dense(), F.max_pool2d(ref.dense(), 2))
 
 
-@pytest.mark.parametrize("pool,C", [(False, 64), (True, 64), (True, 128), (True, 512)])
+@pytest.mark.parametrize("pool,C", [(False, 64), (True, 64), (True, 128), (True, 512), (True, 1024)])
 def test_bn_forward_backward(pool, C):
     from stfunet import nhwc
     H = 16

@@ -137,3 +137,25 @@ def test_library_refuses_bad_arguments_without_launch(dtype):
     assert lib.stf_predict_overlay_scratch_bytes(1, 1 << 24) == 64 * 8
     assert lib.stf_predict_overlay_scratch_bytes(64, 256 * 256) == 64 * 32 * 8
     assert lib.stf_predict_overlay_scratch_bytes(5000, 256 * 256) == 5000 * 8
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+def test_bn_backward_refuses_groups_past_32_bit_units(dtype):
+    """A statistics group of 2^31 or more 16-byte units: STF_EINVAL from stf_bn_bwd_reduce (without
+    dpool) and stf_bn_bwd_apply, with fake non-null pointers -- nothing is launched or dereferenced."""
+    from stfunet import _lib
+    lib = _lib.load(dtype)
+    fake = ctypes.c_void_p(1 << 20)
+    N, H, W, C = 1 << 13, 1 << 9, 1 << 9, 8              # one group of 2^31 pixels x one 8-channel chunk
+    assert (N * H * W) * (C // 8) == 1 << 31
+
+    def reduce(N=N, C=C, groups=1):
+        return lib.stf_bn_bwd_reduce(fake, C, None, fake, C, N, H, W, C, groups, fake, fake, fake, fake, 1, None, 0,
+                                     fake, fake, None)
+
+    def apply(M=N * H * W, C=C, groups=1):
+        return lib.stf_bn_bwd_apply(fake, C, fake, C, M, C, groups, None, None, fake, fake, C, None, None, None)
+
+    assert reduce() == EINVAL and apply() == EINVAL
+    assert reduce(N=N // 2, C=16) == EINVAL and apply(C=16, M=N * H * W // 2) == EINVAL     # 2^30 pixels x 2 chunks
+    assert reduce(N=2 * N, groups=2) == EINVAL and apply(M=2 * N * H * W, groups=2) == EINVAL

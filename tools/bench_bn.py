@@ -1,5 +1,5 @@
 """Per-launch time of the BatchNorm element-wise passes at the STF / UNet shapes.
-    STF_BN_G=0|1 python tools/bench_bn.py      (group-major kernels off / on)"""
+    python tools/bench_bn.py"""
 import os
 import sys
 
@@ -18,7 +18,6 @@ def main():
     shapes = [(128, 64, 64, 64, 8), (128, 32, 32, 128, 8), (128, 16, 16, 256, 8), (128, 8, 8, 512, 8),
               (16, 64, 64, 64, 1), (64, 256, 256, 64, 1), (64, 128, 128, 128, 1), (64, 32, 32, 512, 1)]
     torch.manual_seed(0)
-    print(f"STF_BN_G={os.environ.get('STF_BN_G', '1')}")
     for N, H, W, C, G in shapes:
         y = new_feat(N, H, W, C, dev)
         y.buf.normal_()

@@ -1,6 +1,6 @@
-"""Time one 1x1 stf_igemm shape (HIP events over R reps) under the current environment's tile /
-split-K switches: python tools/bench_gemm_shape.py M N K [dst_cs] -- e.g. STF lstm4's per-step dh
-GEMM 1024 512 2048 1024 (STF_IGEMM_CFG / STF_SPLITK select the variant; read once per process)."""
+"""Time one 1x1 stf_igemm shape (HIP events over R reps) under the current environment's tile
+switch: python tools/bench_gemm_shape.py M N K [dst_cs] -- e.g. STF lstm4's per-step dh
+GEMM 1024 512 2048 1024 (STF_IGEMM_CFG selects the variant; read once per process)."""
 import os
 import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -28,5 +28,5 @@ for _ in range(R):
 e1.record()
 torch.cuda.synchronize()
 us = e0.elapsed_time(e1) / R * 1e3
-tag = " ".join(f"{k}={os.environ[k]}" for k in ("STF_IGEMM_CFG", "STF_SPLITK") if k in os.environ)
+tag = " ".join(f"{k}={os.environ[k]}" for k in ("STF_IGEMM_CFG",) if k in os.environ)
 print(f"M={M} N={N} K={K} dcs={dcs} {tag or 'default'}: {us:.1f} us  {2 * M * N * K / us / 1e6:.1f} TF/s")
