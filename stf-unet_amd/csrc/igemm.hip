@@ -2462,10 +2462,15 @@ Route route_of(const stf_igemm_args* a, bool with_stats) {
   const bool plain = !a->lstm && !a->scatter2x2 && !c.transposed;
   const bool dma_ok = (uint64_t)c.N * c.Hs * c.Ws * c.src_cstride * 2 < 0xFFFFFF00ull &&
                       (uint64_t)a->Nout * c.R * c.S * c.Cs * 2 < 0xFFFFFF00ull;
-  const bool conv3 = plain && c.R == 3 && c.S == 3 && c.stride == 1 && c.pad == 1 && c.Hd == c.Hs && c.Wd == c.Ws;
+  // the tile kernels ('K', halo family) store through a 32-bit buffer descriptor over the whole
+  // destination and read the fused BN-backward y through one: both extents must fit it, else the
+  // launch takes a linear kernel (64-bit destination addressing; the BN-backward reduce runs after)
+  const bool tile_ok = (uint64_t)M * a->dst_cstride * 2 < 0xFFFFFF00ull &&
+                       (!a->bnr || (uint64_t)M * a->bnr->y_cstride * 2 < 0xFFFFFF00ull);
+  const bool conv3 = plain && c.R == 3 && c.S == 3 && c.stride == 1 && c.pad == 1 && c.Hd == c.Hs && c.Wd == c.Ws &&
+                     tile_ok;
   const bool c8 = f == '0' && conv3 && !a->bnr && !a->accumulate && c.Cs == 8 && c.src_cstride % 8 == 0 &&
-                  a->Nout == 64 && a->dst_cstride % 8 == 0 && ((uintptr_t)a->dst & 15) == 0 &&
-                  (uint64_t)c.N * c.Hd * c.Wd * a->dst_cstride * 2 < 0xFFFFFF00ull;
+                  a->Nout == 64 && a->dst_cstride % 8 == 0 && ((uintptr_t)a->dst & 15) == 0;
   const bool four = c.Hd == 8 && c.Wd == 8 && c.N % 4 == 0 && a->Nout % 64 == 0 && c.Cs % 32 == 0 && imgs % 4 == 0;
   const bool two = !four && (with_stats || a->Nout > 256) && c.Hd == 16 && c.Wd == 16 && c.N % 2 == 0 && imgs % 2 == 0;
   const bool halo = conv3 && a->Nout % 64 == 0 &&

@@ -375,10 +375,11 @@ def igemm(src: Feat, wgt, nout, dst: Feat, R, S, stride, pad, transposed=False, 
                   dst.cs, _p(bias), None, int(scatter2x2), M // groups if groups > 1 else 0, int(accumulate),
                   ctypes.pointer(lstm) if lstm is not None else None)
     # the size queries below are pure functions of the launch signature (geometry, flags,
-    # which optional pointers are set, the destination's 16-B alignment): asked once each
+    # which optional pointers are set, the BN-backward y's channel stride, the destination's 16-B
+    # alignment): asked once each
     qkey = (src.N, src.H, src.W, src.C, src.cs, Hd, Wd, R, S, stride, pad, transposed, nout, dst.cs,
             bias is None, scatter2x2, groups, accumulate, None if lstm is None else lstm.backward,
-            bnr is not None, want_stats, dptr & 15)
+            None if bnr is None else bnr[0].cs, want_stats, dptr & 15)
     q = _QUERIES.get(qkey)
     stats, tiles = None, 0
     if bnr is not None:
