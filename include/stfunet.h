@@ -458,7 +458,11 @@ int stf_lstm_seq_supported(int C);
  * GEMM; dgates = [T][P][4C] 16-bit pre-activation gate gradients (for the weight gradient
  * afterwards), dx = rows [T][P] of stride dx_cstride receiving dL/dx_t in channels [0, C);
  * dh_last = dL/dh_{T-1} (stride dh_cstride).  Same values as the per-step path (stf_igemm
- * with the LSTM backward epilogue + the dgates x W GEMM).  C = 64 only; 16-B alignment. */
+ * with the LSTM backward epilogue + the dgates x W GEMM).  C = 64 only; 16-B alignment.
+ * dx == NULL (additive: the ABI version stays 17; it was STF_EINVAL before): nothing consumes
+ * the input gradient (everything upstream of the LSTM is frozen).  Only dgates is written:
+ * per step the launch computes just dh_{t-1} = dgates_t W_hh, with every dh element accumulated
+ * in the same order as with dx, so dgates is bit-identical; dx_cstride is ignored. */
 int stf_lstm_seq_bwd(const void* wcat, const void* wcat_t, const float* bias, const void* lbuf, int P, int T,
                      int C, const float* c_all, const void* dh_last, int dh_cstride, void* dgates, void* dx,
                      int dx_cstride, stf_stream_t stream);

@@ -163,7 +163,13 @@ __global__ __launch_bounds__(NT, OCC) void lstm_seq_fwd_kernel(const uint16_t* _
 // One workgroup per CU (weights + transposed weights + two accumulator sets exceed a
 // 2-wave register budget); the next step's [x | h] rows and c_{t-2} are prefetched
 // into registers behind the step's MFMAs.
-template <int C>
+//
+// DX = false: nothing consumes dx_t (everything upstream of the LSTM is frozen).  GEMM2 then
+// has only the C rows dh_{t-1} = dgates x W_hh, spread over all four waves (NF2 and the w2
+// registers halve), there is no dx staging tile and no per-step dx store, and step 0 runs no
+// GEMM2 at all (dh_{-1} feeds nothing).  Every dh element is the same MFMA chain over the same
+// k order as with DX, so dgates and all recurrent values are bit-identical.
+template <int C, bool DX>
 __global__ __launch_bounds__(NT, 1) void lstm_seq_bwd_kernel(const uint16_t* __restrict__ wcat,
                                                             const uint16_t* __restrict__ wcat_t,
                                                             const float* __restrict__ bias, const uint16_t* lbuf,
@@ -173,7 +179,9 @@ __global__ __launch_bounds__(NT, 1) void lstm_seq_bwd_kernel(const uint16_t* __r
                                                             int dxcs) {
   constexpr int K1 = 2 * C / 32, K2 = 4 * C / 32;   // k-steps of GEMM1 (x|h) and GEMM2 (gates)
   constexpr int NF1 = C / 16;                       // GEMM1 n-fragments per wave (C gate rows)
-  constexpr int NF2 = 2 * C / 4 / 16;               // GEMM2 n-fragments per wave (2C/4 rows of [dx|dh])
+  constexpr int O2 = DX ? 0 : C;                    // first GEMM2 output row ([dx | dh] rows of wcat_t)
+  constexpr int W2 = (2 * C - O2) / 4;              // GEMM2 output rows per wave
+  constexpr int NF2 = W2 / 16;                      // GEMM2 n-fragments per wave
   constexpr int MF = BM / 16;
   constexpr int R1 = 2 * C / 8, RC = C / 4, RG = 4 * C / 8, RH = C / 8;   // 16-B chunks per row
   constexpr int XCH = BM * R1 / NT, CCH = BM * RC / NT;
@@ -182,7 +190,7 @@ __global__ __launch_bounds__(NT, 1) void lstm_seq_bwd_kernel(const uint16_t* __r
   __shared__ __attribute__((aligned(16))) float cb[3][BM * C];           // c tiles (rotating)
   __shared__ __attribute__((aligned(16))) uint16_t dhs[BM * C];          // dh_t
   __shared__ __attribute__((aligned(16))) uint16_t dgs[BM * 4 * C];      // dgates
-  __shared__ __attribute__((aligned(16))) uint16_t dxs[BM * C];          // dx_t staging
+  __shared__ __attribute__((aligned(16))) uint16_t dxs[DX ? BM * C : 8]; // dx_t staging
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int fr = lane & 15, fk = lane >> 4;
@@ -206,7 +214,7 @@ __global__ __launch_bounds__(NT, 1) void lstm_seq_bwd_kernel(const uint16_t* __r
   }
 #pragma unroll
   for (int nf = 0; nf < NF2; ++nf) {
-    const int o = wave * (2 * C / 4) + nf * 16 + fr;
+    const int o = O2 + wave * W2 + nf * 16 + fr;
 #pragma unroll
     for (int ks = 0; ks < K2; ++ks)
       w2[nf][ks] = *reinterpret_cast<const e16x8*>(wcat_t + (size_t)o * 4 * C + ks * 32 + fk * 8);
@@ -323,40 +331,44 @@ __global__ __launch_bounds__(NT, 1) void lstm_seq_bwd_kernel(const uint16_t* __r
           *reinterpret_cast<const uint4*>(&dgs[o16(r, q, RG)]);
     }
     // 3. [dx_t | dh_{t-1}] = dgates x W
-    f32x4 a2[MF][NF2];
-#pragma unroll
-    for (int mf = 0; mf < MF; ++mf)
-#pragma unroll
-      for (int nf = 0; nf < NF2; ++nf) a2[mf][nf] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < K2; ++ks) {
-      e16x8 bf[MF];
-#pragma unroll
-      for (int mf = 0; mf < MF; ++mf)
-        bf[mf] = *reinterpret_cast<const e16x8*>(&dgs[o16(mf * 16 + fr, ks * 4 + fk, RG)]);
+    if (DX || t > 0) {                                 // (without dx, step 0 has no output left)
+      f32x4 a2[MF][NF2];
 #pragma unroll
       for (int mf = 0; mf < MF; ++mf)
 #pragma unroll
-        for (int nf = 0; nf < NF2; ++nf) a2[mf][nf] = mfma16x16x32(w2[nf][ks], bf[mf], a2[mf][nf]);
-    }
+        for (int nf = 0; nf < NF2; ++nf) a2[mf][nf] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int mf = 0; mf < MF; ++mf) {
-      const int r = mf * 16 + fr;
+      for (int ks = 0; ks < K2; ++ks) {
+        e16x8 bf[MF];
 #pragma unroll
-      for (int nf = 0; nf < NF2; ++nf) {
-        const int o = wave * (2 * C / 4) + nf * 16 + fk * 4;     // 4 consecutive output channels
-        const uint2 v = make_uint2(pack2(a2[mf][nf][0], a2[mf][nf][1]), pack2(a2[mf][nf][2], a2[mf][nf][3]));
-        const int oo = o < C ? o : o - C;
-        uint16_t* buf = o < C ? dxs : dhs;
-        *reinterpret_cast<uint2*>(&buf[r * C + ((((oo >> 3) ^ (r & 7))) << 3) + (oo & 7)]) = v;
+        for (int mf = 0; mf < MF; ++mf)
+          bf[mf] = *reinterpret_cast<const e16x8*>(&dgs[o16(mf * 16 + fr, ks * 4 + fk, RG)]);
+#pragma unroll
+        for (int mf = 0; mf < MF; ++mf)
+#pragma unroll
+          for (int nf = 0; nf < NF2; ++nf) a2[mf][nf] = mfma16x16x32(w2[nf][ks], bf[mf], a2[mf][nf]);
+      }
+#pragma unroll
+      for (int mf = 0; mf < MF; ++mf) {
+        const int r = mf * 16 + fr;
+#pragma unroll
+        for (int nf = 0; nf < NF2; ++nf) {
+          const int o = O2 + wave * W2 + nf * 16 + fk * 4;       // 4 consecutive output channels
+          const uint2 v = make_uint2(pack2(a2[mf][nf][0], a2[mf][nf][1]), pack2(a2[mf][nf][2], a2[mf][nf][3]));
+          const int oo = o < C ? o : o - C;
+          uint16_t* buf = (DX && o < C) ? dxs : dhs;
+          *reinterpret_cast<uint2*>(&buf[r * C + ((((oo >> 3) ^ (r & 7))) << 3) + (oo & 7)]) = v;
+        }
       }
     }
     if (t > 0) { store_xh(xb ^ 1); store_c((t + 1) % 3); }
     __syncthreads();
-    for (int e = tid; e < rows * RH; e += NT) {
-      const int r = e / RH, q = e - r * RH;
-      *reinterpret_cast<uint4*>(dxh + ((size_t)t * P + m0 + r) * dxcs + q * 8) =
-          *reinterpret_cast<const uint4*>(&dxs[r * C + ((q ^ (r & 7)) << 3)]);
+    if (DX) {
+      for (int e = tid; e < rows * RH; e += NT) {
+        const int r = e / RH, q = e - r * RH;
+        *reinterpret_cast<uint4*>(dxh + ((size_t)t * P + m0 + r) * dxcs + q * 8) =
+            *reinterpret_cast<const uint4*>(&dxs[r * C + ((q ^ (r & 7)) << 3)]);
+      }
     }
   }
 }
@@ -367,15 +379,20 @@ extern "C" int stf_lstm_seq_bwd(const void* wcat, const void* wcat_t, const floa
                                 int T, int C, const float* c_all, const void* dh_last, int dh_cstride, void* dgates,
                                 void* dx, int dx_cstride, stf_stream_t stream) {
   if (P <= 0 || T <= 0) return 0;
-  if (C != 64 || !wcat || !wcat_t || !bias || !lbuf || !c_all || !dh_last || !dgates || !dx || dh_cstride < C ||
-      dx_cstride < C || dx_cstride % 8)
+  if (C != 64 || !wcat || !wcat_t || !bias || !lbuf || !c_all || !dh_last || !dgates || dh_cstride < C)
     return STF_EINVAL;
+  if (dx && (dx_cstride < C || dx_cstride % 8)) return STF_EINVAL;
   if (((uintptr_t)wcat & 15) || ((uintptr_t)wcat_t & 15) || ((uintptr_t)lbuf & 15) || ((uintptr_t)dgates & 15) ||
       ((uintptr_t)dx & 15) || ((uintptr_t)c_all & 15))
     return STF_EINVAL;
-  hipLaunchKernelGGL((lstm_seq_bwd_kernel<64>), dim3((P + BM - 1) / BM), dim3(NT), 0, (hipStream_t)stream,
-                     (const uint16_t*)wcat, (const uint16_t*)wcat_t, bias, (const uint16_t*)lbuf, P, T, c_all,
-                     (const uint16_t*)dh_last, dh_cstride, (uint16_t*)dgates, (uint16_t*)dx, dx_cstride);
+  if (dx)
+    hipLaunchKernelGGL((lstm_seq_bwd_kernel<64, true>), dim3((P + BM - 1) / BM), dim3(NT), 0, (hipStream_t)stream,
+                       (const uint16_t*)wcat, (const uint16_t*)wcat_t, bias, (const uint16_t*)lbuf, P, T, c_all,
+                       (const uint16_t*)dh_last, dh_cstride, (uint16_t*)dgates, (uint16_t*)dx, dx_cstride);
+  else    // dx == NULL: nothing consumes the input gradient, only dgates and the recurrence
+    hipLaunchKernelGGL((lstm_seq_bwd_kernel<64, false>), dim3((P + BM - 1) / BM), dim3(NT), 0, (hipStream_t)stream,
+                       (const uint16_t*)wcat, (const uint16_t*)wcat_t, bias, (const uint16_t*)lbuf, P, T, c_all,
+                       (const uint16_t*)dh_last, dh_cstride, (uint16_t*)dgates, (uint16_t*)nullptr, 0);
   STF_CHECK_LAUNCH();
   return 0;
 }

@@ -8,7 +8,9 @@ in one flat fp32 buffer and backward finishes parameter blocks in reverse flat
 order, so the finished gradients always form a suffix of that buffer: as soon as
 ``bucket_mb`` of new suffix is final, an all-reduce of that contiguous slice is
 enqueued while the remaining backward kernels keep the GPU busy.  ``finish()``
-reduces the last bucket and makes the compute stream wait.
+reduces the last bucket and makes the compute stream wait.  Only
+``[first trainable offset, numel)`` is ever reduced: the gradient slices of a frozen
+prefix (a frozen encoder) are never read and stay as each rank left them.
 
 Gradients written on side streams (the STF program's LSTM backwards and weight-gradient
 stream) reach the hook as ``deps``.  A bucket's collective is enqueued ON the joiner stream
@@ -61,6 +63,7 @@ class GradAllReduce:
         self.works = []
         self.launched_from = None       # suffix [launched_from, numel) already enqueued
         self.ready_from = None
+        self.lo = 0                     # first trainable flat offset of the step in flight
         self.deps = []                  # side streams the next bucket must wait for
 
     def _joiner(self, dev):
@@ -95,8 +98,11 @@ class GradAllReduce:
                 self.deps.append(s)
         if self.launched_from is None:
             self.launched_from = self.ready_from = self.flat.numel
-        self.ready_from = min(self.ready_from, begin)
-        if self.launched_from - self.ready_from >= self.bucket or self.ready_from == 0:
+            # frozen parameters' slices (a prefix of the flat order up to the first trainable
+            # parameter) are never read: nothing below ``lo`` is reduced
+            self.lo = self.flat.first_trainable_offset()
+        self.ready_from = max(self.lo, min(self.ready_from, begin))
+        if self.launched_from - self.ready_from >= self.bucket or self.ready_from == self.lo:
             self._launch(self.ready_from, self.launched_from)
             self.launched_from = self.ready_from
             return True
@@ -104,8 +110,8 @@ class GradAllReduce:
 
     def finish(self):
         """Complete every outstanding bucket (call after loss.backward())."""
-        if self.launched_from is not None and self.launched_from > 0:
-            self._launch(0, self.launched_from)
+        if self.launched_from is not None and self.launched_from > self.lo:
+            self._launch(self.lo, self.launched_from)
         joined = set()
         for w, t in self.works:
             if w is None:

@@ -91,6 +91,18 @@ class FlatParams:
     def any_requires_grad(self):
         return any(map(_REQ, self.params))
 
+    def requires_grad_flags(self):
+        """The parameters' ``requires_grad`` flags in flat order (what the freeze map is a function of)."""
+        return tuple(map(_REQ, self.params))
+
+    def first_trainable_offset(self):
+        """Flat offset of the first parameter that requires grad (``numel`` if none does): gradients
+        below it belong to frozen parameters only, and nothing reads them."""
+        for p, off in zip(self.params, self.offsets):
+            if p.requires_grad:
+                return off
+        return self.numel
+
     def grad_view(self, p):
         return self._views[self.index[id(p)]]
 

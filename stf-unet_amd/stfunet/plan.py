@@ -23,7 +23,8 @@ Anything that changes what the step would launch -- shapes, train / eval, storag
 dtype, the current stream, parameter or buffer addresses, the gradient buffer, a DDP
 hook appearing, a scalar baked into a recorded launch (BatchNorm momentum / eps, the
 ``STF_*`` environment switches the schedule reads per call, the programs' own knobs such as
-the LSTM spin limit) -- changes the signature and the plan is recorded again.
+the LSTM spin limit, a BatchNorm submodule's train / eval mode, the freeze map derived from the
+parameters' ``requires_grad`` flags) -- changes the signature and the plan is recorded again.
 
 Pool lifetime: a recorded entry's private ``MemPool`` is never destroyed implicitly.  When an
 entry dies (evicted, its runtime closed, or its program collected -- by refcount or by the
@@ -274,10 +275,14 @@ class StepRuntime:
         # scalars the recorded launches carry by value: BatchNorm momentum / eps, the STF_*
         # switches the schedule reads per call, the program's own knobs
         bn = tuple((b.momentum, b.eps) for b in self._bns)
+        # what the schedule itself depends on: every BatchNorm's own mode (a submodule in .eval())
+        # and the freeze map (which blocks' backward runs, so what the forward keeps)
+        modes = tuple(b.training for b in self._bns)
+        fmap = p.fmap.key if p.fmap is not None else None
         env = _stf_env()
         knobs = p.plan_knobs() if hasattr(p, "plan_knobs") else ()
         return (tuple(x.shape), x.dtype, x.device, training, _lib.storage_dtype(), _lib.stream(),
-                p.flat.data.data_ptr(), bufs, bn, env, knobs)
+                p.flat.data.data_ptr(), bufs, bn, env, knobs, modes, fmap)
 
     def _entry(self, sig):
         e = self.entries.get(sig)
@@ -355,7 +360,9 @@ class StepRuntime:
         e = next((v for v in self.entries.values() if v.fwd is not None and v.S is S), None)
         if e is None or not enabled() or nhwc.TIMER is not None:
             return p.backward(S, dlogits)
-        bsig = (tuple(dlogits.shape), p.flat.grad.data_ptr(), p.grad_ready_hook is not None, _lib.stream())
+        fmap = getattr(S, "fmap", None)
+        bsig = (tuple(dlogits.shape), p.flat.grad.data_ptr(), p.grad_ready_hook is not None, _lib.stream(),
+                fmap.key if fmap is not None else None)
         if e.bwd is None or bsig != e.bsig:
             return self._record_backward(e, S, dlogits, bsig)
         e.dl.copy_(dlogits)

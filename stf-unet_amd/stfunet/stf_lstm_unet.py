@@ -24,7 +24,12 @@ function and block steps of program.py):
   * decoder: ConvTranspose2d(3,2,1,1) as a transposed gather into the concat
     buffer, 1x1 fusion conv, ResidualConvBlock; final 1x1 fused into the head.
   * backward mirrors it (BPTT = per-step cell kernel + one GEMM; LSTM weight
-    gradients = one GEMM over all T steps).
+    gradients = one GEMM over all T steps);
+  * frozen parameters (``requires_grad_(False)``, e.g. the ResNet encoder): the step's freeze map
+    (program.py) says per block whether its parameter gradients and its input gradient are needed;
+    launches that would only produce the others are not issued, an LSTM with nothing trainable
+    upstream runs its backward without the input half, and the forward keeps no state for blocks
+    whose backward will not run.
 """
 import os
 
@@ -101,6 +106,7 @@ class ResBlockProgram:
         self.cout = conv1.out_channels
 
     def forward(self, src: Feat, out: Feat, training, groups):
+        """``training``: None = every BatchNorm in its own mode (``conv_bn``), or one flag for all."""
         dev, C, st = src.buf.device, self.cout, self.stride
         s = _S()
         s.src, s.out = src, out
@@ -117,10 +123,12 @@ class ResBlockProgram:
         s.y1, s.a1, s.y2 = y1, a1, y2
         return s
 
-    def backward(self, s, gv, dout: Feat = None, g: Feat = None, dsrc: Feat = None, need_dsrc=True):
+    def backward(self, s, gv, dout: Feat = None, g: Feat = None, dsrc: Feat = None, need_dsrc=True, need_w=True):
         """``dout``: grad w.r.t. the block output (masked here by out > 0), or
         ``g``: already-masked grad (the head fused the final ReLU).  ``dsrc``:
-        destination that the input gradient is accumulated into (None: new)."""
+        destination that the input gradient is accumulated into (None: new).
+        ``need_dsrc=False``: nothing consumes the input gradient (its dgrads are not launched,
+        returns None); ``need_w=False``: a frozen block, no weight gradients."""
         src = s.src
         if g is None:
             dy2, g = nhwc.bn_backward(s.y2, s.bn2, self.bn2, gv(self.bn2.weight), gv(self.bn2.bias), dz=dout,
@@ -128,17 +136,20 @@ class ResBlockProgram:
         else:
             dy2 = nhwc.bn_backward(s.y2, s.bn2, self.bn2, gv(self.bn2.weight), gv(self.bn2.bias), dz=g,
                                    relu=False, out=new_feat(g.N, g.H, g.W, g.C, g.buf.device))
-        dy1 = conv_pair_backward(s, gv, dy2, self.conv1, self.bn1, self.conv2, self.stride)
+        dy1 = conv_pair_backward(s, gv, dy2, self.conv1, self.bn1, self.conv2, self.stride, need_w=need_w)
         del dy2
         if self.sc_conv is None:
             # identity shortcut: d_src = g + dgrad(conv1)
             if dsrc is not None:
                 raise NotImplementedError("identity-shortcut blocks produce their input gradient in place")
+            if not need_dsrc:
+                return None
             nhwc.conv_dgrad(dy1, self.conv1.weight, g, 3, 3, self.stride, 1, accumulate=True)
             return g
         dyd = nhwc.bn_backward(s.yd, s.bnd, self.sc_bn, gv(self.sc_bn.weight), gv(self.sc_bn.bias), dz=g,
                                relu=False)
-        nhwc.wgrad(dyd, src, 1, 1, self.stride, 0, gv(self.sc_conv.weight))
+        if need_w:
+            nhwc.wgrad(dyd, src, 1, 1, self.stride, 0, gv(self.sc_conv.weight))
         if not need_dsrc:
             return None
         acc = dsrc is not None
@@ -250,18 +261,25 @@ class LSTMProgram:
         st.gates = gates if coop else None
         return st
 
-    def backward(self, st, dhT: Feat, gv):
-        """Returns d x_t for every t as a Feat slice [T*B][h][w][C] (stride 2C)."""
+    def backward(self, st, dhT: Feat, gv, need_dx=True, need_w=True):
+        """Returns d x_t for every t as a Feat slice [T*B][h][w][C] (stride 2C).
+
+        ``need_dx=False`` (everything upstream of the LSTM is frozen): only the recurrent half
+        dh_{t-1} = dgates_t W_hh of the backward GEMM is computed -- the whole-sequence kernel's
+        no-dx variant, or the per-step launches without the input-half GEMM -- and None is returned;
+        dgates, and so the weight gradients, are bit for bit the same.  ``need_w=False`` (a frozen
+        LSTM on the way to a trainable encoder): no weight-gradient tail."""
         L, C, lb, T, B = self.lstm, self.C, st.lbuf, st.T, st.B
         dev = lb.buf.device
         npix = B * lb.H * lb.W
-        d2 = new_feat(T * B, lb.H, lb.W, 2 * C, dev)           # rows of step t: [dx_t | dh_{t-1}]
+        # rows of step t: [dx_t | dh_{t-1}] (the whole-sequence kernel keeps dh in LDS: without dx, no buffer)
+        d2 = new_feat(T * B, lb.H, lb.W, 2 * C, dev) if need_dx or not st.fused else None
         dg = new_feat(T * B, lb.H, lb.W, 4 * C, dev)           # pre-activation gate grads (interleaved)
         if st.fused:
             # all T steps backward in one launch (dc in registers, dh_{t-1} in LDS)
             dhT.check()
             call("stf_lstm_seq_bwd", _p(st.wcat), _p(st.wcat_t), _p(st.bias), lb.ptr(), npix, T, C, _p(st.c),
-                 dhT.ptr(), dhT.cs, dg.ptr(), d2.ptr(), d2.cs, stream())
+                 dhT.ptr(), dhT.cs, dg.ptr(), d2.ptr() if need_dx else None, d2.cs if need_dx else 0, stream())
         elif st.coop:
             # C >= 128: all T steps backward in one persistent launch (dgates and [dx | dh]
             # exchanged in-launch inside each pixel block; the forward's gates, no recompute)
@@ -294,19 +312,20 @@ class LSTMProgram:
                     epi = LstmEpi(_p(st.c[t - 1]) if t > 0 else None, _p(st.c[t]), None, 0, None,
                                   1, dh.ptr(), dh.cs, _p(dc) if t < T - 1 else None, _p(dc), dgt.ptr())
                     nhwc.igemm(src, st.wcat, 4 * C, src, 1, 1, 1, 0, bias=st.bias, lstm=epi)
-                if not hoist:
+                if not hoist and need_dx:
                     nhwc.igemm(dgt, st.wcat_t, 2 * C, rows(d2, t * B, B), 1, 1, 1, 0)
                 elif t > 0:                                  # dh_{-1} feeds nothing
                     nhwc.igemm(dgt, w_h, C, rows(d2, t * B, B).slice(C, C), 1, 1, 1, 0)
-            if hoist:
+            if hoist and need_dx:
                 nhwc.igemm(dg, st.wcat_t[:4 * C * C], C, d2.slice(0, C), 1, 1, 1, 0)
-        dwcat = nhwc.empty(8 * C * C, torch.float32, dev)
-        nhwc.wgrad(dg, lb, 1, 1, 1, 0, dwcat, defer=False)
-        dbcat = nhwc.empty(4 * C, torch.float32, dev)
-        nhwc.channel_sum(dg, dbcat)
-        call("stf_lstm_unpack_grad", _p(dwcat), _p(dbcat), C, _p(gv(L.weight_ih_l0)), _p(gv(L.weight_hh_l0)),
-             _p(gv(L.bias_ih_l0)), _p(gv(L.bias_hh_l0)), stream())
-        return d2.slice(0, C)
+        if need_w:
+            dwcat = nhwc.empty(8 * C * C, torch.float32, dev)
+            nhwc.wgrad(dg, lb, 1, 1, 1, 0, dwcat, defer=False)
+            dbcat = nhwc.empty(4 * C, torch.float32, dev)
+            nhwc.channel_sum(dg, dbcat)
+            call("stf_lstm_unpack_grad", _p(dwcat), _p(dbcat), C, _p(gv(L.weight_ih_l0)), _p(gv(L.weight_hh_l0)),
+                 _p(gv(L.bias_ih_l0)), _p(gv(L.bias_hh_l0)), stream())
+        return d2.slice(0, C) if need_dx else None
 
 
 # ------------------------------------------------------------------ program
@@ -336,6 +355,31 @@ class STFProgram(Program):
         self.err_word = None          # sticky device flag of the cooperative LSTM launches
         self._err_host = None         # its pinned host copy, issued at each step boundary
         self._err_event = None
+
+    def graph(self):
+        m = self.m
+        g = [("stem", (m.conv1, m.bn1), ("x",))]
+        prev = "stem"
+        for k in (1, 2, 3, 4):
+            for bi, blk in enumerate(getattr(m, f"layer{k}")):
+                g.append((f"layer{k}.{bi}", (blk,), (prev,)))
+                prev = f"layer{k}.{bi}"             # (with PK maps too: the next layer reads the unfused output)
+            src = prev
+            if m.use_pk_maps:
+                g.append((f"pk_fusion{k}", (getattr(m, f"pk_fusion{k}"),), (prev, "x")))
+                src = f"pk_fusion{k}"
+            g.append((f"lstm{k}", (getattr(m, f"lstm{k}"),), (src,)))
+        below = "lstm4"
+        for n in (4, 3, 2):
+            d = getattr(m, f"decoder{n}")
+            g.append((f"decoder{n}.up", (d.up,), (below,)))
+            g.append((f"decoder{n}.fusion", (d.fusion,), (f"decoder{n}.up", f"lstm{n - 1}")))
+            g.append((f"decoder{n}.res_conv", (d.res_conv,), (f"decoder{n}.fusion",)))
+            below = f"decoder{n}.res_conv"
+        g.append(("upconv1", (m.upconv1,), (below,)))
+        g.append(("final_res", (m.final_res,), ("upconv1",)))
+        g.append(("final", (m.final,), ("final_res",)))
+        return g
 
     def plan_knobs(self):
         """Per-program scalars a recorded plan carries by value (part of its signature)."""
@@ -442,6 +486,10 @@ class STFProgram(Program):
         S = _S()
         S.B, S.T, S.P, S.H, S.W = B, T, P, H, W
         N = T * B
+        # the freeze map: the forward launches do not depend on it, but a block whose backward will
+        # not run keeps no state (its y1 / a1 / y2, the pool argmax) past its own forward
+        fm = S.fmap = self.step_map()
+        bn_train = m.bn1.training              # every BatchNorm runs in its own mode (conv_bn)
         # ---- stem: conv 7x7/s2 over (Cf + P) <= 4 input channels as a 1x1 GEMM over the
         # im2col columns (49 (Cf+P) of them, padded): a per-tap gather would pad every tap
         # to 8 channels (8x the MFMA work at Cf = 1) and its weight gradient re-reads dy
@@ -458,16 +506,16 @@ class STFProgram(Program):
             xin = new_feat(N, H, W, 8, dev)
             call("stf_pack_sequence", _p(x), B, Ttot, Cf, H, W, T, P, 8, xin.ptr(), stream())
             stats, tiles = nhwc.igemm(xin, nhwc.pack_weight(w1, 0, 8), 64, y0, 7, 7, 2, 3,
-                                      want_stats=training, groups=T)
+                                      want_stats=bn_train, groups=T)
         elif kreal == 49 and _STEM_DIRECT and N * h2 * w2 * 64 * 2 < 0xFFFFFF00:    # (32-bit store offsets)
             # one frame channel: the direct 7x7/s2 kernel (no im2col tensor: 268 MB written and read
             # back at cfg3), and in the backward its weight gradient straight from the frames too
             xin = None
             wp = nhwc.pack_weight(w1.view(w1.shape[0], -1, 1, 1), 0, 64)
             tiles = _lib.load().stf_stem_conv7_grid(B, T, H, W)
-            stats = nhwc.empty(T * tiles * 2 * 64, torch.float32, dev) if training else None
+            stats = nhwc.empty(T * tiles * 2 * 64, torch.float32, dev) if bn_train else None
             call("stf_stem_conv7", _p(x), B, Ttot, H, W, T, _p(wp), y0.ptr(), _p(stats), stream())
-            if not training:
+            if not bn_train:
                 tiles = 0
             S.x = x
         else:
@@ -475,18 +523,20 @@ class STFProgram(Program):
             xin = new_feat(N, h2, w2, kpad, dev)
             call("stf_stem_im2col", _p(x), B, Ttot, Cf, H, W, T, P, 7, 2, 3, kpad, xin.ptr(), stream())
             stats, tiles = nhwc.igemm(xin, nhwc.pack_weight(w1.view(w1.shape[0], -1, 1, 1), 0, kpad), 64, y0, 1, 1,
-                                      1, 0, want_stats=training, groups=T)
-        S.bn0 = nhwc.bn_finalize(stats, tiles, m.bn1, y0.M, training, T)
+                                      1, 0, want_stats=bn_train, groups=T)
+        S.bn0 = nhwc.bn_finalize(stats, tiles, m.bn1, y0.M, bn_train, T)
         h4, w4 = (h2 - 1) // 2 + 1, (w2 - 1) // 2 + 1
         p0 = new_feat(N, h4, w4, 64, dev)
         # the window argmax the backward routes through (eval-mode backward needs it too)
-        S.pool_arg = nhwc.empty(N * h4 * w4 * 64, torch.uint8, dev) if need_bwd else None
+        S.pool_arg = nhwc.empty(N * h4 * w4 * 64, torch.uint8, dev) if need_bwd and fm.runs("stem") else None
         # bn1 + relu + maxpool in one pass: the activation relu(bn1(y0)) is never stored (the
         # backward needs only y0 and the argmax)
         y0.check()
         call("stf_bn_act_maxpool3s2", y0.ptr(), N, h2, w2, 64, T, _p(S.bn0.scale), _p(S.bn0.shift), p0.ptr(),
              _p(S.pool_arg), stream())
         S.xin, S.y0, S.p0 = xin, y0, p0
+        if not fm.runs("stem"):
+            S.y0 = None
         # ---- encoder; layer outputs land in the LSTM [x | h] buffers (or PK concat);
         # lstm li (li < 3) starts on its side stream as soon as layer li is done
         S.enc, S.lbuf, S.pkbuf = [], [], []
@@ -511,7 +561,9 @@ class STFProgram(Program):
                     out = pkb.slice(0, C) if P else lbuf.slice(0, C)
                 else:
                     out = new_feat(N, hh, ww, C, dev)
-                saved.append(bp.forward(cur, out, training, T))
+                sb = bp.forward(cur, out, None, T)
+                saved.append(sb if fm.runs(f"layer{li + 1}.{bi}") else None)
+                del sb
                 cur = out
             if P:
                 fus = getattr(m, f"pk_fusion{li + 1}")
@@ -519,19 +571,22 @@ class STFProgram(Program):
                 nhwc.igemm(pkb, wf, C, lbuf.slice(0, C), 1, 1, 1, 0, bias=fus.bias.detach())
             S.enc.append(saved)
             S.lbuf.append(lbuf)
-            S.pkbuf.append(pkb)
+            S.pkbuf.append(pkb if P and fm.runs(f"pk_fusion{li + 1}") else None)
             # ---- per-pixel LSTM of this scale over T
             lp = self.lstm_progs[li]
+            lstm_bwd = need_bwd and fm.runs(f"lstm{li + 1}")
             if li < 3:
                 d = self.decoders[2 - li]
                 Cout = d.up.out_channels
                 dc = dcat[2 - li] = new_feat(B, hh, ww, Cout + d.fusion.in_channels - Cout, dev)
                 nhwc.wait(side[li], main)
                 with torch.cuda.stream(side[li]):
-                    S.lstm[li] = lp.forward(lbuf, T, B, dc.slice(dc.C - lp.C, lp.C), need_bwd)
+                    st = lp.forward(lbuf, T, B, dc.slice(dc.C - lp.C, lp.C), lstm_bwd)
             else:
                 e4f = new_feat(B, hh, ww, lp.C, dev)
-                S.lstm[li] = lp.forward(lbuf, T, B, e4f, need_bwd)
+                st = lp.forward(lbuf, T, B, e4f, lstm_bwd)
+            S.lstm[li] = st if lstm_bwd else None
+            del st
         S.dcat = dcat
         # ---- decoder
         S.dec = []
@@ -557,10 +612,12 @@ class STFProgram(Program):
             nhwc.igemm(cat, nhwc.pack_weight(d.fusion.weight, 0, cat.C), Cout, yf, 1, 1, 1, 0,
                        bias=d.fusion.bias.detach())
             out = new_feat(B, cat.H, cat.W, Cout, dev)
-            rs = self.dec_res[i].forward(yf, out, training, 1)
+            rs = self.dec_res[i].forward(yf, out, None, 1)
             dsv = _S()
             dsv.x, dsv.cat, dsv.yf, dsv.res, dsv.up = cur, cat, yf, rs, up
-            S.dec.append(dsv)
+            name = f"decoder{4 - i}"
+            S.dec.append(dsv if any(fm.runs(f"{name}.{b}") for b in ("up", "fusion", "res_conv")) else None)
+            del rs, dsv
             cur = out
         # ---- upconv1 + final_res + final (head)
         up = m.upconv1
@@ -568,7 +625,10 @@ class STFProgram(Program):
         nhwc.igemm(cur, nhwc.pack_weight(up.weight, 4), up.out_channels, u1, 3, 3, 2, 1, transposed=True,
                    bias=up.bias.detach())
         fr_out = new_feat(B, u1.H, u1.W, up.out_channels, dev)
-        S.fr = self.final_res.forward(u1, fr_out, training, 1)
+        S.fr = self.final_res.forward(u1, fr_out, None, 1)
+        if not fm.runs("final_res"):           # the head's backward reads the block's output only
+            S.fr = _S()
+            S.fr.out = fr_out
         S.d2out, S.u1 = cur, u1
         K = m.final.out_channels
         logits = nhwc.empty((B, K, u1.H, u1.W), torch.float32, dev)
@@ -591,16 +651,28 @@ class STFProgram(Program):
         B, T, P = S.B, S.T, S.P
         if S.low is not None:                  # output_size="input": back through the resize first
             dlogits = resize.resize_bwd(dlogits, S.low)
+        # The freeze map decides per block: weight gradients only where a parameter is trainable
+        # (need_w), the input gradient only where something upstream still wants it (need_din); a
+        # block with neither is not run, so the backward ends at the lowest trainable block.  The
+        # _done calls stay where they are: finished gradients still form a suffix of the flat order
+        fm = S.fmap
         # (no BatchNorm under the head here: its partial sums are not used)
         g, _, _ = nhwc.head_bwd(dlogits, S.fr.out, S.ident, S.head_w, gv(m.final.weight), gv(m.final.bias))
         self._done(m.final)
-        d_u1 = self.final_res.backward(S.fr, gv, g=g)
+        d_u1 = None
+        if fm.runs("final_res"):
+            d_u1 = self.final_res.backward(S.fr, gv, g=g, need_dsrc=fm["final_res"].need_din,
+                                           need_w=fm["final_res"].need_w)
         self._done(m.final_res)
-        up = m.upconv1
-        nhwc.wgrad(S.d2out, d_u1, 3, 3, 2, 1, gv(up.weight))
-        nhwc.channel_sum(d_u1, gv(up.bias))
-        dcur = new_feat(B, S.d2out.H, S.d2out.W, S.d2out.C, dev)
-        nhwc.igemm(d_u1, nhwc.pack_weight(up.weight, 3), S.d2out.C, dcur, 3, 3, 2, 1)
+        up, nu = m.upconv1, fm["upconv1"]
+        dcur = None
+        if d_u1 is not None:
+            if nu.need_w:
+                nhwc.wgrad(S.d2out, d_u1, 3, 3, 2, 1, gv(up.weight))
+                nhwc.channel_sum(d_u1, gv(up.bias))
+            if nu.need_din:
+                dcur = new_feat(B, S.d2out.H, S.d2out.W, S.d2out.C, dev)
+                nhwc.igemm(d_u1, nhwc.pack_weight(up.weight, 3), S.d2out.C, dcur, 3, 3, 2, 1)
         del d_u1
         self._done(up)
         # decoders 2, 3, 4 (reverse of forward order); lstm k's backward starts on its
@@ -610,67 +682,96 @@ class STFProgram(Program):
 
         dhT = [None] * 4
         de = [None] * 4
+        ran = [False] * 4              # lstm k's backward was issued (k < 3: on side stream k) ...
+        joined = [False] * 3           # ... and the main stream has waited for that stream since
 
         def lstm_bwd(k):
-            de[k] = self.lstm_progs[k].backward(S.lstm[k], dhT[k], gv)
-            de[k].buf.record_stream(main)
+            n = fm[f"lstm{k + 1}"]
+            de[k] = self.lstm_progs[k].backward(S.lstm[k], dhT[k], gv, need_dx=n.need_din, need_w=n.need_w)
+            if de[k] is not None:
+                de[k].buf.record_stream(main)
+            ran[k] = True
         for i in (2, 1, 0):
             d, dsv = self.decoders[i], S.dec[i]
+            name = f"decoder{4 - i}"
+            nr, nf, nu = fm[name + ".res_conv"], fm[name + ".fusion"], fm[name + ".up"]
             Cout = d.up.out_channels
-            d_yf = self.dec_res[i].backward(dsv.res, gv, dout=dcur)
-            nhwc.wgrad(d_yf, dsv.cat, 1, 1, 1, 0, gv(d.fusion.weight))
-            nhwc.channel_sum(d_yf, gv(d.fusion.bias))
-            dcat = new_feat(B, dsv.cat.H, dsv.cat.W, dsv.cat.C, dev)
-            nhwc.conv_dgrad(d_yf, d.fusion.weight, dcat, 1, 1, 1, 0)
-            del d_yf
-            dup = dcat.slice(0, Cout)
-            if dsv.up is not None:                             # through the bilinear size fallback
-                du = new_feat(B, dsv.up.H, dsv.up.W, Cout, dev)
-                call("stf_bilinear_ac_bwd", dup.ptr(), B, dup.H, dup.W, Cout, dup.cs, du.ptr(), du.H, du.W, du.cs,
-                     stream())
-                dup = du
-            nhwc.wgrad(dsv.x, dup, 3, 3, 2, 1, gv(d.up.weight))
-            nhwc.channel_sum(dup, gv(d.up.bias))
-            dx = new_feat(B, dsv.x.H, dsv.x.W, dsv.x.C, dev)
-            nhwc.igemm(dup, nhwc.pack_weight(d.up.weight, 3), dsv.x.C, dx, 3, 3, 2, 1)
             k = 2 - i                                          # skip of scale k (decoder4 -> idx 2)
-            dhT[k] = dcat.slice(Cout, dcat.C - Cout)
-            nhwc.wait(side[k], main)
-            with torch.cuda.stream(side[k]):
-                lstm_bwd(k)
+            d_yf = dx = None
+            if fm.runs(name + ".res_conv"):
+                d_yf = self.dec_res[i].backward(dsv.res, gv, dout=dcur, need_dsrc=nr.need_din, need_w=nr.need_w)
+            if d_yf is not None and nf.need_w:
+                nhwc.wgrad(d_yf, dsv.cat, 1, 1, 1, 0, gv(d.fusion.weight))
+                nhwc.channel_sum(d_yf, gv(d.fusion.bias))
+            if d_yf is not None and nf.need_din:
+                # (one launch over the whole concat, whichever of its halves is wanted)
+                dcat = new_feat(B, dsv.cat.H, dsv.cat.W, dsv.cat.C, dev)
+                nhwc.conv_dgrad(d_yf, d.fusion.weight, dcat, 1, 1, 1, 0)
+                del d_yf
+                if fm.runs(name + ".up"):
+                    dup = dcat.slice(0, Cout)
+                    if dsv.up is not None:                     # through the bilinear size fallback
+                        du = new_feat(B, dsv.up.H, dsv.up.W, Cout, dev)
+                        call("stf_bilinear_ac_bwd", dup.ptr(), B, dup.H, dup.W, Cout, dup.cs, du.ptr(), du.H, du.W,
+                             du.cs, stream())
+                        dup = du
+                    if nu.need_w:
+                        nhwc.wgrad(dsv.x, dup, 3, 3, 2, 1, gv(d.up.weight))
+                        nhwc.channel_sum(dup, gv(d.up.bias))
+                    if nu.need_din:
+                        dx = new_feat(B, dsv.x.H, dsv.x.W, dsv.x.C, dev)
+                        nhwc.igemm(dup, nhwc.pack_weight(d.up.weight, 3), dsv.x.C, dx, 3, 3, 2, 1)
+                if fm.runs(f"lstm{k + 1}"):
+                    dhT[k] = dcat.slice(Cout, dcat.C - Cout)
+                    nhwc.wait(side[k], main)
+                    with torch.cuda.stream(side[k]):
+                        lstm_bwd(k)
             dcur = dx
             self._done(d)
-        dhT[3] = dcur                                          # decoder4 input = h_T of lstm4
-        lstm_bwd(3)
+        if fm.runs("lstm4"):
+            dhT[3] = dcur                                      # decoder4 input = h_T of lstm4
+            lstm_bwd(3)
         # join the side streams: all of them now when PK fusion needs every scale, else each
-        # just before the encoder block that first touches its d x_t; a gradient bucket holding
-        # lstm k's gradients waits for side stream k itself (ready-hook dependency), not the main
-        # stream
+        # just before the encoder block that first touches its d x_t (or, where a frozen encoder
+        # has no such block, at the end); a gradient bucket holding lstm k's gradients waits for
+        # side stream k itself (ready-hook dependency), not the main stream
         for k in (3, 2, 1, 0):
-            if P and k < 3:
+            if P and k < 3 and ran[k]:
                 nhwc.wait(main, side[k])
+                joined[k] = True
             self._done(self.lstms[k], side[k] if k < 3 else None)
         if P:
             for k in (3, 2, 1, 0):
-                de[k] = self._pk_fusion_backward(S, k, de[k], gv)
+                de[k] = self._pk_fusion_backward(S, k, de[k], gv, fm[f"pk_fusion{k + 1}"])
             self._done(m.pk_fusion1)
         # encoder: layer4 -> layer1; d(layer k-1 output) accumulates into de[k-1]
         # layer li reads d(its output) = de[li] (lstm li's d x_t, side stream li) and its first
         # block ACCUMULATES d(its input) into de[li - 1], which lstm li-1's backward writes on side
         # stream li-1: main waits for each side stream before the first of those two uses
+        dout = None
         for li in (3, 2, 1, 0):
             progs, saved = self.layers[li], S.enc[li]
             dout = de[li]                           # (li < 3: side stream li waited in layer li+1)
             for bi in range(len(progs) - 1, -1, -1):
+                n = fm[f"layer{li + 1}.{bi}"]
+                if not (n.need_w or n.need_din):    # (nor does any block below it: the backward ends)
+                    dout = None
+                    break
                 bp, s = progs[bi], saved[bi]
                 if bi == 0:
                     target = de[li - 1] if li > 0 else None
-                    if li > 0 and not P:
+                    if li > 0 and not P and ran[li - 1]:
                         nhwc.wait(main, side[li - 1])
-                    dout = bp.backward(s, gv, dout=dout, dsrc=target)
+                        joined[li - 1] = True
+                    dout = bp.backward(s, gv, dout=dout, dsrc=target, need_dsrc=n.need_din, need_w=n.need_w)
                 else:
-                    dout = bp.backward(s, gv, dout=dout)
+                    dout = bp.backward(s, gv, dout=dout, need_dsrc=n.need_din, need_w=n.need_w)
             self._done(getattr(m, f"layer{li + 1}"))
+        for k in (2, 1, 0):                         # an LSTM whose d x_t no encoder block read
+            if ran[k] and not joined[k]:
+                nhwc.wait(main, side[k])
+        if not fm.runs("stem"):
+            return
         # stem: maxpool(3,2,1) <- relu(bn1(conv1 x))
         # the pooled gradient routed by the argmax inside the BN backward's passes (no full-size
         # d relu(bn1(y0)) tensor)
@@ -679,6 +780,8 @@ class STFProgram(Program):
         kreal = w1[0].numel()
         if self.want_dx:
             self.dx = self._input_grad(S, dy0, w1, B, T, P, dev)
+        if not fm["stem"].need_w:
+            return
         if S.xin is None:                      # direct stem conv: the gradient gathers the input too
             assert dy0.cs == 64 and dy0.off == 0
             lib = _lib.load()
@@ -722,11 +825,19 @@ class STFProgram(Program):
         S.dpk_parts = []
         return dx
 
-    def _pk_fusion_backward(self, S, k, de: Feat, gv):
+    def _pk_fusion_backward(self, S, k, de: Feat, gv, need):
+        """``de``: lstm k's d x_t = the gradient of pk_fusion k's output.  Its weight / bias gradients
+        (``need.need_w``) and, if the encoder below or the input wants it (``need.need_din``), the
+        gradient of its input [layer output | PK maps]; returns the layer-output part or None."""
+        if de is None or not (need.need_w or need.need_din):
+            return None
         fus = getattr(self.m, f"pk_fusion{k + 1}")
         pkb = S.pkbuf[k]
-        nhwc.wgrad_padded(de, pkb, 1, 1, 1, 0, gv(fus.weight), fus.in_channels)
-        nhwc.channel_sum(de, gv(fus.bias))
+        if need.need_w:
+            nhwc.wgrad_padded(de, pkb, 1, 1, 1, 0, gv(fus.weight), fus.in_channels)
+            nhwc.channel_sum(de, gv(fus.bias))
+        if not need.need_din:
+            return None
         dpk = new_feat(pkb.N, pkb.H, pkb.W, pkb.C, de.buf.device)
         nhwc.conv_dgrad(de, nhwc.pad_weight(fus.weight, pkb.C), dpk, 1, 1, 1, 0, cache=False)
         if self.want_dx:                  # the resized PK maps' share, for _input_grad
