@@ -16,9 +16,10 @@ import torch
 
 from conftest import GOLDEN
 
-# Every entry of igemm.hip's VARIANTS table that a launch can select without an environment
-# override; the signatures must reach each of them.  Not listed: the two 128 x 256 'F' tile entries
-# (STF_IGEMM_CFG=F only) and the three STF_HALO_DIAG timing entries (STF_ABLATION=1 only).
+# Every entry of the igemm variant table (one slice per csrc/igemm_*.hip) that a launch can select
+# without an environment override; the signatures must reach each of them.  Not listed: the two
+# 128 x 256 'F' tile entries (STF_IGEMM_CFG=F only).  The three DIAG timing entries of the 16 x 32
+# halo kernel are not in the shipped table (a -DHALO_DIAG build only).
 DMA_A, DMA_B, DMA_C = "128, 128, 2, 2, 32, 4", "256, 128, 4, 2, 64, 3", "256, 256, 2, 4, 64, 2"
 DMA_D, DMA_E = "512, 64, 8, 1, 64, 2", "256, 64, 4, 1, 32, 4"
 REACHABLE = (

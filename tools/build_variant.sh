@@ -6,11 +6,11 @@ set -e
 name=$1; flags=$2
 root=$(cd "$(dirname "$0")/.." && pwd)
 tmp=$(mktemp -d /tmp/stfvar.XXXX)
-mkdir -p "$tmp/csrc" "$tmp/stfunet" "$tmp/include" "$root/abvar_$name"
-cp "$root"/stf-unet_amd/csrc/*.hip "$root"/stf-unet_amd/csrc/*.h "$root"/stf-unet_amd/csrc/Makefile "$tmp/csrc/"
-mkdir -p "$tmp/../include" 2>/dev/null || true
-sed -i "s#../../include/stfunet.h#$root/include/stfunet.h#" "$tmp"/csrc/*.hip "$tmp"/csrc/*.h
-make -C "$tmp/csrc" -j8 "CXXFLAGS=--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable $flags" ../stfunet/libstfunet_hip.so > "$tmp/build.log" 2>&1 || { tail -20 "$tmp/build.log"; exit 1; }
-cp "$tmp/stfunet/libstfunet_hip.so" "$root/abvar_$name/"
+# the same layout as the repository, so the sources' relative includes and the Makefile's paths hold
+mkdir -p "$tmp/stf-unet_amd/csrc" "$tmp/stf-unet_amd/stfunet" "$tmp/include" "$root/abvar_$name"
+cp "$root"/stf-unet_amd/csrc/*.hip "$root"/stf-unet_amd/csrc/*.h "$root"/stf-unet_amd/csrc/Makefile "$tmp/stf-unet_amd/csrc/"
+cp "$root/include/stfunet.h" "$tmp/include/"
+make -C "$tmp/stf-unet_amd/csrc" -j8 "CXXFLAGS=--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable $flags" ../stfunet/libstfunet_hip.so > "$tmp/build.log" 2>&1 || { tail -20 "$tmp/build.log"; exit 1; }
+cp "$tmp/stf-unet_amd/stfunet/libstfunet_hip.so" "$root/abvar_$name/"
 rm -rf "$tmp"
 echo "built abvar_$name/libstfunet_hip.so ($flags)"

@@ -1,12 +1,16 @@
 """Where the halo conv kernel's time goes: cycle buckets per wave from the DIAG=4
 build (s_memtime around the DMA wait, the stage barrier, the DMA issue, the nine
-taps' MFMAs and the epilogue), summed over all waves of one launch.
-    python tools/halo_timeline.py [H CIN COUT [B]]      (default: 256 64 64 64)"""
+taps' MFMAs and the epilogue), summed over all waves of one launch.  The shipped
+library has no DIAG kernels: make the timing-only build first (its results are wrong),
+    bash tools/build_variant.sh halo_diag4 -DHALO_DIAG=4
+    python tools/halo_timeline.py [H CIN COUT [B]]      (default: 256 64 64 64)
+STF_LIB, when set, names another such build."""
 import os
 import sys
-os.environ["STF_HALO_DIAG"] = "4"
-os.environ["STF_ABLATION"] = "1"
 HERE = os.path.dirname(os.path.abspath(__file__))
+os.environ.setdefault("STF_LIB", os.path.join(os.path.dirname(HERE), "abvar_halo_diag4", "libstfunet_hip.so"))
+if not os.path.isfile(os.environ["STF_LIB"]):
+    sys.exit(f"no HALO_DIAG=4 build at {os.environ['STF_LIB']}: bash tools/build_variant.sh halo_diag4 -DHALO_DIAG=4")
 sys.path[:0] = [os.path.dirname(HERE), os.path.join(os.path.dirname(HERE), "stf-unet_amd")]
 import torch
 from stfunet import nhwc
