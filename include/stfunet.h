@@ -349,6 +349,51 @@ int stf_adamw_amp(float* p, const float* g, float* m, float* v, int64_t n, float
                   const float* grad_scale, const float* found_inf, float beta1, float beta2, float eps,
                   float weight_decay, stf_stream_t stream);
 
+/* Gradient clipping by the global L2 norm, on the flat fp32 gradient buffer
+ * (torch.nn.utils.clip_grad_norm_, norm_type 2).  A segment is `len` elements at element
+ * offset `off` of the buffer: off >= 0 and a multiple of 4 (FlatParams alignment; the buffer
+ * itself 16-B aligned), len >= 0 and arbitrary.  Only elements inside a segment are read or
+ * written: the padding between parameters and the slices of frozen parameters stay out.
+ * Every call takes the table twice: `segs` in DEVICE memory, which the kernels read, and
+ * `segs_host`, the same `count` entries in host memory, which the call checks and sizes its
+ * grid from before it returns (build both once per parameter set). */
+typedef struct stf_seg {
+  int64_t off;
+  int64_t len;
+} stf_seg;
+/* out[0] = the norm of the segments' elements times 1 / *grad_scale (DEVICE; NULL: already
+ *          unscaled), i.e. the norm of the unscaled gradient;
+ * out[1] = the clip coefficient min(1, max_norm / (out[0] + 1e-6)), torch's fp32 arithmetic;
+ * out[2] = 1.0 if out[0] is not finite, else 0.0;  out[3] = 0 (reserved).
+ * Two launches: a streaming pass (one row of `partial` per workgroup; a fixed assignment of
+ * elements to workgroups, no atomics) and a one-workgroup fold in row order, so `out` and
+ * `partial` are the same bits from run to run.  Squares and sums are in double: no fp32 input
+ * overflows or flushes the sum, whatever loss scale it carries, and out[0] is within 1 ulp of
+ * the fp32 rounding of the exact norm.  partial = stf_grad_norm_rows(n) doubles, n >= the
+ * table's total length (host-only query; never more than 2048).
+ * STF_EINVAL, nothing launched: a NULL pointer other than grad_scale, count < 1, a negative
+ * length, an offset that is negative or not a multiple of 4, max_norm NaN or <= 0. */
+int stf_grad_norm_rows(int64_t n);
+int stf_grad_norm(const float* buf, const stf_seg* segs, const stf_seg* segs_host, int count,
+                  const float* grad_scale, float max_norm, double* partial, float* out,
+                  stf_stream_t stream);
+/* buf[e] *= clip[1] for every element e of the segments, in place, one launch (clip = the out
+ * of stf_grad_norm; a coefficient of exactly 1 writes nothing).  Same argument checks. */
+int stf_grad_scale(float* buf, const stf_seg* segs, const stf_seg* segs_host, int count,
+                   const float* clip, stf_stream_t stream);
+/* stf_adamw_amp with the clip folded into the update: clip = the out of stf_grad_norm over
+ * this gradient.  The gradient enters as (g * (1 / *grad_scale)) * clip[1] -- two fp32
+ * multiplications in this order (the first one only when grad_scale is given), the same bits
+ * as stf_grad_scale on an unscaled buffer followed by the unclipped update; g itself is not
+ * modified.  The update is skipped, and hyper[1] left unchanged, when *found_inf != 0
+ * (found_inf may be NULL) OR clip[2] != 0: a step whose gradient norm is not finite is
+ * skipped, not applied as NaN -- a deliberate difference from torch's
+ * clip_grad_norm_(error_if_nonfinite=False) followed by step().  With clip = {., 1, 0, 0} and
+ * no scale the update is stf_adamw_dev's bit for bit (the same kernel body). */
+int stf_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, float* hyper,
+                   const float* grad_scale, const float* found_inf, const float* clip, float beta1,
+                   float beta2, float eps, float weight_decay, stf_stream_t stream);
+
 /* ---------------------------------------------------------------- layout
  * x [N][C][H][W] fp32 -> NHWC bf16 with Cpad (>= C, multiple of 8) channels,
  * zero-filled (preprocess_input output, train_and_eval.py:9-22). */

@@ -266,19 +266,32 @@ long grid_for(long units, long cap) {
 // and are multiplied by 1/*gscale in fp32 -- GradScaler.unscale_'s arithmetic, exact for
 // its power-of-two scales; *finf != 0 (an inf/nan gradient) skips the whole update, like
 // torch's fused AdamW under GradScaler, with no host synchronisation.
-__global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                 float* __restrict__ v, long n, const float* __restrict__ hyper, float b1, float b2,
-                                 float eps, float wd, const float* __restrict__ gscale,
-                                 const float* __restrict__ finf) {
+// Clipped variant (stf_adamw_clip): clip = the out[4] of stf_grad_norm.  The gradient enters as
+// g * (1/scale) * coef, two fp32 multiplications in that order (the second one never contracted
+// into the moment update's subtraction, so a gradient scaled in memory by stf_grad_scale gives the
+// same bits); clip[2] != 0 (a non-finite norm) skips the update like *finf.
+STF_DEV float mul_exact(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+
+template <bool CLIP>
+STF_DEV void adamw_dev_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                            float* __restrict__ v, long n, const float* __restrict__ hyper, float b1, float b2,
+                            float eps, float wd, const float* __restrict__ gscale, const float* __restrict__ finf,
+                            const float* __restrict__ clip) {
   if (finf && finf[0] != 0.f) return;
+  if (CLIP && clip[2] != 0.f) return;
   const float inv = gscale ? 1.f / gscale[0] : 1.f;
+  const float coef = CLIP ? clip[1] : 1.f;
   const float lr = hyper[0];
   const double step = hyper[1];
   const float bc1 = (float)(1.0 - pow((double)b1, step)), bc2 = (float)(1.0 - pow((double)b2, step));
   const float step_size = lr / bc1, inv_sqrt_bc2 = 1.f / sqrtf(bc2);
   for (long i = blockIdx.x * (long)NT + threadIdx.x; i < n; i += (long)gridDim.x * NT) {
     float pp = p[i] * (1.f - lr * wd);
-    const float gg = gscale ? g[i] * inv : g[i];
+    float gg = gscale ? g[i] * inv : g[i];
+    if (CLIP) gg = mul_exact(gg, coef);
     const float mm = m[i] + (1.f - b1) * (gg - m[i]);
     const float ww = b2 * v[i] + (1.f - b2) * gg * gg;
     pp -= step_size * mm / (sqrtf(ww) * inv_sqrt_bc2 + eps);
@@ -288,9 +301,28 @@ __global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict_
   }
 }
 
+__global__ void adamw_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                 float* __restrict__ v, long n, const float* __restrict__ hyper, float b1, float b2,
+                                 float eps, float wd, const float* __restrict__ gscale,
+                                 const float* __restrict__ finf) {
+  adamw_dev_body<false>(p, g, m, v, n, hyper, b1, b2, eps, wd, gscale, finf, nullptr);
+}
+
+__global__ void adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                  float* __restrict__ v, long n, const float* __restrict__ hyper, float b1, float b2,
+                                  float eps, float wd, const float* __restrict__ gscale,
+                                  const float* __restrict__ finf, const float* __restrict__ clip) {
+  adamw_dev_body<true>(p, g, m, v, n, hyper, b1, b2, eps, wd, gscale, finf, clip);
+}
+
 // the device step count advances unless the update is skipped (one lane; vector stores)
 __global__ void adamw_amp_step_kernel(float* __restrict__ hyper, const float* __restrict__ finf) {
   if (threadIdx.x == 0 && !(finf && finf[0] != 0.f)) hyper[1] += 1.f;
+}
+
+__global__ void adamw_clip_step_kernel(float* __restrict__ hyper, const float* __restrict__ finf,
+                                       const float* __restrict__ clip) {
+  if (threadIdx.x == 0 && !(finf && finf[0] != 0.f) && !(clip[2] != 0.f)) hyper[1] += 1.f;
 }
 
 extern "C" int stf_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, const float* hyper, float beta1,
@@ -312,6 +344,20 @@ extern "C" int stf_adamw_amp(float* p, const float* g, float* m, float* v, int64
   if (n == 0) return 0;
   hipLaunchKernelGGL(adamw_dev_kernel, dim3(grid_for(n, 4096)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, (long)n,
                      hyper, beta1, beta2, eps, weight_decay, grad_scale, found_inf);
+  STF_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stf_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, float* hyper,
+                              const float* grad_scale, const float* found_inf, const float* clip, float beta1,
+                              float beta2, float eps, float weight_decay, stf_stream_t stream) {
+  if (n < 0 || !hyper || !clip) return STF_EINVAL;
+  if (n > 0 && (!p || !g || !m || !v)) return STF_EINVAL;
+  hipLaunchKernelGGL(adamw_clip_step_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, hyper, found_inf, clip);
+  STF_CHECK_LAUNCH();
+  if (n == 0) return 0;
+  hipLaunchKernelGGL(adamw_clip_kernel, dim3(grid_for(n, 4096)), dim3(NT), 0, (hipStream_t)stream, p, g, m, v, (long)n,
+                     hyper, beta1, beta2, eps, weight_decay, grad_scale, found_inf, clip);
   STF_CHECK_LAUNCH();
   return 0;
 }

@@ -8,10 +8,11 @@ kernels through the C ABI in ``include/stfunet.h``.
 from . import _lib  # noqa: F401
 from . import predict  # noqa: F401  (the module; its loop is stfunet.predict.predict)
 from .loss import criterion  # noqa: F401
+from .optim import clip_grad_norm_  # noqa: F401
 from .predict import image_metrics, overlay, predict_masks  # noqa: F401
 from .resize import upsample_logits  # noqa: F401
 from .stf_lstm_unet import STFLSTMUNet  # noqa: F401
 from .unet import UNet  # noqa: F401
 
-__all__ = ["STFLSTMUNet", "UNet", "criterion", "image_metrics", "overlay", "predict", "predict_masks",
+__all__ = ["STFLSTMUNet", "UNet", "clip_grad_norm_", "criterion", "image_metrics", "overlay", "predict", "predict_masks",
            "upsample_logits"]

@@ -104,6 +104,11 @@ class WgradArgs(ctypes.Structure):
                 ("ws", P), ("splits", c_int), ("grid_blocks", c_int)]
 
 
+class Seg(ctypes.Structure):
+    """stf_seg: ``len`` elements at element offset ``off`` of a flat fp32 buffer."""
+    _fields_ = [("off", c_int64), ("len", c_int64)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "stf_igemm_stat_tiles": (c_int, [ctypes.POINTER(IgemmArgs)]),
@@ -145,6 +150,10 @@ _SIGS = {
                           P]),
     "stf_adamw_dev": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, P]),
     "stf_adamw_amp": (c_int, [P, P, P, P, c_int64, P, P, P, c_float, c_float, c_float, c_float, P]),
+    "stf_grad_norm_rows": (c_int, [c_int64]),
+    "stf_grad_norm": (c_int, [P, P, P, c_int, P, c_float, P, P, P]),
+    "stf_grad_scale": (c_int, [P, P, P, c_int, P, P]),
+    "stf_adamw_clip": (c_int, [P, P, P, P, c_int64, P, P, P, P, c_float, c_float, c_float, c_float, P]),
     "stf_pack_input": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "stf_pack_weight": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "stf_pack_weights": (c_int, [P, c_int, c_int64, P]),

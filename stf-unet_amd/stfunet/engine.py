@@ -312,10 +312,35 @@ def evaluate(model, data_loader, device, num_classes):
 
 
 def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler=None,
-                    print_freq=10, scaler=None, *, loss_weight=None, dice=True, ignore_index=-100):
+                    print_freq=10, scaler=None, *, loss_weight=None, dice=True, ignore_index=-100,
+                    max_grad_norm=None):
     """The reference's loop (its positional signature and defaults); the keyword-only
     ``loss_weight`` / ``dice`` / ``ignore_index`` go to ``criterion`` (``ignore_index=255`` for
-    batches whose targets ``collate_fn`` padded to a common size)."""
+    batches whose targets ``collate_fn`` padded to a common size).
+
+    ``max_grad_norm`` (an addition; ``None``: the loop as it was): clip every step's gradients by
+    their global L2 norm.  A ``stfunet.optim.AdamW`` gets it as its param-group option for the epoch
+    (the clip runs inside the update, no ``unscale_``; the previous value is put back at the end);
+    any other optimizer gets ``scaler.unscale_`` and ``stfunet.optim.clip_grad_norm_`` before its
+    step.  The logger gains a ``grad_norm`` meter, read in the same host read as the loss."""
+    from .optim import AdamW, clip_grad_norm_
+    fused_clip = max_grad_norm is not None and isinstance(optimizer, AdamW)
+    if fused_clip:
+        previous = [group.get("max_grad_norm") for group in optimizer.param_groups]
+        for group in optimizer.param_groups:
+            group["max_grad_norm"] = max_grad_norm
+    try:
+        return _train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler,
+                                print_freq, scaler, loss_weight, dice, ignore_index, max_grad_norm, fused_clip,
+                                clip_grad_norm_)
+    finally:
+        if fused_clip:
+            for group, value in zip(optimizer.param_groups, previous):
+                group["max_grad_norm"] = value
+
+
+def _train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler, print_freq, scaler,
+                     loss_weight, dice, ignore_index, max_grad_norm, fused_clip, clip_grad_norm_):
     model.train()
     logger = MetricLogger(delimiter="  ")
     logger.add_meter("lr", SmoothedValue(window_size=1, fmt="{value:.6f}"))
@@ -329,16 +354,28 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
             loss = criterion(model(image), target, loss_weight=loss_weight, num_classes=num_classes, dice=dice,
                              ignore_index=ignore_index)
         optimizer.zero_grad()
+        grad_norm = None
         if scaler is not None:
             scaler.scale(loss).backward()
+            if max_grad_norm is not None and not fused_clip:
+                scaler.unscale_(optimizer)
+                grad_norm = clip_grad_norm_([p for g in optimizer.param_groups for p in g["params"]], max_grad_norm)
             scaler.step(optimizer)
             scaler.update()
         else:
             loss.backward()
+            if max_grad_norm is not None and not fused_clip:
+                grad_norm = clip_grad_norm_([p for g in optimizer.param_groups for p in g["params"]], max_grad_norm)
             optimizer.step()
         lr_scheduler.step()
         lr = optimizer.param_groups[0]["lr"]
-        logger.update(loss=loss.item(), lr=lr)
+        if max_grad_norm is None:
+            logger.update(loss=loss.item(), lr=lr)
+        else:       # one host read for both scalars
+            if fused_clip:
+                grad_norm = optimizer.grad_norm
+            loss_v, norm_v = torch.stack([loss.detach().float().reshape(()), grad_norm.to(loss.device)]).tolist()
+            logger.update(loss=loss_v, grad_norm=norm_v, lr=lr)
     # the epoch's last steps: a device-side failure flag (cooperative LSTM hand-off timeout)
     # raises here instead of at the next epoch's first step
     # (through a DistributedDataParallel-style wrapper's .module as well)

@@ -21,6 +21,29 @@ def _align4(n):
     return (n + 3) & ~3
 
 
+def grad_segments(offsets, numels, selected):
+    """``[(offset, length), ...]`` in elements: what a pass over the gradients of the selected
+    parameters may touch in a flat buffer laid out like ``FlatParams`` (parameter ``i`` at
+    ``offsets[i]``, a multiple of 4).  One segment per selected parameter; a neighbour is merged
+    into the segment before it only when that one ended on a parameter whose ``numel`` is a
+    multiple of 4 and the two touch, so no segment spans padding, and an unselected parameter
+    (frozen, or without a gradient) always splits a run."""
+    segs = []
+    mergeable = False
+    for off, n, sel in zip(offsets, numels, selected):
+        if not sel:
+            mergeable = False
+            continue
+        if n == 0:
+            continue
+        if mergeable and segs[-1][0] + segs[-1][1] == off:
+            segs[-1][1] += n
+        else:
+            segs.append([off, n])
+        mergeable = n % 4 == 0
+    return [tuple(s) for s in segs]
+
+
 class FlatParams:
     def __init__(self, module):
         self.module = module
