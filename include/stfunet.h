@@ -637,6 +637,30 @@ int stf_predict_overlay(const float* frames, int64_t batch_stride, const uint8_t
                         int W, int c0, int c1, int c2, float alpha, int paint, uint8_t* out,
                         void* scratch, stf_stream_t stream);
 
+/* ---------------------------------------------------------------- boundary metrics
+ * Per-image Hausdorff distance, its 95th percentile and the average symmetric surface distance of
+ * two binary masks, as MedPy's hd / hd95 / assd define them at unit pixel spacing (INTEGRATION.md
+ * 2.2 states the definition), and the exact squared Euclidean distance transform underneath.
+ * Additive to ABI v17.  Limits: 1 <= B, 1 <= H, W <= 4096, B * H * W < 2^31 (so d2 < 2^25).
+ * STF_EINVAL (nothing launched) for a NULL required pointer, a size outside the limits, a scratch,
+ * out, counts or target that is not 8-byte aligned or a d2 that is not 4-byte aligned.  No entry
+ * point allocates or reads back; results are the same bits from run to run.
+ *
+ * Bytes of the scratch either call needs for B images of H x W pixels, a multiple of 8 (0 outside
+ * the limits). */
+size_t stf_boundary_scratch_bytes(int B, int H, int W);
+/* mask uint8 [B][H][W] (nonzero = predicted foreground), target int64 [B][H][W] (> 0 = foreground),
+ * ignore as in stf_predict_mask.  out double [B][3] = {hd, hd95, assd} (NaN x3 when either border is
+ * empty), counts int64 [B][2] = {|dP|, |dT|}; both OVERWRITTEN, may arrive uninitialised. */
+int stf_boundary_metrics(const uint8_t* mask, const int64_t* target, int B, int H, int W, int64_t ignore,
+                         double* out, int64_t* counts, void* scratch, stf_stream_t stream);
+/* Squared distance of every pixel to the nearest nonzero pixel of sites (uint8 [B][H][W]) as int32
+ * [B][H][W]; an image without sites gets INT32_MAX everywhere.  where (uint8, may be NULL): compute
+ * only where it is nonzero, write -1 elsewhere.  The same row / column kernels as above.  The cost
+ * per computed pixel grows with the distance found (an outward scan along the column). */
+int stf_edt_sq(const uint8_t* sites, const uint8_t* where, int B, int H, int W, int32_t* d2,
+               void* scratch, stf_stream_t stream);
+
 /* ---------------------------------------------------------------- PK maps (extended Tofts)
  * pk_fitting.py ToftsModelFitter, all fp32.  The host builds
  * the reference's constant tables exactly as the reference does (pk_fitting.py:

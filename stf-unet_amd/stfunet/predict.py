@@ -7,6 +7,9 @@ gfx950 kernels of ``csrc/predict.hip``:
   or the argmax ``evaluate`` scores) and, with a target, the per-image (|P&T|, |P|, |T|) counts
 * ``image_metrics``   counts -> per-image Dice and IoU (``compute_metrics``,
   train_utils/visualize.py:9-50), on the device, no host synchronisation
+* ``boundary_metrics``  per-image Hausdorff distance, HD95 and ASSD of mask against target
+  (MedPy's ``hd`` / ``hd95`` / ``assd`` at isotropic spacing; ``csrc/boundary.hip``), and
+  ``distance_transform_sq``, the exact squared Euclidean distance transform underneath
 * ``overlay``         the mask painted over a frame (``save_overlay_from_tensor``, test.py:52-82,
   through ``merge_images``, train_utils/merge_tumor_images.py:94-120)
 * ``predict``         the loop: eval mode, ``no_grad``, ``preprocess_input``, forward, masks,
@@ -19,6 +22,7 @@ triple to cv2 as B, G, R.  The default colour (0, 255, 0) reads the same both wa
 
 There is no CPU path: tensors on the host raise.
 """
+import numbers
 import os
 
 import torch
@@ -28,6 +32,9 @@ from .nhwc import _p
 
 RULES = {"argmax": 0, "sigmoid": 1}
 MAX_CLASSES = 16
+MAX_SIDE = 4096                  # boundary metrics / distance transform: 1 <= H, W <= 4096
+MAX_PIXELS = 1 << 31             # ... and B * H * W below this
+MAX_FULL_SCAN = 1 << 32          # distance_transform_sq without `where`: B * H * W * H at most this
 
 
 def _device_only(t, what):
@@ -89,6 +96,108 @@ def image_metrics(counts, smooth=1e-5):
     return (2 * inter + smooth) / (p + t + smooth), (inter + smooth) / (p + t - inter + smooth)
 
 
+def _as_u8(t, what):
+    """``t`` as a contiguous uint8 tensor, nonzero where ``t`` is (bool and uint8 are not copied)."""
+    if t.dtype.is_floating_point or t.dtype.is_complex:
+        raise ValueError(f"{what} must be bool or an integer tensor, not {t.dtype}")
+    if t.dtype == torch.bool:
+        t = t.view(torch.uint8)
+    elif t.dtype != torch.uint8:
+        t = (t != 0).view(torch.uint8)
+    return t.contiguous()
+
+
+def _check_bhw(t, what):
+    if t.dim() != 3:
+        raise ValueError(f"{what} must be [B, H, W], not {tuple(t.shape)}")
+    B, H, W = t.shape
+    if B and not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f"{what}: H and W must be in 1..{MAX_SIDE}, not {H} x {W}")
+    if B * H * W >= MAX_PIXELS:
+        raise ValueError(f"{what}: B * H * W must be below 2^31, not {B * H * W}")
+    return B, H, W
+
+
+def _check_spacing(spacing):
+    if isinstance(spacing, bool) or not isinstance(spacing, numbers.Real) or not 0.0 < spacing < float("inf"):
+        raise ValueError(f"spacing must be a finite positive number, not {spacing!r}")
+    return float(spacing)
+
+
+def _boundary_scratch(B, H, W, device):
+    """The scratch of the boundary entry points: whole 8-byte words, never fewer bytes than they ask for."""
+    nbytes = load().stf_boundary_scratch_bytes(B, H, W)
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def boundary_metrics(mask, target, ignore_index=None, spacing=1.0):
+    """Per-image boundary metrics of ``mask`` against ``target`` (both ``[B, H, W]``; ``mask`` bool,
+    uint8 or any integer, nonzero = foreground; ``target`` any integer, > 0 = foreground; pixels
+    whose target equals ``ignore_index`` are background on both sides).
+
+    Returns ``{"hd", "hd95", "assd"}`` as float64 ``[B]`` device tensors and ``border_counts``
+    int64 ``[B, 2]`` = (|dP|, |dT|).  The border of M is ``M & ~erode(M)`` with the 4-neighbour
+    cross and background outside the image; distances are Euclidean between border pixels in both
+    directions, times ``spacing``: HD their maximum, HD95 numpy's linear 95th percentile of all of
+    them, ASSD half the sum of the two directions' means (MedPy's hd / hd95 / assd).  An image
+    with an empty mask or target gets NaN in all three."""
+    if tuple(mask.shape) != tuple(target.shape):
+        raise ValueError(f"target {tuple(target.shape)} does not match the mask's {tuple(mask.shape)}")
+    B, H, W = _check_bhw(mask, "mask")
+    spacing = _check_spacing(spacing)
+    if target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
+        raise ValueError(f"target must be an integer tensor, not {target.dtype}")
+    mask = _as_u8(mask.detach(), "mask")
+    _device_only(mask, "boundary_metrics")
+    _device_only(target, "boundary_metrics")
+    dev = mask.device
+    out = torch.empty((B, 3), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, 2), dtype=torch.int64, device=dev)
+    if B:
+        target = target.detach().to(device=dev, dtype=torch.int64).contiguous()
+        scratch = _boundary_scratch(B, H, W, dev)
+        with torch.cuda.device(dev):
+            call("stf_boundary_metrics", _p(mask), _p(target), B, H, W, -1 if ignore_index is None else ignore_index,
+                 _p(out), _p(counts), _p(scratch), stream())
+        if spacing != 1.0:
+            out = out * spacing
+    hd, hd95, assd = out.unbind(1)
+    return {"hd": hd, "hd95": hd95, "assd": assd, "border_counts": counts}
+
+
+def distance_transform_sq(sites, where=None):
+    """int32 ``[B, H, W]``: the exact squared Euclidean distance of every pixel to the nearest
+    nonzero pixel of ``sites`` (bool or integer ``[B, H, W]``); ``INT32_MAX`` everywhere in an image
+    without sites.  With ``where`` (same shape) only its nonzero pixels are computed, the others
+    are -1.
+
+    The column pass scans outward from each computed pixel, so a pixel costs about the distance it
+    finds, at worst H row reads.  Without ``where`` every pixel is computed, and sparse sites in a
+    large image make that one long kernel; such a call is refused (``ValueError``) when its bound
+    ``B * H * W * H`` exceeds ``MAX_FULL_SCAN`` (2^32: a batch of 64 at 256 x 256 is 2^30, one
+    1024 x 1024 image 2^30, one 2048 x 2048 image 2^33).  Passing ``where`` (all ones, if every pixel
+    is wanted) lifts the guard: the caller then owns the cost."""
+    B, H, W = _check_bhw(sites, "sites")
+    if where is not None and tuple(where.shape) != tuple(sites.shape):
+        raise ValueError(f"where {tuple(where.shape)} does not match the sites' {tuple(sites.shape)}")
+    if where is None and B * H * W * H > MAX_FULL_SCAN:
+        raise ValueError(f"distance_transform_sq without `where` may read B * H * W * H = {B * H * W * H} rows "
+                         f"(more than {MAX_FULL_SCAN}) when the sites are sparse; pass `where` to name the pixels "
+                         "that are needed, or all ones to accept the cost")
+    sites = _as_u8(sites.detach(), "sites")
+    _device_only(sites, "distance_transform_sq")
+    if where is not None:
+        where = _as_u8(where.detach(), "where")
+        _device_only(where, "distance_transform_sq")
+        where = where.to(sites.device)
+    d2 = torch.empty((B, H, W), dtype=torch.int32, device=sites.device)
+    if B:
+        scratch = _boundary_scratch(B, H, W, sites.device)
+        with torch.cuda.device(sites.device):
+            call("stf_edt_sq", _p(sites), _p(where), B, H, W, _p(d2), _p(scratch), stream())
+    return d2
+
+
 def overlay(frames, mask, color=(0, 255, 0), alpha=0.5, paint=1):
     """``uint8 [B, H, W, 3]``: ``frames`` normalised to 0..255 per image, with ``color`` blended
     at ``alpha`` into the pixels where the mask is non-zero (``paint=1``) or zero (``paint=0``).
@@ -136,7 +245,8 @@ def shown_frame(inputs):
 
 
 def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5, ignore_index=None,
-            output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5, paint=1, keep_masks=False):
+            output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5, paint=1, keep_masks=False,
+            boundary=False, spacing=1.0):
     """The inference loop of test.py:146-176 for any batch size.
 
     The loader yields ``inputs`` or ``(inputs, targets)`` (targets may be None).  Returns a dict:
@@ -144,25 +254,34 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
     tensors in slice order) with their means ``mean_dice`` / ``mean_iou`` (None otherwise).
     With ``output_dir`` every slice is written as ``{prefix}_{idx}.png`` (RGB, ``idx`` the running
     slice index); that is the loop's only device-to-host copy, one per batch.  ``keep_masks=True``
-    adds ``masks``, the list of each batch's ``uint8 [B, H, W]`` device mask."""
+    adds ``masks``, the list of each batch's ``uint8 [B, H, W]`` device mask.
+    ``boundary=True`` adds, when targets came, ``boundary_metrics`` of every mask against its target:
+    per-image ``hd`` / ``hd95`` / ``assd`` (NaN where the mask or the target is empty), their means
+    over the defined images ``mean_hd`` / ``mean_hd95`` / ``mean_assd`` (NaN when there is none) and
+    ``num_boundary``, the number of defined images -- all device tensors, no host synchronisation."""
     if rule not in RULES:
         raise ValueError(f"unknown rule {rule!r} (one of {sorted(RULES)})")
     color = _check_paint(color, alpha, paint)
+    if boundary:
+        spacing = _check_spacing(spacing)
     from .engine import preprocess_input
     if output_dir is not None:
         from PIL import Image
         os.makedirs(output_dir, exist_ok=True)
     model.eval()
-    all_counts, masks, idx = [], [], 0
+    all_counts, all_boundary, masks, idx = [], [], [], 0
     with torch.no_grad():
         for batch in data_loader:
             inputs, targets = batch if isinstance(batch, (tuple, list)) else (batch, None)
             inputs = preprocess_input(inputs, model).to(device)
             outputs = model(inputs)
             if targets is not None:
-                mask, counts = predict_masks(outputs, rule, channel, threshold, target=targets.to(device),
+                targets = targets.to(device)
+                mask, counts = predict_masks(outputs, rule, channel, threshold, target=targets,
                                              ignore_index=ignore_index)
                 all_counts.append(counts)
+                if boundary:
+                    all_boundary.append(boundary_metrics(mask, targets, ignore_index, spacing))
             else:
                 mask = predict_masks(outputs, rule, channel, threshold)
             if output_dir is not None:
@@ -176,6 +295,12 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
     if all_counts:
         dice, iou = image_metrics(torch.cat(all_counts))
         res.update(dice=dice, iou=iou, mean_dice=dice.mean(), mean_iou=iou.mean())
+    if boundary:
+        for k in ("hd", "hd95", "assd"):
+            v = torch.cat([m[k] for m in all_boundary]) if all_boundary else None
+            res[k] = v
+            res["mean_" + k] = None if v is None else torch.nanmean(v)
+        res["num_boundary"] = None if not all_boundary else (~torch.isnan(res["hd"])).sum()
     if keep_masks:
         res["masks"] = masks
     return res

@@ -11,6 +11,15 @@ overlay reads again (the frame for the blend after the min / max pass, the mask)
 line.
 
     python tools/bench_predict.py [--rule argmax|sigmoid] [--batch 64] [--size 256] [--rounds 7] [--iters 20]
+
+``--boundary`` measures ``stfunet.boundary_metrics`` (csrc/boundary.hip) instead, on two synthetic
+mask regimes at the same shape: ``overlap`` (a blob against itself moved by a few pixels: the column
+scan ends after a few rows) and ``far_apart`` (two small blobs in opposite corners: every border
+pixel scans most of its column, the bad case).  For scale, the same round times ``predict_masks``
+with counts (one kernel) and ``overlay`` (two kernels) on the same shape.  Where scipy imports, the
+host computation a user would otherwise run (mask to the host, ``binary_erosion``,
+``distance_transform_edt``, ``np.percentile`` per slice) is timed on ``--host-images`` images of
+each regime.  Prints one JSON line.
 """
 import argparse
 import json
@@ -30,6 +39,8 @@ ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--size", type=int, default=256)
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--iters", type=int, default=20)
+ap.add_argument("--boundary", action="store_true", help="measure boundary_metrics instead")
+ap.add_argument("--host-images", type=int, default=8, help="images per regime of the scipy host timing")
 args = ap.parse_args()
 if not torch.cuda.is_available():
     sys.exit("bench_predict.py measures on the GPU: no ROCm device found")
@@ -79,6 +90,46 @@ def torch_per_slice():
     return tuple(torch.cat(v) for v in zip(*out))
 
 
+def blobs(regime):
+    """(mask uint8, target int64) [B, H, W]: one disk per image and side, seeded."""
+    g = torch.Generator().manual_seed(1 if regime == "overlap" else 2)
+    yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    P, T = torch.zeros(B, H, W, dtype=torch.uint8), torch.zeros(B, H, W, dtype=torch.int64)
+    for b in range(B):
+        if regime == "overlap":
+            r = int(torch.randint(H // 12, H // 6, (1,), generator=g))
+            cy, cx = (int(v) for v in torch.randint(H // 4, 3 * H // 4, (2,), generator=g))
+            dy, dx = (int(v) for v in torch.randint(-4, 5, (2,), generator=g))
+            py, px, ty, tx = cy + dy, cx + dx, cy, cx
+        else:
+            r = max(2, H // 20)
+            oy, ox = (int(v) for v in torch.randint(0, H // 16 + 1, (2,), generator=g))
+            py, px, ty, tx = r + oy, r + ox, H - 1 - r - oy, W - 1 - r - ox
+        P[b] = ((yy - py) ** 2 + (xx - px) ** 2 <= r * r).to(torch.uint8)
+        T[b] = ((yy - ty) ** 2 + (xx - tx) ** 2 <= r * r).long()
+    return P, T
+
+
+def scipy_host_us(P, T, n):
+    """us per image of the host computation on n images, the device-to-host copy included; None without scipy."""
+    try:
+        import numpy as np
+        from scipy.ndimage import binary_erosion, distance_transform_edt, generate_binary_structure
+    except ImportError:
+        return None
+    import time
+    cross = generate_binary_structure(2, 1)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for b in range(n):
+        p, t = P[b].cpu().numpy().astype(bool), T[b].cpu().numpy() > 0
+        bp, bt = p ^ binary_erosion(p, cross), t ^ binary_erosion(t, cross)
+        if bp.any() and bt.any():
+            a, c = distance_transform_edt(~bt)[bp], distance_transform_edt(~bp)[bt]
+            _ = max(a.max(), c.max()), np.percentile(np.hstack((a, c)), 95), (a.mean() + c.mean()) / 2
+    return (time.perf_counter() - t0) * 1e6 / n
+
+
 def timed(fn, iters):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -88,6 +139,62 @@ def timed(fn, iters):
     torch.cuda.synchronize()
     return a.elapsed_time(b) * 1e3 / iters           # us per call
 
+
+if args.boundary:
+    from stfunet import boundary_metrics
+    data = {k: tuple(t.cuda() for t in blobs(k)) for k in ("overlap", "far_apart")}
+    mask0 = data["overlap"][0]
+    legs = (("boundary_overlap", lambda: boundary_metrics(*data["overlap"])),
+            ("boundary_far_apart", lambda: boundary_metrics(*data["far_apart"])),
+            ("predict_masks_with_counts", lambda: predict_masks(logits, args.rule, 0, 0.5, target=target)),
+            ("overlay", lambda: overlay(frames, mask0, COLOR, ALPHA, PAINT)))
+    for _, fn in legs:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name, _ in legs}
+    for _ in range(args.rounds):
+        for name, fn in legs:
+            us[name].append(timed(fn, args.iters) / B)
+    # the predict loop (UNet, two batches of B) without and with boundary=True, interleaved: without
+    # the flag the loop issues the launches it issued before the option existed
+    import time
+    from stfunet.predict import predict
+    from stfunet.unet import UNet
+    model = UNet(in_channels=8, num_classes=2).cuda()
+    loader = [(inputs.view(B, 1, 8, H, W), data[k][1]) for k in ("overlap", "far_apart")]
+
+    def loop_ms(flag):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        predict(model, loader, torch.device("cuda"), boundary=flag)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for flag in (False, True, False, True):
+        loop_ms(flag)
+    loop = {False: [], True: []}
+    for _ in range(args.rounds):
+        for flag in (False, True):
+            loop[flag].append(loop_ms(flag))
+    loop_med = {k: statistics.median(v) for k, v in loop.items()}
+    res = {k: boundary_metrics(*v) for k, v in data.items()}
+    host = {k: scipy_host_us(*v, min(B, args.host_images)) for k, v in data.items()}
+    med = {k: statistics.median(v) for k, v in us.items()}
+    print(json.dumps({
+        "tool": "bench_predict", "leg": "boundary", "shape": [B, H, W], "rounds": args.rounds, "iters": args.iters,
+        "us_per_image": {k: round(v, 3) for k, v in med.items()},
+        "us_per_image_min_max": {k: [round(min(v), 3), round(max(v), 3)] for k, v in us.items()},
+        "far_apart_over_overlap": round(med["boundary_far_apart"] / med["boundary_overlap"], 2),
+        "mean_hd95": {k: float(torch.nanmean(v["hd95"])) for k, v in res.items()},
+        "mean_border_pixels": {k: float(v["border_counts"].double().mean()) for k, v in res.items()},
+        "scipy_host_us_per_image": {k: None if v is None else round(v, 1) for k, v in host.items()},
+        "predict_loop_ms": {"images": 2 * B, "plain": round(loop_med[False], 3), "boundary": round(loop_med[True], 3),
+                            "plain_min_max": [round(min(loop[False]), 3), round(max(loop[False]), 3)],
+                            "boundary_min_max": [round(min(loop[True]), 3), round(max(loop[True]), 3)],
+                            "added_us_per_image": round((loop_med[True] - loop_med[False]) * 1e3 / (2 * B), 2)},
+    }))
+    sys.exit(0)
 
 paths = (("device", device_path, args.iters), ("torch_batched", torch_batched, args.iters),
          ("torch_per_slice", torch_per_slice, max(1, args.iters // 10)))
