@@ -166,7 +166,6 @@ _SIGS = {
     "stf_lstm_coop_sync_bytes": (c_size_t, [c_int, c_int]),
     "stf_lstm_coop_supported": (c_int, [c_int]),
     "stf_lstm_coop_fwd": (c_int, [P, P, P, c_int, c_int, c_int, P, P, c_int, P, P, c_int, c_uint, P]),
-    "stf_lstm_coop_bwd": (c_int, [P, P, P, c_int, c_int, c_int, P, c_int, P, P, c_int, P, c_int, c_uint, P]),
     "stf_lstm_coop_error": (c_int, [P, c_int, c_int, P, P]),
     "stf_bilinear_ac_fwd": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P]),
     "stf_bilinear_ac_bwd": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int, c_int, c_int, P]),

@@ -32,6 +32,7 @@ function and block steps of program.py):
     whose backward will not run.
 """
 import os
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -160,6 +161,57 @@ class ResBlockProgram:
         return dsrc
 
 
+class LstmRoute(NamedTuple):
+    """Which launches run one LSTM.
+
+    ``fwd``: "seq" (stf_lstm_seq_fwd, all T steps in one launch, C = 64), "coop" (stf_lstm_coop_fwd,
+    one persistent launch, C = 128 / 256 / 512) or "step" (T GEMMs with the cell update in their
+    epilogue).  ``bwd``: "seq" (stf_lstm_seq_bwd), or the per-step loop with its cell backward from
+    the "gates" the cooperative forward kept or from a "recompute" of step t's gates (the forward's
+    GEMM).  ``hoist`` (per-step backwards): d x for all T steps as one GEMM after the loop, per step
+    only dh_{t-1}; False = one [dx | dh] GEMM per step.  The non-default routes are the oracles of
+    the bitwise tests."""
+    fwd: str
+    bwd: str
+    hoist: bool = True
+
+
+# hidden sizes that take the cooperative forward by default: lstm4 only (the main-stream LSTM).
+# Measured (same box, cfg3, round 3): coop forward of lstm4 +1.0 %; coop lstm2 / lstm3 on their side
+# streams -0.5..-4 % (a launch that needs its whole group resident spins on CUs the encoder needs)
+LSTM_COOP = frozenset({512})
+# workgroup budget of a cooperative launch on a side stream (lstm1-3); lstm4 gets the whole chip
+LSTM_SIDE_WG = 64
+
+
+def lstm_route(C, lbuf_off, lbuf_cs, hT_cs, hT_ptr, need_bwd=True, coop=LSTM_COOP, forced=None):
+    """The route of an LSTM of hidden size ``C`` over an [x | h] buffer of channel offset / stride
+    ``lbuf_off`` / ``lbuf_cs`` whose h_T goes to address ``hT_ptr``, channel stride ``hT_cs``.
+
+    Default: "seq" where the sequence kernel takes this C and layout, else "coop" for C in ``coop``
+    where the cooperative kernel does (it keeps its gates for the backward if ``need_bwd``), else
+    "step" with gate recompute; the per-step backwards hoist.  ``forced``: that LstmRoute instead,
+    ValueError if this C or layout cannot run it ("seq" has no hoist: fixed to True there)."""
+    lib = _lib.load()
+    packed = lbuf_off == 0 and lbuf_cs == 2 * C and hT_cs >= C
+    seq_ok = packed and bool(lib.stf_lstm_seq_supported(C))
+    coop_ok = packed and bool(lib.stf_lstm_coop_supported(C)) and hT_cs % 8 == 0 and hT_ptr % 16 == 0
+    if forced is None:
+        if seq_ok:
+            return LstmRoute("seq", "seq")
+        if C in coop and coop_ok:
+            return LstmRoute("coop", "gates" if need_bwd else "recompute")
+        return LstmRoute("step", "recompute")
+    fwd, bwd, hoist = forced
+    if fwd not in ("seq", "coop", "step") or bwd not in ("seq", "gates", "recompute"):
+        raise ValueError(f"{forced}: no such LSTM route")
+    if (fwd == "seq" and not seq_ok) or (fwd == "coop" and not coop_ok):
+        raise ValueError(f"{forced}: no {fwd!r} forward at C = {C} with this layout")
+    if (bwd == "seq") != (fwd == "seq") or (bwd == "gates" and fwd != "coop"):
+        raise ValueError(f"{forced}: a {bwd!r} backward cannot follow a {fwd!r} forward")
+    return LstmRoute(fwd, bwd, True if bwd == "seq" else bool(hoist))
+
+
 class LSTMProgram:
     """nn.LSTM(C, C) over T steps for every pixel, only h_T kept (src/stf_lstm_unet.py:214-242).
 
@@ -169,13 +221,15 @@ class LSTMProgram:
     rows and h_T in ``hT`` (e.g. the decoder's concat slice).  Only the cell states
     c_t (fp32) are kept for the backward: each backward step reruns step t's GEMM on
     the same rows (same kernel, bitwise the forward's gates) with the cell backward in
-    its epilogue, instead of storing T x P x 4C fp32 activated gates.
+    its epilogue, instead of storing T x P x 4C fp32 activated gates (the cooperative forward
+    does store them).  ``forward`` resolves which launches run (``lstm_route``) once and keeps
+    the answer in its state (``st.route``); ``backward`` follows it.
     """
 
     def __init__(self, lstm, max_wg=0):
         self.lstm = lstm
         self.C = lstm.hidden_size
-        # workgroup budget of the cooperative kernels (one per CU; 0 = the whole chip): an LSTM
+        # workgroup budget of the cooperative forward (one per CU; 0 = the whole chip): an LSTM
         # on a side stream leaves the rest to the encoder / decoder of the main stream
         self.max_wg = max_wg
         # polls before a cooperative hand-off gives up (0 = the library's ~4 s; tests force 1)
@@ -183,32 +237,8 @@ class LSTMProgram:
         # the owning program's sticky device error word (STFProgram.err_word): every cooperative
         # launch ORs its timeout flag into it, the program raises at the next step boundary
         self.err_word = None
-
-    def _note_coop(self, sync, npix, T):
-        self.last_sync = (sync, npix, T)
-        if self.err_word is not None:
-            call("stf_lstm_coop_error", _p(sync), npix, T, _p(self.err_word), stream())
-
-    def fused(self, lbuf: Feat, hT: Feat):
-        """Whole-sequence kernel (stf_lstm_seq_fwd) for this hidden size and layout?
-        STF_LSTM_SEQ=0 keeps the per-step launches (A/B)."""
-        return (os.environ.get("STF_LSTM_SEQ", "1") != "0" and bool(_lib.load().stf_lstm_seq_supported(self.C))
-                and lbuf.off == 0 and lbuf.cs == 2 * self.C and hT.cs >= self.C)
-
-    def coop(self, lbuf: Feat, hT: Feat):
-        """Cooperative whole-sequence forward (stf_lstm_coop_fwd, C = 128 / 256 / 512)?
-        STF_LSTM_COOP: 1 = every supported C, 0 = the per-step launches, or a comma list of
-        hidden sizes ("512", the default: only lstm4, the one on the main stream).
-        STF_LSTM_COOP_BWD=1 also runs the cooperative backward (off by default, see above)."""
-        # default: lstm4 only (the main-stream LSTM).  Measured (same box, cfg3, round 3): coop
-        # forward of lstm4 +1.0 %; coop lstm2 / lstm3 on their side streams -0.5..-4 % (a launch
-        # that needs its whole group resident spins on CUs the encoder needs); coop backward
-        # -0.4..-2 % (lstm3's and lstm4's backward start together and contend)
-        mode = os.environ.get("STF_LSTM_COOP", "512")
-        on = mode == "1" or (mode not in ("0", "") and str(self.C) in mode.split(","))
-        return (on and bool(_lib.load().stf_lstm_coop_supported(self.C))
-                and lbuf.off == 0 and lbuf.cs == 2 * self.C and hT.cs >= self.C and hT.cs % 8 == 0
-                and hT.ptr() % 16 == 0)
+        # None: the default route of every call's layout (lstm_route); an LstmRoute forces that one
+        self.route = None
 
     def coop_error(self):
         """Nonzero if the last cooperative launch's in-launch hand-off timed out (syncs)."""
@@ -219,8 +249,10 @@ class LSTMProgram:
         call("stf_lstm_coop_error", _p(sync), npix, T, _p(out), stream())
         return int(out.item())
 
-    def forward(self, lbuf: Feat, T, B, hT: Feat, need_bwd=True):
+    def forward(self, lbuf: Feat, T, B, hT: Feat, need_bwd=True, coop=LSTM_COOP):
+        """``coop``: the hidden sizes whose default route is the cooperative forward."""
         C, dev = self.C, lbuf.buf.device
+        route = lstm_route(C, lbuf.off, lbuf.cs, hT.cs, hT.ptr(), need_bwd, coop, self.route)
         L = self.lstm
         npix = B * lbuf.H * lbuf.W
         wcat = nhwc.empty(8 * C * C, nhwc.sdt(), dev)
@@ -229,25 +261,27 @@ class LSTMProgram:
         call("stf_lstm_pack", _p(L.weight_ih_l0.detach()), _p(L.weight_hh_l0.detach()), _p(L.bias_ih_l0.detach()),
              _p(L.bias_hh_l0.detach()), C, _p(wcat), _p(wcat_t), _p(bias), stream())
         cst = nhwc.empty((T, npix, C), torch.float32, dev)
-        fused = self.fused(lbuf, hT)
-        coop = not fused and self.coop(lbuf, hT)
-        if fused:
+        gates = None
+        if route.fwd == "seq":
             # all T steps in one launch: c in registers, h_{t-1} in LDS (same values)
             lbuf.check()
             hT.check()
             call("stf_lstm_seq_fwd", _p(wcat), _p(bias), lbuf.ptr(), npix, T, C, _p(cst), hT.ptr(), hT.cs, stream())
-        elif coop:
+        elif route.fwd == "coop":
             # C >= 128: all T steps in one persistent launch, the C/32 workgroups of a pixel
             # block hand h_t to each other in-launch (same values as the per-step launches)
             lbuf.check()
             hT.check()
             lib = _lib.load()
             sync = nhwc.empty(lib.stf_lstm_coop_sync_bytes(npix, T) // 4, torch.int32, dev)
-            # the activated gates (fp32) are kept for the cooperative backward (no recompute)
-            gates = nhwc.empty((T, npix, 4 * C), torch.float32, dev) if need_bwd else None
+            if route.bwd == "gates":
+                # the activated gates (fp32) are kept for the backward (no recompute)
+                gates = nhwc.empty((T, npix, 4 * C), torch.float32, dev)
             call("stf_lstm_coop_fwd", _p(wcat), _p(bias), lbuf.ptr(), npix, T, C, _p(cst), hT.ptr(), hT.cs,
                  _p(gates), _p(sync), self.max_wg, self.spin_limit, stream())
-            self._note_coop(sync, npix, T)
+            self.last_sync = (sync, npix, T)
+            if self.err_word is not None:
+                call("stf_lstm_coop_error", _p(sync), npix, T, _p(self.err_word), stream())
         else:
             for t in range(T):
                 src = rows(lbuf, t * B, B)
@@ -256,9 +290,7 @@ class LSTMProgram:
                 nhwc.igemm(src, wcat, 4 * C, src, 1, 1, 1, 0, bias=bias, lstm=epi)
         st = _S()
         st.lbuf, st.T, st.B, st.wcat, st.wcat_t, st.bias, st.c = lbuf, T, B, wcat, wcat_t, bias, cst
-        st.fused = fused
-        st.coop = coop and need_bwd and os.environ.get("STF_LSTM_COOP_BWD", "0") == "1"
-        st.gates = gates if coop else None
+        st.route, st.gates = route, gates
         return st
 
     def backward(self, st, dhT: Feat, gv, need_dx=True, need_w=True):
@@ -273,22 +305,14 @@ class LSTMProgram:
         dev = lb.buf.device
         npix = B * lb.H * lb.W
         # rows of step t: [dx_t | dh_{t-1}] (the whole-sequence kernel keeps dh in LDS: without dx, no buffer)
-        d2 = new_feat(T * B, lb.H, lb.W, 2 * C, dev) if need_dx or not st.fused else None
+        seq, gates, hoist = st.route.bwd == "seq", st.route.bwd == "gates", st.route.hoist
+        d2 = new_feat(T * B, lb.H, lb.W, 2 * C, dev) if need_dx or not seq else None
         dg = new_feat(T * B, lb.H, lb.W, 4 * C, dev)           # pre-activation gate grads (interleaved)
-        if st.fused:
+        if seq:
             # all T steps backward in one launch (dc in registers, dh_{t-1} in LDS)
             dhT.check()
             call("stf_lstm_seq_bwd", _p(st.wcat), _p(st.wcat_t), _p(st.bias), lb.ptr(), npix, T, C, _p(st.c),
                  dhT.ptr(), dhT.cs, dg.ptr(), d2.ptr() if need_dx else None, d2.cs if need_dx else 0, stream())
-        elif st.coop:
-            # C >= 128: all T steps backward in one persistent launch (dgates and [dx | dh]
-            # exchanged in-launch inside each pixel block; the forward's gates, no recompute)
-            dhT.check()
-            lib = _lib.load()
-            sync = nhwc.empty(lib.stf_lstm_coop_sync_bytes(npix, T) // 4, torch.int32, dev)
-            call("stf_lstm_coop_bwd", _p(st.wcat_t), _p(st.gates), _p(st.c), npix, T, C, dhT.ptr(), dhT.cs,
-                 dg.ptr(), d2.ptr(), d2.cs, _p(sync), self.max_wg, self.spin_limit, stream())
-            self._note_coop(sync, npix, T)
         else:
             # BPTT over the per-step launches.  Per step: the cell backward -- from the activated
             # gates the cooperative forward kept (elementwise stf_lstm_cell_bwd, the arithmetic of
@@ -296,9 +320,7 @@ class LSTMProgram:
             # gates (the forward's GEMM) with the cell backward in its epilogue -- then ONLY the
             # recurrent half dh_{t-1} = dgates_t W_hh (N = C).  The input half d x_t = dgates_t W_ih
             # does not feed the recurrence: it is ONE GEMM over all T steps after the loop (SURVEY
-            # section 2.1 K10, src/stf_lstm_unet.py:124-127; STF_LSTM_HOIST=0: [dx | dh] per step).
-            hoist = os.environ.get("STF_LSTM_HOIST", "1") != "0"
-            gates = st.gates is not None and os.environ.get("STF_LSTM_GATES", "1") != "0"
+            # section 2.1 K10, src/stf_lstm_unet.py:124-127; route.hoist False: [dx | dh] per step).
             w_h = st.wcat_t[4 * C * C:]                     # rows C..2C-1 of [2C][4C]: the h outputs
             dc = nhwc.empty((npix, C), torch.float32, dev)
             for t in range(T - 1, -1, -1):
@@ -347,8 +369,11 @@ class STFProgram(Program):
         fr = m.final_res
         self.final_res = ResBlockProgram(fr.conv_block[0], fr.conv_block[1], fr.conv_block[3], fr.conv_block[4])
         self.lstms = [m.lstm1, m.lstm2, m.lstm3, m.lstm4]
-        side_wg = int(os.environ.get("STF_LSTM_SIDE_WG", "64"))
-        self.lstm_progs = [LSTMProgram(lstm, side_wg if k < 3 else 0) for k, lstm in enumerate(self.lstms)]
+        self.lstm_progs = [LSTMProgram(lstm, LSTM_SIDE_WG if k < 3 else 0) for k, lstm in enumerate(self.lstms)]
+        # hidden sizes whose LSTM takes the cooperative forward (stf_lstm_coop_fwd; a subset of 128,
+        # 256, 512); frozenset() keeps every C >= 128 on the per-step launches, e.g. where a
+        # cooperative launch timed out (check_device_errors)
+        self.lstm_coop = LSTM_COOP
         self._side = None
         self._wstream = None
         self._ident = {}
@@ -383,7 +408,8 @@ class STFProgram(Program):
 
     def plan_knobs(self):
         """Per-program scalars a recorded plan carries by value (part of its signature)."""
-        return tuple((lp.spin_limit, lp.max_wg) for lp in self.lstm_progs) + (self.m.output_size,)
+        return (tuple((lp.spin_limit, lp.max_wg, lp.route) for lp in self.lstm_progs)
+                + (tuple(sorted(self.lstm_coop)), self.m.output_size))
 
     def check_device_errors(self, dev=None, block=False):
         """Raise if a cooperative LSTM launch of an earlier step timed out in its in-launch
@@ -415,10 +441,10 @@ class STFProgram(Program):
         if int(self._err_host[0]) != 0:
             self.err_word.zero_()
             self._err_host.zero_()
-            raise RuntimeError("stfunet: a cooperative LSTM launch (stf_lstm_coop_fwd/bwd) timed out in its "
+            raise RuntimeError("stfunet: a cooperative LSTM launch (stf_lstm_coop_fwd) timed out in its "
                                "in-launch hand-off (its workgroups could not all be resident), so that step's "
-                               "LSTM outputs and gradients are invalid; STF_LSTM_COOP=0 selects the per-step "
-                               "launches")
+                               "LSTM outputs and gradients are invalid; model.program.lstm_coop = frozenset() "
+                               "selects the per-step launches")
 
     def _identity(self, C, dev):
         """BatchNorm-identity state of the head's input (no BN there), made once per (C, device)."""
@@ -434,22 +460,12 @@ class STFProgram(Program):
         1/16 and 1/32 resolution (lstm4 stays on the main stream: the decoder and the
         encoder backward need it first).
 
-        ``STF_SIDE_STREAMS`` maps lstm 1-3 to streams, one character each: a digit names a
-        private stream, ``w`` the weight-gradient side stream (``nhwc.wgrad_side_stream``)."""
+        lstm1 and lstm2 share one private stream; lstm3 runs on the weight-gradient side stream
+        (``nhwc.wgrad_side_stream``; a private stream where there is none).  One stream each and
+        three private streams measured slower."""
         if self._side is None or self._side[0].device != dev:
-            spec = os.environ.get("STF_SIDE_STREAMS", "00w")
-            if len(spec) != 3 or any(c not in "012w" for c in spec):
-                raise ValueError(f"STF_SIDE_STREAMS={spec!r}: three of 0 1 2 w")
-            own, ws = {}, nhwc.wgrad_side_stream(dev)
-            side = []
-            for c in spec:
-                if c == "w" and ws is not None:
-                    side.append(ws)
-                else:
-                    if c not in own:
-                        own[c] = nhwc.side_stream(dev, "side" + c)
-                    side.append(own[c])
-            self._side = side
+            s0, ws = nhwc.side_stream(dev, "side0"), nhwc.wgrad_side_stream(dev)
+            self._side = [s0, s0, ws if ws is not None else nhwc.side_stream(dev, "sidew")]
         return self._side
 
     def _done(self, module, side=None):
@@ -581,10 +597,10 @@ class STFProgram(Program):
                 dc = dcat[2 - li] = new_feat(B, hh, ww, Cout + d.fusion.in_channels - Cout, dev)
                 nhwc.wait(side[li], main)
                 with torch.cuda.stream(side[li]):
-                    st = lp.forward(lbuf, T, B, dc.slice(dc.C - lp.C, lp.C), lstm_bwd)
+                    st = lp.forward(lbuf, T, B, dc.slice(dc.C - lp.C, lp.C), lstm_bwd, self.lstm_coop)
             else:
                 e4f = new_feat(B, hh, ww, lp.C, dev)
-                st = lp.forward(lbuf, T, B, e4f, lstm_bwd)
+                st = lp.forward(lbuf, T, B, e4f, lstm_bwd, self.lstm_coop)
             S.lstm[li] = st if lstm_bwd else None
             del st
         S.dcat = dcat

@@ -153,6 +153,45 @@ def test_plan_rerecords_on_shape_change():
         os.environ.pop("STF_PLAN", None)
 
 
+def test_plan_rerecords_on_lstm_route_change():
+    """The LSTM routes are part of a plan's signature (STFProgram.plan_knobs): after a change of
+    ``lstm_coop`` or of an LSTM program's forced ``route`` the old plan is not replayed (an eager
+    warm-up step, then a recording of its own), and going back finds the first plan again."""
+    from stfunet import engine
+    from stfunet.stf_lstm_unet import LstmRoute
+    os.environ["STF_PLAN"] = "1"
+    try:
+        model = _make("stf")
+        (x, t), = _batches("stf", 1)
+        prog = model.program
+        rt, lp4 = prog.runtime, prog.lstm_progs[3]
+
+        def steps(n):
+            for _ in range(n):
+                for p in model.parameters():
+                    p.grad = None
+                engine.criterion(model(x), t).backward()
+            return rt.fwd, prog.flat.grad.clone()
+        p0, g0 = steps(3)                               # warm-up, record, replay
+        assert p0 is not None and len(rt.entries) == 1
+        prog.lstm_coop = frozenset()                    # lstm4 on the per-step launches
+        p1, g1 = steps(3)
+        assert p1 is not None and p1 is not p0 and len(rt.entries) == 2
+        prog.lstm_coop = frozenset({512})
+        p, g = steps(1)
+        assert p is p0 and torch.equal(g, g0)           # back: no re-recording
+        lp4.route = LstmRoute("step", "recompute", True)       # the per-step launches again, now forced
+        p2, g2 = steps(3)
+        assert p2 is not None and p2 is not p0 and p2 is not p1
+        lp4.route = None
+        p, g = steps(1)
+        assert p is p0 and torch.equal(g, g0)
+        # same weights and batch throughout, and every route computes the same bits
+        assert torch.equal(g1, g0) and torch.equal(g2, g0)
+    finally:
+        os.environ.pop("STF_PLAN", None)
+
+
 def test_plan_two_forwards_before_backward():
     """forward A, forward B, backward A, backward B == the eager gradients: B must not replay
     over the static state A's backward still needs."""
