@@ -209,10 +209,6 @@ inline void launch(void (*k)(A...), dim3 g, dim3 b, unsigned sh, hipStream_t s, 
 }
 
 hipError_t memset_async(void* p, int value, size_t bytes, hipStream_t s);
-// Timing-only ablation knobs (results are WRONG while one is on: STF_WGRAD_DIAG,
-// STF_WGRAD_ONE_SLAB) take effect only with STF_ABLATION=1 also set; otherwise a set knob is
-// refused with one line on stderr and reads as 0.  Defined in plan.hip.
-int ablation_env(const char* name);
 // The one A/B switch, STF_IGEMM_CFG (results stay valid; read once, at its first use; DESIGN.md
 // "A/B switches"); nothing else in the library reads the environment.
 char ab_letter(const char* name);     // first character of the value, 0 when unset

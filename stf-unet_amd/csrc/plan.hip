@@ -144,18 +144,6 @@ bool stf::plan_recording() { return g_rec != nullptr; }
 
 void stf::plan_append(stf::PlanOp* op, hipStream_t s) { append(op, s); }
 
-int stf::ablation_env(const char* name) {
-  const char* e = getenv(name);
-  if (!e || !e[0] || (e[0] == '0' && !e[1])) return 0;
-  const char* ok = getenv("STF_ABLATION");
-  if (ok && ok[0] == '1') {
-    fprintf(stderr, "stfunet: timing-only ablation %s=%s is ON -- results are not valid\n", name, e);
-    return atoi(e);
-  }
-  fprintf(stderr, "stfunet: %s=%s ignored (a timing-only ablation: set STF_ABLATION=1 as well)\n", name, e);
-  return 0;
-}
-
 char stf::ab_letter(const char* name) {
   const char* e = getenv(name);
   return e ? e[0] : 0;

@@ -14,6 +14,19 @@
 #include "../../include/stfunet.h"
 #include "reduce.h"
 
+// Timing-only builds of the fused 3x3 kernel (results wrong, never in the shipped build; made with
+// tools/build_variant.sh and loaded through STF_LIB).  -DWGRAD_DIAG=4: the 4 x 16-tile launches take
+// the DIAG = 4 instantiation, whose per-wave cycle buckets overwrite the start of every block's slab
+// tile (tools/wgrad_timeline.py).  -DWGRAD_ONE_SLAB=1: every split writes slab 0 (L2-resident, no
+// slab traffic to HBM) -- the upper bound of folding the slabs in-kernel (tools/ablate_bench.py slab).
+#ifndef WGRAD_DIAG
+#define WGRAD_DIAG 0
+#endif
+#ifndef WGRAD_ONE_SLAB
+#define WGRAD_ONE_SLAB 0
+#endif
+static_assert(WGRAD_DIAG == 0 || WGRAD_DIAG == 4, "WGRAD_DIAG: 0 or 4");
+
 namespace {
 
 constexpr int NT = 256;
@@ -23,9 +36,18 @@ typedef __attribute__((address_space(3))) v4s lds_v4s;
 struct WArgs {
   const uint16_t* dy; const uint16_t* x; float* ws;
   int N, Hs, Ws, Cs, xcs, Hd, Wd, R, S, st, pad, M, Nout, dycs, chunk;
-  int colmajor;         // fused 3x3: walk pixel tiles column-major (vertical neighbours in turn)
-  int one_slab;         // timing-only ablation (STF_WGRAD_ONE_SLAB=1): every split writes slab 0
+  int colmajor;         // fused 3x3: walk pixel tiles column-major (vertical neighbours in turn); always 1
+  int pad_;             // unused: keeps the kernarg layout the tile kernels were measured with
 };
+
+// One MFMA operand fragment (8 consecutive K slots of one column per lane) out of a row-major LDS
+// image: two transposed reads of 4 rows x 16 columns each.  Lane 4q + p of a 16-lane group passes the
+// address of row q (lo; hi: the row 4 K slots on), columns 4p..4p+3, and receives column (lane & 15).
+__device__ __forceinline__ e16x8 read_tr(const void* lo, const void* hi) {
+  const v4s l = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)lo);
+  const v4s h = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)hi);
+  return __builtin_bit_cast(e16x8, __builtin_shufflevector(l, h, 0, 1, 2, 3, 4, 5, 6, 7));
+}
 
 template <int BM, int BN, int BKP, bool GENERAL>
 __global__ __launch_bounds__(NT, 2) void wgrad_kernel(WArgs a) {
@@ -122,18 +144,12 @@ __global__ __launch_bounds__(NT, 2) void wgrad_kernel(WArgs a) {
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int col = wm * WTM + i * 16 + p4;
-        v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(sa + krow * SA + col));
-        v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(sa + (krow + 4) * SA + col));
-        short s8[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        af[i] = __builtin_bit_cast(e16x8, s8);
+        af[i] = read_tr(sa + krow * SA + col, sa + (krow + 4) * SA + col);
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const int col = wn * WTN + j * 16 + p4;
-        v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(sb + krow * SB + col));
-        v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(sb + (krow + 4) * SB + col));
-        short s8[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        bfr[j] = __builtin_bit_cast(e16x8, s8);
+        bfr[j] = read_tr(sb + krow * SB + col, sb + (krow + 4) * SB + col);
       }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -175,6 +191,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad_kernel(WArgs a) {
 // Waves: 1 (n) x 4 (c); each holds 64 n x 16 c x 9 taps = 36 accumulators.
 template <int PW, int DIAG = 0>
 __global__ __launch_bounds__(NT, 2) void wgrad3x3_kernel(WArgs a, int tiles_y, int tiles_x, int ntiles) {
+  static_assert(DIAG == 0 || DIAG == 4, "DIAG: 0, or 4 in a -DWGRAD_DIAG=4 build");
   constexpr int PH = 64 / PW, HW = PW + 2, HR = (PH + 2) * HW;
   constexpr int SR = 64 + 16;                   // LDS row stride (elements), 160 B
   constexpr int A_EL = 64 * SR, B_EL = HR * SR;
@@ -271,27 +288,22 @@ __global__ __launch_bounds__(NT, 2) void wgrad3x3_kernel(WArgs a, int tiles_y, i
   for (int it = 0; it < steps; ++it) {
     const int cur = it & 1;
     stamp(-1);
-    if (it + 1 < steps && (DIAG != 1 || it < 1)) load(t_begin + it + 1);
+    if (it + 1 < steps) load(t_begin + it + 1);
     stamp(0);
     const uint16_t* sa = smem[cur];
     const uint16_t* sb = sa + A_EL;
-    if (DIAG == 2) { if (it + 1 < steps) store(cur ^ 1); __syncthreads(); continue; }
     // software-pipelined: the 18 (k-step, tap) steps in one flat sequence, B fragments
     // read two steps ahead (across the k-step boundary), the second k-step's A fragments
     // four steps before they are needed -- LDS latency hides behind the MFMAs
     auto readA = [&](int k2, int i) {
       const int col = i * 16 + p4;
-      v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(sa + arow[k2][0] + col));
-      v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(sa + arow[k2][1] + col));
-      return __builtin_bit_cast(e16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+      return read_tr(sa + arow[k2][0] + col, sa + arow[k2][1] + col);
     };
     auto readB = [&](int st) {
       const int k2 = st / 9, t = st % 9;
       const int toff = ((t / 3) * HW + t % 3) * SR;
       const int col = wn * 16 + p4;
-      v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(sb + brow[k2][0] + toff + col));
-      v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4s*)(sb + brow[k2][1] + toff + col));
-      return __builtin_bit_cast(e16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+      return read_tr(sb + brow[k2][0] + toff + col, sb + brow[k2][1] + toff + col);
     };
     e16x8 af[2][TMW], bq[18];
 #pragma unroll
@@ -319,7 +331,7 @@ __global__ __launch_bounds__(NT, 2) void wgrad3x3_kernel(WArgs a, int tiles_y, i
   }
 
   const int RSC = 9 * a.Cs;
-  float* out = a.ws + (size_t)(a.one_slab ? 0 : split) * a.Nout * RSC;
+  float* out = a.ws + (size_t)(WGRAD_ONE_SLAB ? 0 : split) * a.Nout * RSC;
 #pragma unroll
   for (int t = 0; t < 9; ++t)
 #pragma unroll
@@ -368,14 +380,6 @@ constexpr int WC8_STAGE = WC8_HBYTES + 256 * 64 * 2;     // bytes: halo rows + d
 // dy tile: 32-B slot h of pixel p stored at slot h ^ wc8_swz(p), so that the 8 pixel rows one
 // 32-lane half of a transposed read touches (p0 + 0..3, p0 + 8..11) cover all 64 banks once
 __device__ __forceinline__ int wc8_swz(int p) { return ((p >> 1) & 1) | (((p >> 3) & 1) << 1); }
-typedef short wc8_s4 __attribute__((ext_vector_type(4)));
-typedef short wc8_s8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ e16x8 wc8_tr(const uint8_t* p, int second) {
-  typedef __attribute__((address_space(3))) wc8_s4* lp;
-  const wc8_s4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(p));
-  const wc8_s4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(p + second));
-  return __builtin_bit_cast(e16x8, (wc8_s8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 __global__ __launch_bounds__(NT, 2) void wgrad3x3_c8_kernel(WArgs a, int tiles_y, int tiles_x, int ntiles) {
   __shared__ __attribute__((aligned(16))) uint8_t lds[2 * WC8_STAGE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -451,10 +455,10 @@ __global__ __launch_bounds__(NT, 2) void wgrad3x3_c8_kernel(WArgs a, int tiles_y
       // k-slots fk*8 + 0..7 = pixels p0 + 0..7 (p0 = wave*64 + ks*32 + fk*8) in both operands
       e16x8 bq[5];
 #pragma unroll
-      for (int kb = 0; kb < 5; ++kb) bq[kb] = wc8_tr(st + boff[ks][kb], 4 * 16);
+      for (int kb = 0; kb < 5; ++kb) bq[kb] = read_tr(st + boff[ks][kb], st + boff[ks][kb] + 4 * 16);
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb) {
-        const e16x8 av = wc8_tr(st + aoff[ks][nb], 4 * 128);
+        const e16x8 av = read_tr(st + aoff[ks][nb], st + aoff[ks][nb] + 4 * 128);
 #pragma unroll
         for (int kb = 0; kb < 5; ++kb) acc[nb][kb] = mfma16x16x32(av, bq[kb], acc[nb][kb]);
       }
@@ -697,181 +701,164 @@ __global__ __launch_bounds__(256) void wgrad_reduce_tap_kernel(const float* __re
   o[0] = (float)a0; o[RS] = (float)a1; o[2 * RS] = (float)a2; o[3 * RS] = (float)a3;
 }
 
-bool big_tile(const stf_wgrad_args* a) { return a->Nout % 128 == 0 && a->g.Cs % 128 == 0; }
+// One launchable instantiation.  family: 'K' 8-channel input, '3' fused 3x3, 'T' ConvT 2x2 (both on
+// 64-pixel tiles), 'G' generic.  key = the template arguments: '3' {PW, DIAG}, 'T' {PW, NB},
+// 'G' {BM, BN, BKP, GENERAL}.  Name, key and kernel of an entry come from the same macro arguments.
+struct WVariant {
+  const char* name;
+  char family;
+  int key[4];
+  void (*tile)(WArgs, int, int, int);
+  void (*generic)(WArgs);
+};
+#define W_STR_(...) #__VA_ARGS__
+#define W_STR(...) W_STR_(__VA_ARGS__)
+#define W_TILE(FAM, KERNEL, ...) {#KERNEL "<" W_STR(__VA_ARGS__) ">", FAM, {__VA_ARGS__}, KERNEL<__VA_ARGS__>, nullptr}
+#define W_GENERIC(...) {"wgrad_kernel<" W_STR(__VA_ARGS__) ">", 'G', {__VA_ARGS__}, nullptr, wgrad_kernel<__VA_ARGS__>}
+const WVariant kVariants[] = {
+    {"wgrad3x3_c8_kernel", 'K', {0, 0, 0, 0}, wgrad3x3_c8_kernel, nullptr},
+    W_TILE('3', wgrad3x3_kernel, 16, WGRAD_DIAG),   // the only entry a -DWGRAD_DIAG=4 build changes
+    W_TILE('3', wgrad3x3_kernel, 8, 0),
+    W_TILE('T', wgrad2x2s2_kernel, 16, 2), W_TILE('T', wgrad2x2s2_kernel, 8, 2),
+    W_TILE('T', wgrad2x2s2_kernel, 16, 1), W_TILE('T', wgrad2x2s2_kernel, 8, 1),
+    W_GENERIC(128, 128, 32, false), W_GENERIC(64, 64, 64, false),
+    W_GENERIC(64, 96, 64, true), W_GENERIC(64, 64, 64, true),
+};
 
-// fused-tap kernel: 3x3, stride 1, pad 1, 64-multiples of channels, W >= 8
-int fused_pw(const stf_wgrad_args* a) {
+const WVariant* find_variant(char family, int k0, int k1, int k2 = 0, int k3 = 0) {
+  for (const WVariant& v : kVariants)
+    if (v.family == family && v.key[0] == k0 && v.key[1] == k1 && v.key[2] == k2 && v.key[3] == k3) return &v;
+  return nullptr;
+}
+
+// Which kernel runs a launch, in how many splits of what chunk, on what grid and workspace.
+struct WRoute {
+  const WVariant* variant = nullptr;
+  char family = 'G';
+  // tile kernels ('K', '3', 'T'): tile width, dy channels per block in 64s, tiles per image, tiles
+  int pw = 0, nb = 1, ty = 0, tx = 0, nt = 0;
+  // generic kernel: dy-channel x column tile, pixels per K step, column blocks that straddle taps
+  int bm = 64, bn = 64, bkp = 64;
+  bool general = false;
+  int splits = 1, chunk = 0;     // chunk: pixel tiles per split (tile kernels), pixels (generic)
+  dim3 grid;                     // (split, dy-channel block, column block)
+  size_t ws_bytes = 0;           // splits fp32 slabs [Nout][R * S * Cs]
+};
+
+// The rules, in the order they apply ("same" = 3x3 / stride 1 / pad 1 with equal source and
+// destination sizes; grid_blocks > 0 replaces the 512 of rules 1 and 4):
+//  1. same, Cs == 8 dense, Nout == 64 -> wgrad3x3_c8_kernel on 16 x 16 pixel tiles, persistent: one
+//     split per workgroup, min(tiles, 512) of them (two workgroups per CU).
+//  2. same, Nout and Cs multiples of 64, W >= 8 -> the fused 3x3 kernel, 4 x 16 pixel tiles from W = 16
+//     up and 8 x 8 below.
+//  3. 2x2 / stride 2 / pad 0 over a source twice the destination's size (ConvT 2x2; x = the 2x larger
+//     gradient tensor), Nout and Cs multiples of 64, W >= 8 -> the fused ConvT kernel on the same
+//     tiles.  128 dy channels per block (NB = 2) from 256 dy channels up (measured, tools/ab_convt.sh,
+//     batch 64: up16/32/64 132/127/134 -> 104/99/107 us; at 128 channels the two 64-channel blocks of
+//     a pixel tile meet in L2 anyway and the 3-per-CU occupancy wins, 150 vs 172 us).
+//  4. rules 2 and 3 split the pixel tiles until ~512 workgroups, every split keeping at least 4 tiles.
+//  5. everything else -> the generic kernel: 128 x 128 tile with 32-pixel K steps when Nout and Cs are
+//     multiples of 128, else 64 x 64 with 64-pixel steps; column blocks straddle taps (GENERAL) unless
+//     Cs is a multiple of 64 (which the 128 x 128 tile's Cs % 128 == 0 implies).
+//  6. GENERAL with 64 < R * S * Cs <= 96 (the 8-channel network input, 3x3: 72 columns) -> one
+//     96-column block, which reads dy once (two 64-column blocks would read the 64-channel dy twice).
+//  7. rule 5 splits K until ~target workgroups, every split keeping at least 4 K steps.  Every split
+//     writes a [Nout][R*S*Cs] fp32 slab that the reduce reads back, so the 128 x 128 tile (1x1 weight
+//     gradients of the STF LSTMs and downsamples: up to 1024 splits of 134 MB slabs at 2048) aims at
+//     512, two workgroups per CU (STF cfg3 +2.6 % over 2048, same box); the 64-wide tiles keep 2048
+//     (UNet's first layer: 512 measured -0.5..-0.8 %).  grid_blocks is not read.
+// Nothing is validated here (stf_wgrad does that): the plan and name queries answer for any argument.
+WRoute route_of(const stf_wgrad_args* a) {
   const stf_conv_geom& c = a->g;
-  if (c.R != 3 || c.S != 3 || c.stride != 1 || c.pad != 1 || c.Hd != c.Hs || c.Wd != c.Ws) return 0;
-  if (a->Nout % 64 || c.Cs % 64 || c.Wd < 8) return 0;
-  return c.Wd >= 16 ? 16 : 8;
-}
+  WRoute r;
+  const bool same = c.R == 3 && c.S == 3 && c.stride == 1 && c.pad == 1 && c.Hd == c.Hs && c.Wd == c.Ws;
+  const bool blocks64 = a->Nout % 64 == 0 && c.Cs % 64 == 0 && c.Wd >= 8;
+  const bool convt = c.R == 2 && c.S == 2 && c.stride == 2 && c.pad == 0 && !c.transposed && c.Hs == 2 * c.Hd &&
+                     c.Ws == 2 * c.Wd;
+  if (same && c.Cs == 8 && c.src_cstride == 8 && a->Nout == 64 && !c.transposed) r.family = 'K';
+  else if (same && blocks64) r.family = '3';
+  else if (convt && blocks64) r.family = 'T';
+  const auto ceil_div = [](long x, long y) { return (x + y - 1) / y; };
+  // `want` splits of `work` units (pixel tiles or pixels), at most `most`, at least one
+  const auto clamp = [](long want, long most) { return std::max<long>(1, std::min(want, most)); };
+  long gy = 1, gz = 1;                  // grid.y, grid.z: dy-channel blocks, column blocks
 
-// ConvT 2x2 / stride 2 fused-tap kernel (x = the 2x larger gradient tensor)
-int fused22_pw(const stf_wgrad_args* a) {
-  const stf_conv_geom& c = a->g;
-  if (c.R != 2 || c.S != 2 || c.stride != 2 || c.pad != 0 || c.transposed) return 0;
-  if (c.Hs != 2 * c.Hd || c.Ws != 2 * c.Wd || a->Nout % 64 || c.Cs % 64 || c.Wd < 8) return 0;
-  return c.Wd >= 16 ? 16 : 8;
-}
-
-// dy channels per ConvT 2x2 block, in 64s: 2 from 256 dy channels up (measured, tools/ab_convt.sh,
-// batch 64: up16/32/64 132/127/134 -> 104/99/107 us; at 128 channels the two 64-channel blocks
-// of a pixel tile meet in L2 anyway and the 3-per-CU occupancy wins, 150 vs 172 us).
-// STF_WGRAD22_NB=1: always 1 (A/B)
-int fused22_nb(const stf_wgrad_args* a) {
-  return (a->Nout % 128 == 0 && a->Nout >= 256) ? 2 : 1;
-}
-
-// the 8-channel-input 3x3 layer (conv3x3_c8_kernel's weight gradient)
-bool fused_c8(const stf_wgrad_args* a) {
-  const stf_conv_geom& c = a->g;
-  return c.R == 3 && c.S == 3 && c.stride == 1 && c.pad == 1 && c.Hd == c.Hs && c.Wd == c.Ws &&
-         c.Cs == 8 && c.src_cstride == 8 && a->Nout == 64 && !c.transposed;
-}
-
-void c8_tiles(const stf_wgrad_args* a, int& ty, int& tx, int& nt) {
-  ty = (a->g.Hd + WC8_T - 1) / WC8_T;
-  tx = (a->g.Wd + WC8_T - 1) / WC8_T;
-  nt = a->g.N * ty * tx;
-}
-
-void fused_tiles(const stf_wgrad_args* a, int pw, int& ty, int& tx, int& nt) {
-  ty = (a->g.Hd + 64 / pw - 1) / (64 / pw);
-  tx = (a->g.Wd + pw - 1) / pw;
-  nt = a->g.N * ty * tx;
-}
-
-void plan(const stf_wgrad_args* a, int& splits, int& chunk) {
-  if (fused_c8(a)) {                                 // persistent: two workgroups per CU
-    int ty, tx, nt;
-    c8_tiles(a, ty, tx, nt);
-    const long want = std::min<long>(nt, a->grid_blocks > 0 ? a->grid_blocks : 512);
-    chunk = (int)((nt + want - 1) / want);
-    splits = (nt + chunk - 1) / chunk;
-    return;
+  if (r.family == 'G') {
+    const int M = c.N * c.Hd * c.Wd;
+    const long rsc = (long)c.R * c.S * c.Cs;
+    const bool big = a->Nout % 128 == 0 && c.Cs % 128 == 0;    // implies Cs % 64 == 0: never GENERAL
+    r.general = c.Cs % 64 != 0;
+    r.bm = big ? 128 : 64;
+    r.bn = big ? 128 : (r.general && rsc > 64 && rsc <= 96) ? 96 : 64;
+    r.bkp = big ? 32 : 64;
+    gy = ceil_div(a->Nout, r.bm);
+    gz = r.bn == 96 ? 1 : ceil_div(rsc, r.bn);
+    const long want = clamp(ceil_div(big ? 512 : 2048, gy * gz), ceil_div(M, 4 * r.bkp));
+    r.chunk = (int)(ceil_div(ceil_div(M, want), r.bkp) * r.bkp);
+    r.splits = (M + r.chunk - 1) / r.chunk;
+    r.variant = find_variant('G', r.bm, r.bn, r.bkp, r.general);
+  } else {
+    const long budget = a->grid_blocks > 0 ? a->grid_blocks : 512;
+    r.pw = r.family == 'K' ? WC8_T : c.Wd >= 16 ? 16 : 8;
+    const int ph = r.family == 'K' ? WC8_T : 64 / r.pw;
+    r.ty = (c.Hd + ph - 1) / ph;
+    r.tx = (c.Wd + r.pw - 1) / r.pw;
+    r.nt = c.N * r.ty * r.tx;
+    long want = std::min<long>(r.nt, budget);                  // 'K': one split per workgroup
+    if (r.family != 'K') {
+      r.nb = (r.family == 'T' && a->Nout % 128 == 0 && a->Nout >= 256) ? 2 : 1;
+      gy = a->Nout / (64 * r.nb);
+      gz = c.Cs / 64;
+      want = clamp(ceil_div(budget, gy * gz), (r.nt + 3) / 4);
+    }
+    r.chunk = (int)((r.nt + want - 1) / want);
+    r.splits = (r.nt + r.chunk - 1) / r.chunk;
+    r.variant = r.family == 'K'   ? find_variant('K', 0, 0)
+                : r.family == 'T' ? find_variant('T', r.pw, r.nb)
+                                  : find_variant('3', r.pw, r.pw == 16 ? WGRAD_DIAG : 0);
   }
-  if (const int pw = fused_pw(a) ? fused_pw(a) : fused22_pw(a)) {
-    int ty, tx, nt;
-    fused_tiles(a, pw, ty, tx, nt);
-    const long tiles = (long)(a->Nout / (fused_pw(a) ? 64 : 64 * fused22_nb(a))) * (a->g.Cs / 64);
-    const long target = a->grid_blocks > 0 ? a->grid_blocks : 512;
-    long want = (target + tiles - 1) / tiles;
-    const long maxs = (nt + 3) / 4;                  // at least 4 pixel tiles per split
-    if (want > maxs) want = maxs;
-    if (want < 1) want = 1;
-    chunk = (int)((nt + want - 1) / want);
-    splits = (nt + chunk - 1) / chunk;
-    return;
-  }
-  const int M = a->g.N * a->g.Hd * a->g.Wd;
-  const int bm = big_tile(a) ? 128 : 64, bkp = big_tile(a) ? 32 : 64;
-  const long rsc = (long)a->g.R * a->g.S * a->g.Cs;
-  const long cblocks = (a->g.Cs % 64 && rsc > 64 && rsc <= 96) ? 1 : (rsc + bm - 1) / bm;
-  const long tiles = (long)((a->Nout + bm - 1) / bm) * cblocks;
-  // K splits until ~target workgroups: every split writes a [Nout][R*S*Cs] fp32 slab that the reduce
-  // reads back, so the 128 x 128 tile (1x1 weight gradients of the STF LSTMs and downsamples: up to
-  // 1024 splits of 134 MB slabs at 2048) aims at two workgroups per CU (STF cfg3 +2.6 % over 2048,
-  // same box); the 64-wide tiles keep 2048 (UNet's first layer: 512 measured -0.5..-0.8 %)
-  const long target = big_tile(a) ? 512 : 2048;
-  long want = (target + tiles - 1) / tiles;
-  long maxs = (M + 4 * bkp - 1) / (4 * bkp);        // at least 4 K steps per split
-  if (want > maxs) want = maxs;
-  if (want < 1) want = 1;
-  chunk = (int)(((M + want - 1) / want + bkp - 1) / bkp * bkp);
-  splits = (M + chunk - 1) / chunk;
+  r.grid = dim3(r.splits, (unsigned)gy, (unsigned)gz);
+  r.ws_bytes = (size_t)r.splits * a->Nout * c.R * c.S * c.Cs * sizeof(float);
+  return r;
 }
+
+// stf_wgrad_reduce's per-tap kernels by R * S
+struct TapReduce { int rs; void (*kernel)(const float*, int, int, int, float*); };
+const TapReduce kTapReduce[] = {
+    {9, wgrad_reduce_tap_kernel<9>}, {4, wgrad_reduce_tap_kernel<4>}, {1, wgrad_reduce_tap_kernel<1>}};
 
 }  // namespace
 
 extern "C" int stf_wgrad_plan(const stf_wgrad_args* a, int* splits, size_t* ws_bytes) {
-  int s, chunk;
-  plan(a, s, chunk);
-  if (splits) *splits = s;
-  if (ws_bytes) *ws_bytes = (size_t)s * a->Nout * a->g.R * a->g.S * a->g.Cs * sizeof(float);
+  const WRoute r = route_of(a);
+  if (splits) *splits = r.splits;
+  if (ws_bytes) *ws_bytes = r.ws_bytes;
   return 0;
 }
 
+// Name of the device kernel these args run (as rocprofv3 prints it), for timers
 extern "C" const char* stf_wgrad_kernel_name(const stf_wgrad_args* a) {
-  if (fused_c8(a)) return "wgrad3x3_c8_kernel";
-  if (const int pw = fused_pw(a)) {
-    return pw == 16 ? "wgrad3x3_kernel<16, 0>" : "wgrad3x3_kernel<8, 0>";
-  }
-  if (const int pw = fused22_pw(a)) {
-    if (fused22_nb(a) == 2) return pw == 16 ? "wgrad2x2s2_kernel<16, 2>" : "wgrad2x2s2_kernel<8, 2>";
-    return pw == 16 ? "wgrad2x2s2_kernel<16, 1>" : "wgrad2x2s2_kernel<8, 1>";
-  }
-  if (big_tile(a)) return "wgrad_kernel<128, 128, 32, false>";
-  const int rsc = a->g.R * a->g.S * a->g.Cs;
-  if (a->g.Cs % 64 == 0) return "wgrad_kernel<64, 64, 64, false>";
-  return (rsc > 64 && rsc <= 96) ? "wgrad_kernel<64, 96, 64, true>" : "wgrad_kernel<64, 64, 64, true>";
+  const WRoute r = route_of(a);
+  return r.variant ? r.variant->name : "(no kernel)";     // every route has a table entry today
 }
 
 extern "C" int stf_wgrad(const stf_wgrad_args* a, stf_stream_t stream) {
   const stf_conv_geom& c = a->g;
   if (c.transposed || a->Nout % 8 || c.Cs % 8 || a->dy_cstride % 8 || c.src_cstride % 8) return STF_EINVAL;
   if (((uintptr_t)a->dy & 15) || ((uintptr_t)a->x & 15)) return STF_EINVAL;
-  int splits, chunk;
-  plan(a, splits, chunk);
-  if (a->splits != splits) return STF_EINVAL;
+  const WRoute r = route_of(a);
+  if (!r.variant || a->splits != r.splits) return STF_EINVAL;
   WArgs w;
   w.dy = (const uint16_t*)a->dy; w.x = (const uint16_t*)a->x; w.ws = a->ws;
   w.N = c.N; w.Hs = c.Hs; w.Ws = c.Ws; w.Cs = c.Cs; w.xcs = c.src_cstride; w.Hd = c.Hd; w.Wd = c.Wd;
   w.R = c.R; w.S = c.S; w.st = c.stride; w.pad = c.pad; w.M = c.N * c.Hd * c.Wd; w.Nout = a->Nout;
-  w.dycs = a->dy_cstride; w.chunk = chunk;
+  w.dycs = a->dy_cstride; w.chunk = r.chunk;
   w.colmajor = 1;
-  // timing-only ablation: the split-K slabs of the fused 3x3 kernel all land in slab 0 (L2-resident:
-  // no slab traffic to HBM; the sums are wrong) -- the upper bound of folding the slabs in-kernel
-  static const int one_slab = stf::ablation_env("STF_WGRAD_ONE_SLAB") == 1;
-  w.one_slab = one_slab;
+  w.pad_ = 0;
+  const WVariant& v = *r.variant;
   hipStream_t s = (hipStream_t)stream;
-  const int rsc = c.R * c.S * c.Cs;
-  if (fused_c8(a)) {
-    int ty, tx, nt;
-    c8_tiles(a, ty, tx, nt);
-    hipLaunchKernelGGL(wgrad3x3_c8_kernel, dim3(splits), dim3(NT), 0, s, w, ty, tx, nt);
-    STF_CHECK_LAUNCH();
-    return 0;
-  }
-  if (const int pw = fused_pw(a)) {
-    int ty, tx, nt;
-    fused_tiles(a, pw, ty, tx, nt);
-    dim3 grid(splits, a->Nout / 64, c.Cs / 64);
-    static const int diag = stf::ablation_env("STF_WGRAD_DIAG");
-    if (pw == 16 && diag == 1)
-      hipLaunchKernelGGL((wgrad3x3_kernel<16, 1>), grid, dim3(NT), 0, s, w, ty, tx, nt);
-    else if (pw == 16 && diag == 2)
-      hipLaunchKernelGGL((wgrad3x3_kernel<16, 2>), grid, dim3(NT), 0, s, w, ty, tx, nt);
-    else if (pw == 16 && diag == 4)
-      hipLaunchKernelGGL((wgrad3x3_kernel<16, 4>), grid, dim3(NT), 0, s, w, ty, tx, nt);
-    else if (pw == 16)
-      hipLaunchKernelGGL((wgrad3x3_kernel<16>), grid, dim3(NT), 0, s, w, ty, tx, nt);
-    else
-      hipLaunchKernelGGL((wgrad3x3_kernel<8>), grid, dim3(NT), 0, s, w, ty, tx, nt);
-  } else if (const int pw22 = fused22_pw(a)) {
-    int ty, tx, nt;
-    fused_tiles(a, pw22, ty, tx, nt);
-    const int nb = fused22_nb(a);
-    dim3 grid(splits, a->Nout / (64 * nb), c.Cs / 64);
-    if (nb == 2 && pw22 == 16) hipLaunchKernelGGL((wgrad2x2s2_kernel<16, 2>), grid, dim3(NT), 0, s, w, ty, tx, nt);
-    else if (nb == 2) hipLaunchKernelGGL((wgrad2x2s2_kernel<8, 2>), grid, dim3(NT), 0, s, w, ty, tx, nt);
-    else if (pw22 == 16) hipLaunchKernelGGL((wgrad2x2s2_kernel<16, 1>), grid, dim3(NT), 0, s, w, ty, tx, nt);
-    else hipLaunchKernelGGL((wgrad2x2s2_kernel<8, 1>), grid, dim3(NT), 0, s, w, ty, tx, nt);
-  } else if (big_tile(a)) {
-    dim3 grid(splits, a->Nout / 128, rsc / 128);
-    hipLaunchKernelGGL((wgrad_kernel<128, 128, 32, false>), grid, dim3(NT), 0, s, w);
-  } else if (c.Cs % 64 == 0) {
-    dim3 grid(splits, (a->Nout + 63) / 64, rsc / 64);
-    hipLaunchKernelGGL((wgrad_kernel<64, 64, 64, false>), grid, dim3(NT), 0, s, w);
-  } else if (rsc > 64 && rsc <= 96) {
-    // 8-channel network input, 3x3 (72 columns): one 96-column block reads dy once
-    // (two 64-column blocks would read the 64-channel dy twice)
-    dim3 grid(splits, (a->Nout + 63) / 64, 1);
-    hipLaunchKernelGGL((wgrad_kernel<64, 96, 64, true>), grid, dim3(NT), 0, s, w);
-  } else {
-    dim3 grid(splits, (a->Nout + 63) / 64, (rsc + 63) / 64);
-    hipLaunchKernelGGL((wgrad_kernel<64, 64, 64, true>), grid, dim3(NT), 0, s, w);
-  }
+  if (v.tile) hipLaunchKernelGGL(v.tile, r.grid, dim3(NT), 0, s, w, r.ty, r.tx, r.nt);
+  else hipLaunchKernelGGL(v.generic, r.grid, dim3(NT), 0, s, w);
   STF_CHECK_LAUNCH();
   return 0;
 }
@@ -882,12 +869,13 @@ extern "C" int stf_wgrad_reduce(float* ws, int splits, int Nout, int R, int S, i
   if (total % 8 || ((uintptr_t)ws & 15)) return STF_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const int rs = R * S;
-  const bool shape_ok = (rs == 9 || rs == 4 || rs == 1) && ((long)Nout * Cs) % 4 == 0;
-  if (shape_ok && splits <= 8) {
+  const TapReduce* tap = nullptr;
+  if (((long)Nout * Cs) % 4 == 0 && splits <= 8)
+    for (const TapReduce& t : kTapReduce)
+      if (t.rs == rs) tap = &t;
+  if (tap) {
     const unsigned blocks = (unsigned)(((long)Nout * Cs / 4 * rs + 255) / 256);
-    if (rs == 9) hipLaunchKernelGGL(wgrad_reduce_tap_kernel<9>, dim3(blocks), dim3(256), 0, s, ws, splits, Nout, Cs, out);
-    else if (rs == 4) hipLaunchKernelGGL(wgrad_reduce_tap_kernel<4>, dim3(blocks), dim3(256), 0, s, ws, splits, Nout, Cs, out);
-    else hipLaunchKernelGGL(wgrad_reduce_tap_kernel<1>, dim3(blocks), dim3(256), 0, s, ws, splits, Nout, Cs, out);
+    hipLaunchKernelGGL(tap->kernel, dim3(blocks), dim3(256), 0, s, ws, splits, Nout, Cs, out);
   } else {
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(256), 0, s, ws, splits, Nout, R,
                        S, Cs, out);

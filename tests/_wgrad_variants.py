@@ -178,7 +178,7 @@ def dy_bytes(s):
 
 
 def plan(s):
-    """csrc/wgrad.hip's plan() restated: the kernel family, its split count and chunk (pixel tiles per
+    """csrc/wgrad.hip's route_of restated: the kernel family, its split count and chunk (pixel tiles per
     split for the tile kernels, pixels for the generic ones), and the tiling the properties speak of."""
     d = fields(s)
     N, Hd, Wd, Cs, Nout, R, gb = d["N"], d["Hd"], d["Wd"], d["Cs"], d["Nout"], d["R"], d["grid_blocks"]

@@ -10,6 +10,7 @@
           consumers' operand loads could save (the backward half)
   slab    every split of the fused 3x3 weight gradient writes the same slab (L2-resident) and
           the many-split reductions are skipped: the most an in-kernel split-K fold could save
+          (needs the -DWGRAD_ONE_SLAB=1 build of tools/build_variant.sh; STF_LIB names another)
   none    no ablation (the same process layout, for the A/B)
 """
 import os
@@ -24,9 +25,11 @@ sys.path.insert(0, ROOT)
 def main():
     which = set(sys.argv[1].split(","))
     sys.argv = [os.path.join(ROOT, "bench.py")] + sys.argv[2:]
-    if "slab" in which:
-        os.environ["STF_WGRAD_ONE_SLAB"] = "1"
-        os.environ["STF_ABLATION"] = "1"
+    if "slab" in which:               # a timing-only build: bash tools/build_variant.sh wgrad_one_slab -DWGRAD_ONE_SLAB=1
+        os.environ.setdefault("STF_LIB", os.path.join(ROOT, "abvar_wgrad_one_slab", "libstfunet_hip.so"))
+        if not os.path.isfile(os.environ["STF_LIB"]):
+            sys.exit(f"no WGRAD_ONE_SLAB=1 build at {os.environ['STF_LIB']}: "
+                     "bash tools/build_variant.sh wgrad_one_slab -DWGRAD_ONE_SLAB=1")
     import bench
     from stfunet import nhwc, unet
 

@@ -1,16 +1,21 @@
 """Where the fused-tap 3x3 weight gradient's time goes: per-wave cycle buckets from the DIAG=4
 build of wgrad3x3_kernel (s_memtime around the next tile's global-load issue, the 18 MFMA steps,
 the LDS store of the staged tile -- its wait for those loads included -- and the tile barrier),
-summed over all waves of one launch (timing only: the slabs are overwritten).
-    python tools/wgrad_timeline.py [H CIN COUT [B]]      (default: 256 64 64 64)"""
+summed over all waves of one launch (timing only: the slabs are overwritten).  The shipped library
+has no DIAG kernel: make the timing-only build first,
+    bash tools/build_variant.sh wgrad_diag4 -DWGRAD_DIAG=4
+    python tools/wgrad_timeline.py [H CIN COUT [B]]      (default: 256 64 64 64)
+STF_LIB, when set, names another such build.  --nodiag times the shipped kernel instead."""
 import ctypes
 import os
 import sys
 NODIAG = "--nodiag" in sys.argv           # time the production kernel instead
-if not NODIAG:
-    os.environ["STF_WGRAD_DIAG"] = "4"
-    os.environ["STF_ABLATION"] = "1"
 HERE = os.path.dirname(os.path.abspath(__file__))
+if not NODIAG:
+    os.environ.setdefault("STF_LIB", os.path.join(os.path.dirname(HERE), "abvar_wgrad_diag4", "libstfunet_hip.so"))
+    if not os.path.isfile(os.environ["STF_LIB"]):
+        sys.exit(f"no WGRAD_DIAG=4 build at {os.environ['STF_LIB']}: "
+                 "bash tools/build_variant.sh wgrad_diag4 -DWGRAD_DIAG=4")
 sys.path[:0] = [os.path.dirname(HERE), os.path.join(os.path.dirname(HERE), "stf-unet_amd")]
 import torch
 from stfunet import nhwc
@@ -43,6 +48,8 @@ print(f"{name}: splits {splits.value} ws {nbytes.value} B; last launch {e0.elaps
       f"{2.0 * B * H * H * co * ci * 9 / e0.elapsed_time(e1) / 1e9:.0f} TF/s")
 if NODIAG:
     sys.exit(0)
+if not name.endswith(", 4>"):     # another build, or a shape the 4 x 16-tile kernel does not take (W < 16)
+    sys.exit(f"{name} is no DIAG = 4 kernel: nothing to decode (a -DWGRAD_DIAG=4 build and W >= 16 are needed)")
 RSC = 9 * ci
 rows = []
 for z in range(ci // 64):
