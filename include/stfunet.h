@@ -246,7 +246,9 @@ int stf_bn_groupsum_batch(const stf_bn_gsum_desc* descs, int count, stf_stream_t
  * g_out = NULL.  Optional per-tile column sums of dy for the bias of the
  * producing conv (bias_partial [stf_bn_bwd_apply_tiles][C]) reduced into dbias.
  * C / 8 must divide 256 and a statistics group must hold fewer than 2^31
- * 16-byte units ((M / groups) * (C / 8)): STF_EINVAL otherwise, nothing is launched. */
+ * 16-byte units ((M / groups) * (C / 8)): STF_EINVAL otherwise, nothing is launched.
+ * With bias_partial every group writes at least one row, so groups must not exceed
+ * stf_bn_bwd_apply_tiles(M, C) (a tensor of fewer than groups x 256 units): STF_EINVAL. */
 int stf_bn_bwd_apply_tiles(int64_t M, int C);
 int stf_bn_bwd_apply(const void* g, int g_cstride, const void* y, int y_cstride, int64_t M,
                      int C, int groups, const float* mask_scale, const float* mask_shift,

@@ -19,6 +19,13 @@
 //   g = dz [+ maxpool routing of dpool] masked by the ReLU (recomputed from y,
 //       or read from the saved output when the ReLU followed a residual add),
 //   dgamma = sum g*xhat, dbeta = sum g,  dy = A*g + B*y + C  (fp64 coefficients).
+//
+// Layout of the file: the finalize tails, the per-unit arithmetic, the streaming kernels (flat,
+// pooled, group-major, and the stem's three through its MaxPool(3,2,1)), then the host side: one
+// BnRoute per launch signature from bn_route -- kernel, block, grid, partial rows, refusal, under the
+// numbered rules above it -- which every streaming entry point and both row queries read.
+#include <algorithm>
+
 #include "common.h"
 #include "../../include/stfunet.h"
 #include "reduce.h"
@@ -27,20 +34,23 @@ namespace {
 
 constexpr int NT = 256;
 
-int tiles_per_group(long units_per_group, int groups) {
-  long t = (units_per_group + NT - 1) / NT;
-  const long cap = (1024 + groups - 1) / groups;    // <= FOLD16_ROWS partial rows per group
-  if (t > cap) t = cap;
-  if (t < 1) t = 1;
-  return (int)t;
-}
-
 // ------------------------------------------------------------------ finalize
 // stats: [G][T][2][C] with the first S rows of every group folded.  Grid =
 // (channel chunks of 16) x G; block = 16 channels x 16 row-lanes folding ONE
 // group.  With G > 1 the running statistics must see the G updates in order:
 // each block parks (mean, biased var) in row 0 of its group (scratch) and
-// bn_running_kernel applies them sequentially.
+// bn_running_batch_kernel applies them sequentially.
+// (mean, invstd, scale, shift) of channel c of group g from its mean and biased variance
+STF_DEV void bn_fin_store(int g, int c, int C, double mu, double var, const float* gamma, const float* beta,
+                          float eps, float* mean, float* invstd, float* scale, float* shift) {
+  const float inv = (float)(1.0 / sqrt(var + (double)eps));
+  const float sc = gamma[c] * inv;
+  mean[g * C + c] = (float)mu;
+  invstd[g * C + c] = inv;
+  scale[g * C + c] = sc;
+  shift[g * C + c] = beta[c] - (float)mu * sc;
+}
+
 // the training-mode finalize of channel c of group g from its folded (sum, sum of squares)
 STF_DEV void bn_fin_fwd_out(float* base, int g, int c, int G, int C, long Mg, double s1, double s2,
                             const float* gamma, const float* beta, float mom, float eps, float* rm, float* rv,
@@ -48,18 +58,13 @@ STF_DEV void bn_fin_fwd_out(float* base, int g, int c, int G, int C, long Mg, do
   const double mu = s1 / Mg;
   double var = s2 / Mg - mu * mu;
   if (var < 0) var = 0;
-  const float inv = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = gamma[c] * inv;
-  mean[g * C + c] = (float)mu;
-  invstd[g * C + c] = inv;
-  scale[g * C + c] = sc;
-  shift[g * C + c] = beta[c] - (float)mu * sc;
+  bn_fin_store(g, c, C, mu, var, gamma, beta, eps, mean, invstd, scale, shift);
   if (G == 1) {
     if (!rm) return;
     const double unb = Mg > 1 ? var * Mg / (Mg - 1) : var;
     rm[c] = (1.f - mom) * rm[c] + mom * (float)mu;
     rv[c] = (1.f - mom) * rv[c] + mom * (float)unb;
-  } else {                               // parked for bn_running_kernel / stf_bn_running_batch
+  } else {                               // parked for bn_running_batch_kernel
     base[c] = (float)mu;
     base[C + c] = (float)var;
   }
@@ -82,29 +87,7 @@ __global__ __launch_bounds__(stf::FOLD_NT) void bn_finalize_kernel(float* __rest
     return;
   }
   if (!lead) return;                     // eval mode: running statistics, no update
-  const double mu = rm ? rm[c] : 0.f, var = rv ? rv[c] : 1.f;
-  const float inv = (float)(1.0 / sqrt(var + (double)eps));
-  const float sc = gamma[c] * inv;
-  mean[g * C + c] = (float)mu;
-  invstd[g * C + c] = inv;
-  scale[g * C + c] = sc;
-  shift[g * C + c] = beta[c] - (float)mu * sc;
-}
-
-__global__ void bn_running_kernel(const float* __restrict__ stats, int T, int G, int C, long Mg, float mom,
-                                  float* rm, float* rv) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  float run_m = rm[c], run_v = rv[c];
-  for (int g = 0; g < G; ++g) {
-    const float* base = stats + (size_t)g * T * 2 * C;
-    const double var = base[C + c];
-    const double unb = Mg > 1 ? var * Mg / (Mg - 1) : var;
-    run_m = (1.f - mom) * run_m + mom * base[c];
-    run_v = (1.f - mom) * run_v + mom * (float)unb;
-  }
-  rm[c] = run_m;
-  rv[c] = run_v;
+  bn_fin_store(g, c, C, rm ? rm[c] : 0.f, rv ? rv[c] : 1.f, gamma, beta, eps, mean, invstd, scale, shift);
 }
 
 // dy = A g + B y + C coefficients of channel c of group g from its folded (sum g, sum g*xhat)
@@ -459,7 +442,7 @@ __global__ __launch_bounds__(PNT) void bn_bwd_reduce_pool_kernel(const uint16_t*
 // partial: [G][T][2][C] (first S rows per group folded).  coef: [G][3][C].
 // Grid = (channel chunks of 16) x G.  dgamma/dbeta are summed over the groups
 // (one BatchNorm module, G calls): with G > 1 each block parks its group's sums
-// in row 0 of the group and bn_bwd_groupsum_kernel adds them in order.
+// in row 0 of the group and bn_groupsum_batch_kernel adds them in order.
 __global__ __launch_bounds__(stf::FOLD_NT) void bn_bwd_finalize_kernel(float* __restrict__ partial, int S, int T, int G,
                                                             int C, long Mg, const float* gamma, const float* mean,
                                                             const float* invstd, float* dgamma, float* dbeta,
@@ -474,8 +457,9 @@ __global__ __launch_bounds__(stf::FOLD_NT) void bn_bwd_finalize_kernel(float* __
   if (lead) bn_fin_bwd_out(base, g, c, G, C, Mg, s1, s2, gamma, mean, invstd, dgamma, dbeta, coef);
 }
 
-// Deferred running-statistics updates of many grouped BatchNorms in one launch
-// (blockIdx.y = descriptor; same arithmetic as bn_running_kernel).
+// The running-statistics updates of grouped BatchNorms, group by group in order, many BatchNorms in
+// one launch (blockIdx.y = descriptor): stf_bn_running_batch's deferred ones, or the single
+// descriptor of a stf_bn_finalize call that was given the running statistics.
 constexpr int RUN_BATCH = 32;
 struct RunBatch { stf_bn_run_desc d[RUN_BATCH]; };
 __global__ void bn_running_batch_kernel(RunBatch b) {
@@ -495,7 +479,8 @@ __global__ void bn_running_batch_kernel(RunBatch b) {
   d.running_var[c] = run_v;
 }
 
-// Deferred dgamma/dbeta sums of many grouped BatchNorm backwards in one launch
+// The dgamma/dbeta sums over the groups of grouped BatchNorm backwards, many in one launch
+// (stf_bn_groupsum_batch, or the single descriptor of a stf_bn_bwd_finalize call that wants them)
 struct GsumBatch { stf_bn_gsum_desc d[RUN_BATCH]; };
 __global__ void bn_groupsum_batch_kernel(GsumBatch b) {
   const stf_bn_gsum_desc& d = b.d[blockIdx.y];
@@ -511,20 +496,6 @@ __global__ void bn_groupsum_batch_kernel(GsumBatch b) {
   if (d.dbeta) d.dbeta[c] = (float)db;
 }
 
-__global__ void bn_bwd_groupsum_kernel(const float* __restrict__ partial, int T, int G, int C, float* dgamma,
-                                       float* dbeta) {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= C) return;
-  double dg = 0.0, db = 0.0;
-  for (int g = 0; g < G; ++g) {
-    const float* base = partial + (size_t)g * T * 2 * C;
-    db += base[c];
-    dg += base[C + c];
-  }
-  if (dgamma) dgamma[c] = (float)dg;
-  if (dbeta) dbeta[c] = (float)db;
-}
-
 // ------------------------------------------------------------------ group-major streaming passes
 // The three element-wise passes with the grid split by statistics group (blockIdx.y = g):
 // a thread's channel chunk and its group's affine / coefficient vectors are fixed, so the loop
@@ -533,7 +504,7 @@ __global__ void bn_bwd_groupsum_kernel(const float* __restrict__ partial, int T,
 // (a block covers UPT x 256 consecutive units per iteration)
 // before it uses any (UPT x 2-3 16-B loads in flight per lane: the STF encoder's 8-67 MB tensors
 // are latency-bound at one unit per iteration).  Index math is 32-bit: units per group < 2^31
-// (checked by the launchers).  Unit u of group g: pixel g * Mg + (u >> cgs), chunk u & (CG - 1).
+// (bn_route, rule 3).  Unit u of group g: pixel g * Mg + (u >> cgs), chunk u & (CG - 1).
 constexpr int UPT = 4;
 
 template <bool RES>
@@ -665,9 +636,61 @@ __global__ __launch_bounds__(NT) void bn_bwd_apply_g_kernel(const uint16_t* g_in
   bn_block_fold(red, sb, sb, C, CG, g, bias_partial);
 }
 
-// ------------------------------------------------------------------ stem: BN backward through MaxPool(3,2,1)
-// g of the stem's BatchNorm backward gathered straight from its max pool's backward: the sum of
-// dout over the <= 4 windows whose recorded first maximum (argmax, index dy*3+dx) is this pixel,
+// ------------------------------------------------------------------ stem: BN through MaxPool(3,2,1)
+// Forward: the stem's BatchNorm + ReLU fused into its max pool (src/stf_lstm_unet.py:178-180): each
+// window tap is relu(y*scale[g]+shift[g]) rounded to the 16-bit storage -- exactly the value
+// stf_bn_act would have stored in the activation a0 -- so the pooled output and the recorded
+// argmax equal bn_act followed by stf.hip's maxpool3_fwd_kernel bit for bit, and a0 (4x the pooled
+// bytes) is never written nor read back.  g = n / ipg (per-time-step statistics of the encoder).
+// (The 3x3 scan repeats maxpool3_fwd_kernel's with the affine inside.  The two stay apart: that one
+// indexes 64-bit units and this one 32-bit, so a shared scan would take the tap's value as a callable
+// and both index types as parameters -- more lines than the 12 it saves.)
+__global__ void bn_act_maxpool3_kernel(const uint16_t* __restrict__ y, int N, int H, int W, int C, int Ho, int Wo,
+                                       int ipg, const float* __restrict__ scale, const float* __restrict__ shift,
+                                       uint16_t* __restrict__ out, uint8_t* __restrict__ argmax) {
+  // 32-bit index math (the host checks units < 2^31; 64-bit divisions made this VALU-bound)
+  const int CG = C / 8, HoWo = Ho * Wo;
+  const int units = N * HoWo * CG;
+  for (int u = blockIdx.x * NT + threadIdx.x; u < units; u += gridDim.x * NT) {
+    const int p = u / CG, cg = u - p * CG;
+    const int n = p / HoWo;
+    const int rem = p - n * HoWo;
+    const int oy = rem / Wo, ox = rem - oy * Wo;
+    float sc[8], sh[8];
+    load_pair(scale, shift, n / ipg, C, cg, sc, sh);
+    // every valid tap's value is >= 0 (ReLU) > -inf, so the first valid tap always takes the
+    // maximum and a strict '>' keeps the first maximum in row-major window order
+    float mx[8];
+    int am[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { mx[j] = -INFINITY; am[j] = 0; }
+    for (int dy = 0; dy < 3; ++dy) {
+      const int iy = 2 * oy - 1 + dy;
+      if (iy < 0 || iy >= H) continue;
+      for (int dx = 0; dx < 3; ++dx) {
+        const int ix = 2 * ox - 1 + dx;
+        if (ix < 0 || ix >= W) continue;
+        float v[8];
+        unpack8(*reinterpret_cast<const uint4*>(y + (((long)n * H + iy) * W + ix) * C + cg * 8), v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float a = round_e(fmaxf(v[j] * sc[j] + sh[j], 0.f));     // bn_act's stored value
+          if (a > mx[j]) { mx[j] = a; am[j] = dy * 3 + dx; }
+        }
+      }
+    }
+    const size_t o = (size_t)p * C + cg * 8;          // N*Ho*Wo*C may pass 2^31 (units < 2^31 only)
+    *reinterpret_cast<uint4*>(out + o) = pack8(mx);
+    if (argmax) {
+      uint32_t lo = 0, hi = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { lo |= (uint32_t)am[j] << (8 * j); hi |= (uint32_t)am[4 + j] << (8 * j); }
+      *reinterpret_cast<uint2*>(argmax + o) = make_uint2(lo, hi);
+    }
+  }
+}
+
+// Backward: g of the stem's BatchNorm gathered straight from its max pool's backward: the sum of dout over the <= 4 windows whose recorded first maximum (argmax, index dy*3+dx) is this pixel,
 // in the order stf_maxpool3s2_bwd adds them, rounded to the 16-bit storage -- so the values equal
 // maxpool3s2_bwd + the mask-recomputing reduce / apply without writing or reading d a0.  A unit is
 // a 2x2 block of input pixels (2by + a, 2bx + b): the windows (by + {0,1}, bx + {0,1}) cover all
@@ -778,20 +801,141 @@ __global__ __launch_bounds__(NT) void bn_bwd_pool3_kernel(const uint8_t* __restr
   if constexpr (!APPLY) bn_block_fold(red, sg, sgx, C, CG, g, partial);
 }
 
-}  // namespace
+// ------------------------------------------------------------------ the route
+// What a streaming launch is asked for: the shape and the options that pick a kernel or size a grid
+// (strides and pointers do neither; the entry points check those themselves).
+enum class BnOp { Act, Reduce, Apply, ActPool3, ReducePool3, ApplyPool3 };
+struct BnSig {
+  BnOp op;
+  long N;                  // images; Apply: the M pixels (H = W = 1)
+  int H, W, C, groups;
+  bool pooled = false;     // Act: the 2x2 max pool is written too; Reduce: dpool joins
+  int mask = 0;            // Reduce: mask_mode 0 / 1 / 2; Apply: 1 = the ReLU mask is recomputed
+  bool res = false;        // Act: a residual joins
+  bool bias = false;       // Apply: the per-block bias sums are wanted
+};
+enum class BnKernel {
+  None, ActG, ActGRes, ActFlat, ActFlatPool, ReduceG0, ReduceG1, ReduceG2, ReduceDpp, ReduceWin, ApplyG, ApplyGMask,
+  ActPool3, ReducePool3, ApplyPool3
+};
+struct BnRoute {
+  bool refused = true;     // STF_EINVAL, nothing is launched
+  BnKernel kernel = BnKernel::None;
+  int block = NT;
+  dim3 grid;               // grid.x == 0: nothing to do (an empty tensor)
+  int rows = 0;            // partial rows per group the launch writes (0: the kernel writes no partials)
+  int alloc = 1;           // rows the caller allocates: per group (Reduce), over all groups (Apply)
+  int cgs = 0;             // log2(C / 8) where rule 4 holds
+  long Mg = 0;             // pixels per group
+};
 
-// the backward kernels keep a thread's channel chunk fixed: C / 8 divides the block (so it is a power of two)
-static bool cg_ok(int C) { return C >= 8 && C % 8 == 0 && NT % (C / 8) == 0; }
-// the group-major kernels: that, and a group's units fit 32-bit indices
-static bool bn_g_ok(long Mg, int C) { return cg_ok(C) && Mg * (C / 8) < (1L << 31); }
-static int log2i(int v) { return 31 - __builtin_clz(v); }
-// blocks per group: about UPT units per thread, at least one, the whole grid <= cap blocks
-static int g_tiles(long upg, int groups, long cap) {
-  long t = (upg + (long)NT * UPT - 1) / ((long)NT * UPT);
-  const long per = cap / groups > 0 ? cap / groups : 1;
-  if (t > per) t = per;
-  return (int)(t < 1 ? 1 : t);
+// The rules (a unit = 8 channels of one pixel, of one 2x2 window where the 2x2 pool joins, of one
+// 2x2 block of input pixels in the stem's backward, of one pooled pixel in the stem's forward; upg =
+// units per group):
+//  1. Row budget.  A reduce writes one partial row per block and stf_bn_bwd_finalize's fp64 fold reads
+//     up to FOLD16_ROWS = 1024 rows directly (more cost it a first colsum stage), so a reduce runs
+//     ceil(upg / 256) blocks per group, at most ceil(1024 / groups), at least one: these are the rows of
+//     stf_bn_bwd_tiles.  The bias sums of the apply come under the same budget, over all groups at
+//     once: stf_bn_bwd_apply_tiles = ceil(M * (C / 8) / 256), at most 1024, at least one.
+//  2. Block cap.  A streaming grid without partial rows has at most 8192 blocks (32 per CU: enough to
+//     hide the tail, and a grid-stride loop beyond it); the flat kernels run min(ceil(units / 256),
+//     8192), the group-major ones -- UPT units per thread and iteration -- ceil(upg / (256 * UPT))
+//     blocks per group, at most max(8192 / groups, 1), at least one.  With bias sums the apply's cap is
+//     rule 1's allocation in place of 8192; more groups than allocated rows (every group needs a block
+//     of its own) is refused: groups x rows <= the allocation always.
+//  3. 2^31 units.  The group-major and stem kernels index units and pixels in 32 bits: a group of
+//     2^31 units or more is refused (the forward instead falls to the flat kernel, which divides 64-bit
+//     indices), and so is a stem tensor of 2^31 pixels.  The stem's forward adds its grid stride:
+//     units < 2^31 - 8192 * 256, and N*H*W*C < 2^34.
+//  4. Power-of-two chunks.  The backward kernels and the group-major forward keep a thread's channel
+//     chunk fixed: C / 8 divides the 256-thread block (so it is a power of two; C <= 2048).  Otherwise
+//     the backward is refused and the forward takes the flat kernel (any C % 8 == 0).
+//  5. DPP or window.  The pooled reduce puts a 2x2 window in a DPP quad, 512 threads a block (3 loads
+//     and a few dozen registers per lane against 13 loads and ~150: the window form was occupancy /
+//     latency bound at 3.4 TB/s), when 64 % (C / 8) == 0 (the grid stride then keeps a lane's pixel
+//     and chunk fixed) and the tensor has fewer than 2^31 pixels (its 32-bit index math); else one
+//     thread per window (C = 1024, 2048).  Both take rule 1's rows, counted in 256-unit blocks of
+//     windows, as one flat grid of rows x groups blocks.
+//  6. Stem grids.  The stem's reduce takes rule 1's rows for the UNPOOLED pixel count, because that is
+//     what its caller allocates (stf_bn_bwd_tiles with pooled = 0; include/stfunet.h says so), although
+//     its units are 2x2 blocks, a quarter as many: a block then meets ~64 units per iteration pair
+//     and the kernel issues two units' loads per thread to keep bytes in flight.  The stem's apply
+//     takes one unit per thread and iteration where rule 2's kernels take UPT, so it runs UPT blocks
+//     for each block of rule 2: up to UPT x 8192 in all.  The stem's forward is a flat grid of rule 2.
+constexpr long ROW_CAP = stf::FOLD16_ROWS, BLOCK_CAP = 8192, IDX_CAP = 1L << 31;
+
+BnRoute bn_route(const BnSig& s) {
+  BnRoute r;
+  if (s.groups < 1) return r;
+  const auto clamp = [](long want, long most) { return (int)std::max<long>(1, std::min(want, most)); };
+  const auto ceil_div = [](long x, long y) { return (x + y - 1) / y; };
+  const int CG = s.C / 8, Ho = (s.H - 1) / 2 + 1, Wo = (s.W - 1) / 2 + 1;
+  const long Ng = s.N / s.groups, px = s.N * s.H * s.W;
+  r.Mg = Ng * s.H * s.W;
+  const bool chunk_ok = s.C >= 8 && s.C % 8 == 0 && NT % CG == 0;                  // rule 4
+  const bool g_ok = chunk_ok && r.Mg * CG < IDX_CAP;                               // rules 3, 4
+  if (chunk_ok) r.cgs = 31 - __builtin_clz(CG);
+  const bool uneven = s.N % s.groups != 0, odd = ((s.H | s.W) & 1) != 0;
+  const long upg = Ng * CG * (s.op == BnOp::ApplyPool3 ? (long)((s.H + 1) / 2) * ((s.W + 1) / 2)
+                              : s.pooled ? (long)(s.H / 2) * (s.W / 2) : (long)s.H * s.W);
+  const auto rows_of = [&](long units) { return clamp(ceil_div(units, NT), ceil_div(ROW_CAP, s.groups)); };   // rule 1
+  const auto blocks_of = [&](long cap) { return clamp(ceil_div(upg, (long)NT * UPT), cap / s.groups); };      // rule 2
+  const auto flat = [&](long units) { return (unsigned)std::min(ceil_div(units, NT), BLOCK_CAP); };           // rule 2
+  switch (s.op) {
+    case BnOp::Act:
+      r.refused = s.C % 8 || uneven || (s.pooled && (odd || s.res));
+      if (!s.pooled && g_ok) {
+        r.kernel = s.res ? BnKernel::ActGRes : BnKernel::ActG;
+        r.grid = dim3(upg ? blocks_of(BLOCK_CAP) : 0, s.groups);
+      } else {
+        r.kernel = s.pooled ? BnKernel::ActFlatPool : BnKernel::ActFlat;
+        r.grid = dim3(flat(upg * s.groups));
+      }
+      break;
+    case BnOp::Reduce:
+      r.refused = !chunk_ok || uneven || (s.pooled ? odd || s.mask == 2 : !g_ok);
+      r.rows = r.alloc = rows_of(upg);
+      if (!s.pooled) {
+        r.kernel = s.mask == 1 ? BnKernel::ReduceG1 : s.mask == 2 ? BnKernel::ReduceG2 : BnKernel::ReduceG0;
+        r.grid = dim3(r.rows, s.groups);
+      } else {                                                                     // rule 5
+        const bool dpp = chunk_ok && 64 % CG == 0 && px < IDX_CAP;
+        r.kernel = dpp ? BnKernel::ReduceDpp : BnKernel::ReduceWin;
+        r.block = dpp ? PNT : NT;
+        r.grid = dim3(r.rows * s.groups);
+      }
+      break;
+    case BnOp::Apply:
+      r.alloc = clamp(ceil_div(px * CG, NT), ROW_CAP);
+      r.rows = blocks_of(s.bias ? r.alloc : BLOCK_CAP);
+      r.refused = !g_ok || uneven || (s.bias && (long)r.rows * s.groups > r.alloc);
+      r.kernel = s.mask ? BnKernel::ApplyGMask : BnKernel::ApplyG;
+      r.grid = dim3(r.rows, s.groups);
+      if (!s.bias) r.rows = 0;
+      break;
+    case BnOp::ActPool3: {                                                         // rules 3, 6
+      const long units = s.N * Ho * Wo * CG;
+      r.refused = s.C % 8 || uneven || units >= IDX_CAP - BLOCK_CAP * NT || px * s.C >= IDX_CAP * 8;
+      r.kernel = BnKernel::ActPool3;
+      r.grid = dim3(std::max(flat(units), 1u));
+      break;
+    }
+    case BnOp::ReducePool3:                                                        // rule 6
+      r.refused = !g_ok || uneven || px >= IDX_CAP;
+      r.kernel = BnKernel::ReducePool3;
+      r.rows = r.alloc = rows_of(r.Mg * CG);
+      r.grid = dim3(r.rows, s.groups);
+      break;
+    case BnOp::ApplyPool3:                                                         // rule 6
+      r.refused = !g_ok || uneven || px >= IDX_CAP;
+      r.kernel = BnKernel::ApplyPool3;
+      r.grid = dim3(blocks_of(BLOCK_CAP) * UPT, s.groups);
+      break;
+  }
+  return r;
 }
+
+}  // namespace
 
 // sum over tiles of partial[t][C] -> out[C] (fixed order); shared with misc.hip / loss.hip
 // launch: grid ceil(C/16), 256 threads (16 channels x 16 row-lanes)
@@ -816,8 +960,9 @@ extern "C" int stf_bn_finalize(float* stats, int tiles, int groups, int C, int64
                      scale, shift);
   STF_CHECK_LAUNCH();
   if (stats && running_mean && groups > 1) {
-    hipLaunchKernelGGL(bn_running_kernel, dim3((C + 255) / 256), dim3(256), 0, s, stats, tiles, groups, C,
-                       (long)(M / groups), momentum, running_mean, running_var);
+    RunBatch b;
+    b.d[0] = stf_bn_run_desc{stats, running_mean, running_var, M / groups, tiles, groups, C, momentum};
+    hipLaunchKernelGGL(bn_running_batch_kernel, dim3((C + 255) / 256, 1), dim3(256), 0, s, b);
     STF_CHECK_LAUNCH();
   }
   return 0;
@@ -827,82 +972,67 @@ extern "C" int stf_bn_act(const void* y, int y_cstride, int N, int H, int W, int
                           const float* scale, const float* shift, int relu, const void* res, int res_cstride,
                           const float* res_scale, const float* res_shift, void* out, int out_cstride,
                           void* pooled, stf_stream_t stream) {
-  if (C % 8 || y_cstride % 8 || out_cstride % 8 || (pooled && ((H | W) & 1)) || groups < 1 || N % groups)
-    return STF_EINVAL;
-  if (res && (res_cstride % 8 || pooled)) return STF_EINVAL;
+  const BnRoute r = bn_route({BnOp::Act, N, H, W, C, groups, pooled != nullptr, 0, res != nullptr});
+  if (r.refused || y_cstride % 8 || out_cstride % 8 || (res && res_cstride % 8)) return STF_EINVAL;
+  if (!r.grid.x) return 0;
   const int res_mode = res ? (res_scale ? 2 : 1) : 0;
-  const long M = (long)N * H * W;
-  const long units = pooled ? (long)N * (H / 2) * (W / 2) * (C / 8) : M * (C / 8);
-  long blocks = (units + NT - 1) / NT;
-  if (blocks > 8192) blocks = 8192;
-  if (blocks < 1) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  const long Mg = M / groups;
-  if (!pooled && bn_g_ok(Mg, C)) {
-    const int cgs = log2i(C / 8);
-    const dim3 grid(g_tiles(Mg * (C / 8), groups, 8192), groups);
-#define STF_AG(RES) hipLaunchKernelGGL(bn_act_g_kernel<RES>, grid, dim3(NT), 0, s, (const uint16_t*)y, y_cstride,   \
-                                       (int)Mg, cgs, scale, shift, relu, res_mode, (const uint16_t*)res, res_cstride, \
-                                       res_scale, res_shift, (uint16_t*)out, out_cstride)
-    if (res) STF_AG(true);
-    else STF_AG(false);
-#undef STF_AG
-    STF_CHECK_LAUNCH();
-    return 0;
+  const auto group_major = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, r.grid, dim3(r.block), 0, (hipStream_t)stream, (const uint16_t*)y, y_cstride, (int)r.Mg,
+                       r.cgs, scale, shift, relu, res_mode, (const uint16_t*)res, res_cstride, res_scale, res_shift,
+                       (uint16_t*)out, out_cstride);
+  };
+  const auto flat = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, r.grid, dim3(r.block), 0, (hipStream_t)stream, (const uint16_t*)y, y_cstride, (long)N, H,
+                       W, C, r.Mg, scale, shift, relu, res_mode, (const uint16_t*)res, res_cstride, res_scale,
+                       res_shift, (uint16_t*)out, out_cstride, (uint16_t*)pooled);
+  };
+  switch (r.kernel) {
+    case BnKernel::ActG: group_major(bn_act_g_kernel<false>); break;
+    case BnKernel::ActGRes: group_major(bn_act_g_kernel<true>); break;
+    case BnKernel::ActFlat: flat(bn_act_kernel<false>); break;
+    case BnKernel::ActFlatPool: flat(bn_act_kernel<true>); break;
+    default: return STF_EINVAL;
   }
-  // (res and pooled exclude each other: checked above)
-#define STF_A(POOL) hipLaunchKernelGGL(bn_act_kernel<POOL>, dim3(blocks), dim3(NT), 0, s, (const uint16_t*)y, y_cstride, \
-                                       (long)N, H, W, C, Mg, scale, shift, relu, res_mode, (const uint16_t*)res,         \
-                                       res_cstride, res_scale, res_shift, (uint16_t*)out, out_cstride, (uint16_t*)pooled)
-  if (pooled) STF_A(true);
-  else STF_A(false);
-#undef STF_A
   STF_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int stf_bn_bwd_tiles(int N, int H, int W, int C, int groups, int pooled) {
-  const long Ng = (long)N / groups;
-  const long upg = pooled ? Ng * (H / 2) * (W / 2) * (C / 8) : Ng * H * W * (C / 8);
-  return tiles_per_group(upg, groups);
+  return bn_route({BnOp::Reduce, N, H, W, C, groups, pooled != 0}).alloc;
 }
 
 extern "C" int stf_bn_bwd_reduce(const void* dz, int dz_cstride, const void* dpool, const void* y, int y_cstride,
                                  int N, int H, int W, int C, int groups, const float* scale, const float* shift,
                                  const float* mean, const float* invstd, int mask_mode, const void* mask_src,
                                  int mask_cstride, void* g_out, float* partial, stf_stream_t stream) {
-  if (!cg_ok(C) || y_cstride % 8 || (dz && dz_cstride % 8) || groups < 1 || N % groups) return STF_EINVAL;
+  const BnRoute r = bn_route({BnOp::Reduce, N, H, W, C, groups, dpool != nullptr, mask_mode});
+  if (r.refused || y_cstride % 8 || (dz && dz_cstride % 8)) return STF_EINVAL;
   if (!dz && !dpool) return STF_EINVAL;
   if (!g_out && dpool) return STF_EINVAL;            // the pooled routing must be materialized
-  if (dpool && (((H | W) & 1) || mask_mode == 2)) return STF_EINVAL;
   if (mask_mode == 2 && (!mask_src || mask_cstride % 8)) return STF_EINVAL;
-  const long Mgp = (long)N * H * W / groups;
-  if (!dpool && !bn_g_ok(Mgp, C)) return STF_EINVAL;   // >= 2^31 units in a group
-  const int tpg = stf_bn_bwd_tiles(N, H, W, C, groups, dpool != nullptr);
   hipStream_t s = (hipStream_t)stream;
-  if (!dpool) {
-    const dim3 g2(tpg, groups);
-    const int cgs = log2i(C / 8);
-#define STF_RG(MM) hipLaunchKernelGGL(bn_bwd_reduce_g_kernel<MM>, g2, dim3(NT), 0, s, (const uint16_t*)dz, dz_cstride, \
-                                      (const uint16_t*)y, y_cstride, (int)Mgp, cgs, scale, shift, mean, invstd,     \
-                                      (const uint16_t*)mask_src, mask_cstride, (uint16_t*)g_out, partial)
-    if (mask_mode == 1) STF_RG(1);
-    else if (mask_mode == 2) STF_RG(2);
-    else STF_RG(0);
-#undef STF_RG
-    STF_CHECK_LAUNCH();
-    return 0;
+  const auto group_major = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, r.grid, dim3(r.block), 0, s, (const uint16_t*)dz, dz_cstride, (const uint16_t*)y,
+                       y_cstride, (int)r.Mg, r.cgs, scale, shift, mean, invstd, (const uint16_t*)mask_src,
+                       mask_cstride, (uint16_t*)g_out, partial);
+  };
+  switch (r.kernel) {
+    case BnKernel::ReduceG0: group_major(bn_bwd_reduce_g_kernel<0>); break;
+    case BnKernel::ReduceG1: group_major(bn_bwd_reduce_g_kernel<1>); break;
+    case BnKernel::ReduceG2: group_major(bn_bwd_reduce_g_kernel<2>); break;
+    case BnKernel::ReduceDpp:
+      hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel, r.grid, dim3(r.block), 0, s, (const uint16_t*)dz, dz_cstride,
+                         (const uint16_t*)dpool, (const uint16_t*)y, y_cstride, (long)N, H, W, C, groups, r.rows, scale,
+                         shift, mean, invstd, mask_mode, (uint16_t*)g_out, partial);
+      break;
+    case BnKernel::ReduceWin:
+      hipLaunchKernelGGL(bn_bwd_reduce_win_kernel, r.grid, dim3(r.block), 0, s, (const uint16_t*)dz, dz_cstride,
+                         (const uint16_t*)dpool, (const uint16_t*)y, y_cstride, (long)N, H, W, C, groups, r.rows, scale,
+                         shift, mean, invstd, mask_mode, (const uint16_t*)mask_src, mask_cstride, (uint16_t*)g_out,
+                         partial);
+      break;
+    default: return STF_EINVAL;
   }
-  const dim3 grid(tpg * groups);
-  if (64 % (C / 8) == 0 && (long)N * H * W < (1L << 31))     // (mask_mode 2 has no pooled form: refused above)
-    hipLaunchKernelGGL(bn_bwd_reduce_pool_kernel, grid, dim3(PNT), 0, s, (const uint16_t*)dz, dz_cstride,
-                       (const uint16_t*)dpool, (const uint16_t*)y, y_cstride, (long)N, H, W, C, groups, tpg, scale,
-                       shift, mean, invstd, mask_mode, (uint16_t*)g_out, partial);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_win_kernel, grid, dim3(NT), 0, s, (const uint16_t*)dz, dz_cstride,
-                       (const uint16_t*)dpool, (const uint16_t*)y, y_cstride, (long)N, H, W, C, groups, tpg, scale,
-                       shift, mean, invstd, mask_mode, (const uint16_t*)mask_src, mask_cstride, (uint16_t*)g_out,
-                       partial);
   STF_CHECK_LAUNCH();
   return 0;
 }
@@ -917,8 +1047,9 @@ extern "C" int stf_bn_bwd_finalize(float* partial, int tiles, int groups, int C,
                      C, (long)(M / groups), gamma, mean, invstd, dgamma, dbeta, coef);
   STF_CHECK_LAUNCH();
   if (groups > 1 && (dgamma || dbeta)) {
-    hipLaunchKernelGGL(bn_bwd_groupsum_kernel, dim3((C + 255) / 256), dim3(256), 0, s, partial, tiles, groups, C,
-                       dgamma, dbeta);
+    GsumBatch b;
+    b.d[0] = stf_bn_gsum_desc{partial, dgamma, dbeta, tiles, groups, C};
+    hipLaunchKernelGGL(bn_groupsum_batch_kernel, dim3((C + 255) / 256, 1), dim3(256), 0, s, b);
     STF_CHECK_LAUNCH();
   }
   return 0;
@@ -955,54 +1086,61 @@ extern "C" int stf_bn_groupsum_batch(const stf_bn_gsum_desc* descs, int count, s
 }
 
 extern "C" int stf_bn_bwd_apply_tiles(int64_t M, int C) {
-  long t = (M * (C / 8) + NT - 1) / NT;
-  return (int)(t < 1 ? 1 : (t > 1024 ? 1024 : t));
+  return bn_route({BnOp::Apply, M, 1, 1, C, 1, false, 0, false, true}).alloc;
 }
 
 extern "C" int stf_bn_bwd_apply(const void* g, int g_cstride, const void* y, int y_cstride, int64_t M, int C,
                                 int groups, const float* mask_scale, const float* mask_shift, const float* coef,
                                 void* dy, int dy_cstride, float* bias_partial, float* dbias, stf_stream_t stream) {
-  if (!cg_ok(C) || y_cstride % 8 || dy_cstride % 8 || g_cstride % 8 || groups < 1 || M % groups) return STF_EINVAL;
+  const BnRoute r =
+      bn_route({BnOp::Apply, M, 1, 1, C, groups, false, mask_scale != nullptr, false, bias_partial != nullptr});
+  if (r.refused || y_cstride % 8 || dy_cstride % 8 || g_cstride % 8) return STF_EINVAL;
   if ((mask_scale == nullptr) != (mask_shift == nullptr)) return STF_EINVAL;
-  const long Mg = M / groups;
-  if (!bn_g_ok(Mg, C)) return STF_EINVAL;              // >= 2^31 units in a group
   hipStream_t s = (hipStream_t)stream;
-  // bias_partial rows: groups x tpg <= stf_bn_bwd_apply_tiles (the caller's allocation)
-  const int tpg = g_tiles(Mg * (C / 8), groups, bias_partial ? stf_bn_bwd_apply_tiles(M, C) : 8192);
-  const dim3 grid(tpg, groups);
-  const int cgs = log2i(C / 8);
-#define STF_AP(MM) hipLaunchKernelGGL(bn_bwd_apply_g_kernel<MM>, grid, dim3(NT), 0, s, (const uint16_t*)g, g_cstride, \
-                                      (const uint16_t*)y, y_cstride, (int)Mg, cgs, coef, mask_scale, mask_shift,     \
-                                      (uint16_t*)dy, dy_cstride, bias_partial)
-  if (mask_scale) STF_AP(true);
-  else STF_AP(false);
-#undef STF_AP
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, r.grid, dim3(r.block), 0, s, (const uint16_t*)g, g_cstride, (const uint16_t*)y,
+                       y_cstride, (int)r.Mg, r.cgs, coef, mask_scale, mask_shift, (uint16_t*)dy, dy_cstride,
+                       bias_partial);
+  };
+  switch (r.kernel) {
+    case BnKernel::ApplyG: launch(bn_bwd_apply_g_kernel<false>); break;
+    case BnKernel::ApplyGMask: launch(bn_bwd_apply_g_kernel<true>); break;
+    default: return STF_EINVAL;
+  }
   STF_CHECK_LAUNCH();
   if (bias_partial && dbias) {
-    const int S = stf::colsum_stage1(bias_partial, tpg * groups, C, s, 1, stf::FOLD16_ROWS);
+    const int S = stf::colsum_stage1(bias_partial, r.rows * groups, C, s, 1, stf::FOLD16_ROWS);
     hipLaunchKernelGGL(stf_tile_sum_kernel, dim3((C + 15) / 16), dim3(stf::FOLD_NT), 0, s, bias_partial, S, C, dbias);
     STF_CHECK_LAUNCH();
   }
   return 0;
 }
 
-// BatchNorm backward of the STF stem through its MaxPool(3,2,1) (src/stf_lstm_unet.py:178-180):
-// the incoming gradient is the pooled output's (dout [N][Ho][Wo][C]) routed by the forward's
-// argmax (stf_bn_act_maxpool3s2 / stf_maxpool3s2_fwd), never materialized at full size.
-// Partials as stf_bn_bwd_reduce (rows per group = stf_bn_bwd_tiles(N, H, W, C, groups, 0)).
+// The STF stem's BatchNorm + ReLU inside its MaxPool(3,2,1) (src/stf_lstm_unet.py:178-180)
+extern "C" int stf_bn_act_maxpool3s2(const void* y, int N, int H, int W, int C, int groups, const float* scale,
+                                     const float* shift, void* out, void* argmax, stf_stream_t stream) {
+  const BnRoute r = bn_route({BnOp::ActPool3, N, H, W, C, groups});
+  if (r.refused || !y || !scale || !shift || !out) return STF_EINVAL;
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+  hipLaunchKernelGGL(bn_act_maxpool3_kernel, r.grid, dim3(r.block), 0, (hipStream_t)stream, (const uint16_t*)y, N, H,
+                     W, C, Ho, Wo, N / groups, scale, shift, (uint16_t*)out, (uint8_t*)argmax);
+  STF_CHECK_LAUNCH();
+  return 0;
+}
+
+// BatchNorm backward of the STF stem through that max pool: the incoming gradient is the pooled
+// output's (dout [N][Ho][Wo][C]) routed by the forward's argmax (stf_bn_act_maxpool3s2 /
+// stf_maxpool3s2_fwd), never materialized at full size.  Partials as stf_bn_bwd_reduce (rule 6).
 extern "C" int stf_bn_bwd_reduce_pool3(const void* argmax, const void* dout, const void* y, int N, int H, int W,
                                        int C, int groups, const float* scale, const float* shift,
                                        const float* mean, const float* invstd, float* partial,
                                        stf_stream_t stream) {
-  const long Mg = (long)N * H * W / (groups > 0 ? groups : 1);
-  if (!argmax || !dout || !y || !partial || groups < 1 || N % groups || !bn_g_ok(Mg, C) ||
-      (long)N * H * W >= (1L << 31))
-    return STF_EINVAL;
-  const int tpg = stf_bn_bwd_tiles(N, H, W, C, groups, 0);
+  const BnRoute r = bn_route({BnOp::ReducePool3, N, H, W, C, groups});
+  if (r.refused || !argmax || !dout || !y || !partial) return STF_EINVAL;
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-  hipLaunchKernelGGL(bn_bwd_pool3_kernel<false>, dim3(tpg, groups), dim3(NT), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(bn_bwd_pool3_kernel<false>, r.grid, dim3(r.block), 0, (hipStream_t)stream,
                      (const uint8_t*)argmax, (const uint16_t*)dout, (const uint16_t*)y, H, W, Ho, Wo, N / groups,
-                     log2i(C / 8), scale, shift, mean, invstd, (const float*)nullptr, (uint16_t*)nullptr, partial);
+                     r.cgs, scale, shift, mean, invstd, (const float*)nullptr, (uint16_t*)nullptr, partial);
   STF_CHECK_LAUNCH();
   return 0;
 }
@@ -1011,15 +1149,11 @@ extern "C" int stf_bn_bwd_reduce_pool3(const void* argmax, const void* dout, con
 extern "C" int stf_bn_bwd_apply_pool3(const void* argmax, const void* dout, const void* y, int N, int H, int W,
                                       int C, int groups, const float* scale, const float* shift, const float* coef,
                                       void* dy, stf_stream_t stream) {
-  const long Mg = (long)N * H * W / (groups > 0 ? groups : 1);
-  if (!argmax || !dout || !y || !coef || !dy || groups < 1 || N % groups || !bn_g_ok(Mg, C) ||
-      (long)N * H * W >= (1L << 31))
-    return STF_EINVAL;
+  const BnRoute r = bn_route({BnOp::ApplyPool3, N, H, W, C, groups});
+  if (r.refused || !argmax || !dout || !y || !coef || !dy) return STF_EINVAL;
   const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-  const long units = (long)(N / groups) * ((H + 1) / 2) * ((W + 1) / 2) * (C / 8);
-  const dim3 grid(g_tiles(units, groups, 8192) * UPT, groups);
-  hipLaunchKernelGGL(bn_bwd_pool3_kernel<true>, grid, dim3(NT), 0, (hipStream_t)stream, (const uint8_t*)argmax,
-                     (const uint16_t*)dout, (const uint16_t*)y, H, W, Ho, Wo, N / groups, log2i(C / 8), scale, shift,
+  hipLaunchKernelGGL(bn_bwd_pool3_kernel<true>, r.grid, dim3(r.block), 0, (hipStream_t)stream, (const uint8_t*)argmax,
+                     (const uint16_t*)dout, (const uint16_t*)y, H, W, Ho, Wo, N / groups, r.cgs, scale, shift,
                      (const float*)nullptr, (const float*)nullptr, coef, (uint16_t*)dy, (float*)nullptr);
   STF_CHECK_LAUNCH();
   return 0;

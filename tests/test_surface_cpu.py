@@ -74,7 +74,7 @@ def test_library_rejects_bad_shapes_without_launch():
     assert lib.stf_igemm(ctypes.byref(a), None) == 100001
     assert lib.stf_bn_act(None, 8, 1, 4, 4, 12, 1, None, None, 1, None, 0, None, None, None, 12, None,
                           None) == 100001
-    # stem BN+ReLU+MaxPool(3,2,1) (stf.hip bn_act_maxpool3): its unit index is 32-bit,
+    # stem BN+ReLU+MaxPool(3,2,1) (bn.hip bn_act_maxpool3): its unit index is 32-bit,
     # so a launch whose N*Ho*Wo*C/8 units (plus the grid stride) reach 2^31 is refused up front;
     # the largest accepted one writes through 64-bit offsets.  Fake non-null pointers: nothing runs.
     fake = ctypes.c_void_p(1 << 20)
