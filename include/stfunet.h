@@ -655,6 +655,37 @@ int stf_boundary_metrics(const uint8_t* mask, const int64_t* target, int B, int 
 int stf_edt_sq(const uint8_t* sites, const uint8_t* where, int B, int H, int W, int32_t* d2,
                void* scratch, stf_stream_t stream);
 
+/* ---------------------------------------------------------------- connected components
+ * Labels and component post-processing of binary masks (INTEGRATION.md 2.2 states the definition).
+ * Every image of mask uint8 [B][H][W] is labelled on its own: foreground is mask != 0, connectivity
+ * is 4 (edge neighbours) or 8 (edges and corners), pixels outside the image are background.
+ * Additive to ABI v17.  Limits: 1 <= B, 1 <= H, W <= 4096, B * H * W < 2^31.  STF_EINVAL (nothing
+ * launched) for a NULL required pointer, a size outside the limits, a connectivity other than 4 or
+ * 8, min_size < 0, counts without target, out == mask, a labels or num that is not 4-byte aligned,
+ * or a scratch, counts or target that is not 8-byte aligned (mask and out may sit at any byte).
+ * No entry point allocates, reads back or waits between workgroups; the number of launches is
+ * fixed; the results are integers and the same bits from run to run.  All outputs are OVERWRITTEN
+ * and may arrive uninitialised, the scratch too.
+ *
+ * Bytes of the scratch either call needs, a multiple of 8 (0 outside the limits). */
+size_t stf_ccl_scratch_bytes(int B, int H, int W);
+/* labels int32 [B][H][W]: 0 on the background, 1..n on the components, numbered per image in raster
+ * order of each component's first pixel (scipy.ndimage.label's numbering); num int32 [B] = n. */
+int stf_ccl_label(const uint8_t* mask, int B, int H, int W, int connectivity, int32_t* labels, int32_t* num,
+                  void* scratch, stf_stream_t stream);
+/* out uint8 [B][H][W] (may not alias mask): a foreground pixel keeps its own value when its
+ * component passes, every other pixel is 0.  A component passes when its area is >= min_size and,
+ * with keep_largest != 0, it is the image's largest (equal areas: the one whose first pixel comes
+ * first in raster order); min_size applies first, so an image whose largest component is below it
+ * comes out empty.  With target (int64 [B][H][W], or NULL) and counts (int64 [B][3], or NULL):
+ * counts = (|P' & T|, |P'|, |T|) of the filtered mask with stf_predict_mask's rules (P' = out != 0,
+ * T = target > 0, pixels whose target equals ignore_index left out of all three; ignore_index < 0:
+ * none).  The mask is labelled with those pixels in.  num (or NULL) int32 [B]: the number of
+ * components BEFORE filtering. */
+int stf_ccl_filter(const uint8_t* mask, const int64_t* target, int B, int H, int W, int connectivity,
+                   int keep_largest, int64_t min_size, int64_t ignore_index, uint8_t* out, int64_t* counts,
+                   int32_t* num, void* scratch, stf_stream_t stream);
+
 /* ---------------------------------------------------------------- PK maps (extended Tofts)
  * pk_fitting.py ToftsModelFitter, all fp32.  The host builds
  * the reference's constant tables exactly as the reference does (pk_fitting.py:

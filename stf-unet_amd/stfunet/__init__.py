@@ -9,10 +9,12 @@ from . import _lib  # noqa: F401
 from . import predict  # noqa: F401  (the module; its loop is stfunet.predict.predict)
 from .loss import criterion  # noqa: F401
 from .optim import clip_grad_norm_  # noqa: F401
-from .predict import boundary_metrics, distance_transform_sq, image_metrics, overlay, predict_masks  # noqa: F401
+from .predict import (boundary_metrics, connected_components, distance_transform_sq, filter_components,  # noqa: F401
+                      image_metrics, overlay, predict_masks)
 from .resize import upsample_logits  # noqa: F401
 from .stf_lstm_unet import STFLSTMUNet  # noqa: F401
 from .unet import UNet  # noqa: F401
 
-__all__ = ["STFLSTMUNet", "UNet", "boundary_metrics", "clip_grad_norm_", "criterion", "distance_transform_sq",
-           "image_metrics", "overlay", "predict", "predict_masks", "upsample_logits"]
+__all__ = ["STFLSTMUNet", "UNet", "boundary_metrics", "clip_grad_norm_", "connected_components", "criterion",
+           "distance_transform_sq", "filter_components", "image_metrics", "overlay", "predict", "predict_masks",
+           "upsample_logits"]

@@ -10,6 +10,9 @@ gfx950 kernels of ``csrc/predict.hip``:
 * ``boundary_metrics``  per-image Hausdorff distance, HD95 and ASSD of mask against target
   (MedPy's ``hd`` / ``hd95`` / ``assd`` at isotropic spacing; ``csrc/boundary.hip``), and
   ``distance_transform_sq``, the exact squared Euclidean distance transform underneath
+* ``connected_components`` / ``filter_components``  per-image component labels in
+  ``scipy.ndimage.label``'s numbering, and the usual clean-up of a predicted mask (keep the largest
+  component, drop components below a size) with the counts of the cleaned mask (``csrc/ccl.hip``)
 * ``overlay``         the mask painted over a frame (``save_overlay_from_tensor``, test.py:52-82,
   through ``merge_images``, train_utils/merge_tumor_images.py:94-120)
 * ``predict``         the loop: eval mode, ``no_grad``, ``preprocess_input``, forward, masks,
@@ -198,6 +201,91 @@ def distance_transform_sq(sites, where=None):
     return d2
 
 
+CONNECTIVITIES = (4, 8)
+
+
+def _check_components(connectivity, min_size=0):
+    if isinstance(connectivity, bool) or connectivity not in CONNECTIVITIES:
+        raise ValueError(f"connectivity must be 4 (edge neighbours) or 8 (edges and corners), not {connectivity!r}")
+    if isinstance(min_size, bool) or not isinstance(min_size, numbers.Integral) or not 0 <= min_size < 1 << 63:
+        raise ValueError(f"min_size must be an integer >= 0, not {min_size!r}")
+    return int(connectivity), int(min_size)
+
+
+def _ccl_scratch(B, H, W, device):
+    nbytes = load().stf_ccl_scratch_bytes(B, H, W)
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def connected_components(mask, connectivity=8):
+    """``(labels int32 [B, H, W], num int32 [B])``: the connected components of every image of
+    ``mask`` (``[B, H, W]`` bool or any integer, nonzero = foreground), each image on its own.
+
+    ``connectivity`` 4 joins edge neighbours, 8 edges and corners; pixels outside the image are
+    background.  ``labels`` is 0 on the background and 1..n on the components, numbered per image in
+    raster order of each component's first pixel -- ``scipy.ndimage.label(mask[b],
+    generate_binary_structure(2, 1 or 2))`` -- and ``num[b]`` is n.  Integers only: the same bits
+    from run to run."""
+    B, H, W = _check_bhw(mask, "mask")
+    connectivity, _ = _check_components(connectivity)
+    mask = _as_u8(mask.detach(), "mask")
+    _device_only(mask, "connected_components")
+    labels = torch.empty((B, H, W), dtype=torch.int32, device=mask.device)
+    num = torch.empty((B,), dtype=torch.int32, device=mask.device)
+    if B:
+        scratch = _ccl_scratch(B, H, W, mask.device)
+        with torch.cuda.device(mask.device):
+            call("stf_ccl_label", _p(mask), B, H, W, connectivity, _p(labels), _p(num), _p(scratch), stream())
+    return labels, num
+
+
+def _filter(mask, target, keep_largest, min_size, connectivity, ignore_index):
+    """``stf_ccl_filter`` on a checked uint8 device mask: (filtered mask, counts or None, num int32 [B])."""
+    B, H, W = mask.shape
+    dev = mask.device
+    out = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    num = torch.empty((B,), dtype=torch.int32, device=dev)
+    counts = None
+    if target is not None:
+        target = target.detach().to(device=dev, dtype=torch.int64).contiguous()
+        counts = torch.empty((B, 3), dtype=torch.int64, device=dev)
+    if B:
+        scratch = _ccl_scratch(B, H, W, dev)
+        with torch.cuda.device(dev):
+            call("stf_ccl_filter", _p(mask), _p(target), B, H, W, connectivity, int(bool(keep_largest)), min_size,
+                 -1 if ignore_index is None else ignore_index, _p(out), _p(counts), _p(num), _p(scratch), stream())
+    return out, counts, num
+
+
+def filter_components(mask, keep_largest=False, min_size=0, connectivity=8, target=None, ignore_index=None):
+    """``uint8 [B, H, W]``: ``mask`` (``[B, H, W]`` bool or any integer, nonzero = foreground) with the
+    components that do not pass set to 0, each image on its own.
+
+    A component (``connected_components``) passes when its area is at least ``min_size`` pixels and,
+    with ``keep_largest``, it is the largest of its image; of several largest ones the one whose first
+    pixel comes first in raster order is kept (``np.argmax(np.bincount(labels.ravel())[1:])``).
+    ``min_size`` applies first: an image whose largest component is smaller comes out empty.  A pixel
+    that stays keeps its own value, so a mask of class ids keeps them (integer masks wider than
+    uint8 are reduced to 0 / 1 first).  With ``target`` (``[B, H, W]`` integers) returns ``(mask,
+    counts)``, ``counts`` the ``int64 [B, 3]`` (|P&T|, |P|, |T|) of the filtered mask with
+    ``predict_masks``' rules (``ignore_index`` pixels left out of all three, but labelled like any
+    other pixel).  With neither option set the output equals the input; the call still runs the
+    kernels."""
+    B, H, W = _check_bhw(mask, "mask")
+    connectivity, min_size = _check_components(connectivity, min_size)
+    if target is not None:
+        if tuple(target.shape) != (B, H, W):
+            raise ValueError(f"target {tuple(target.shape)} does not match the mask's {(B, H, W)}")
+        if target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
+            raise ValueError(f"target must be an integer tensor, not {target.dtype}")
+    mask = _as_u8(mask.detach(), "mask")
+    _device_only(mask, "filter_components")
+    if target is not None:
+        _device_only(target, "filter_components")
+    out, counts, _ = _filter(mask, target, keep_largest, min_size, connectivity, ignore_index)
+    return out if target is None else (out, counts)
+
+
 def overlay(frames, mask, color=(0, 255, 0), alpha=0.5, paint=1):
     """``uint8 [B, H, W, 3]``: ``frames`` normalised to 0..255 per image, with ``color`` blended
     at ``alpha`` into the pixels where the mask is non-zero (``paint=1``) or zero (``paint=0``).
@@ -246,7 +334,7 @@ def shown_frame(inputs):
 
 def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5, ignore_index=None,
             output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5, paint=1, keep_masks=False,
-            boundary=False, spacing=1.0):
+            boundary=False, spacing=1.0, keep_largest=False, min_size=0, connectivity=8):
     """The inference loop of test.py:146-176 for any batch size.
 
     The loader yields ``inputs`` or ``(inputs, targets)`` (targets may be None).  Returns a dict:
@@ -258,18 +346,26 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
     ``boundary=True`` adds, when targets came, ``boundary_metrics`` of every mask against its target:
     per-image ``hd`` / ``hd95`` / ``assd`` (NaN where the mask or the target is empty), their means
     over the defined images ``mean_hd`` / ``mean_hd95`` / ``mean_assd`` (NaN when there is none) and
-    ``num_boundary``, the number of defined images -- all device tensors, no host synchronisation."""
+    ``num_boundary``, the number of defined images -- all device tensors, no host synchronisation.
+    ``keep_largest=True`` and / or ``min_size > 0`` clean every batch's mask with
+    ``filter_components`` (at ``connectivity``) before anything consumes it: ``dice`` / ``iou`` come
+    from the filter's counts, and the boundary metrics, the overlays and ``masks`` see the filtered
+    mask.  The result then gains ``num_components``, an int64 device tensor in slice order: the
+    components of each mask before filtering.  No device-to-host copy is added.  With both options
+    off nothing of this runs and the result has no such key."""
     if rule not in RULES:
         raise ValueError(f"unknown rule {rule!r} (one of {sorted(RULES)})")
     color = _check_paint(color, alpha, paint)
     if boundary:
         spacing = _check_spacing(spacing)
+    connectivity, min_size = _check_components(connectivity, min_size)
+    components = bool(keep_largest) or min_size > 0
     from .engine import preprocess_input
     if output_dir is not None:
         from PIL import Image
         os.makedirs(output_dir, exist_ok=True)
     model.eval()
-    all_counts, all_boundary, masks, idx = [], [], [], 0
+    all_counts, all_boundary, all_num, masks, idx = [], [], [], [], 0
     with torch.no_grad():
         for batch in data_loader:
             inputs, targets = batch if isinstance(batch, (tuple, list)) else (batch, None)
@@ -279,11 +375,17 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
                 targets = targets.to(device)
                 mask, counts = predict_masks(outputs, rule, channel, threshold, target=targets,
                                              ignore_index=ignore_index)
+                if components:
+                    mask, counts, num = _filter(mask, targets, keep_largest, min_size, connectivity, ignore_index)
+                    all_num.append(num)
                 all_counts.append(counts)
                 if boundary:
                     all_boundary.append(boundary_metrics(mask, targets, ignore_index, spacing))
             else:
                 mask = predict_masks(outputs, rule, channel, threshold)
+                if components:
+                    mask, _, num = _filter(mask, None, keep_largest, min_size, connectivity, None)
+                    all_num.append(num)
             if output_dir is not None:
                 pics = overlay(shown_frame(inputs), mask, color, alpha, paint).cpu().numpy()
                 for j, pic in enumerate(pics):
@@ -301,6 +403,8 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
             res[k] = v
             res["mean_" + k] = None if v is None else torch.nanmean(v)
         res["num_boundary"] = None if not all_boundary else (~torch.isnan(res["hd"])).sum()
+    if components:
+        res["num_components"] = torch.cat(all_num).to(torch.int64) if all_num else None
     if keep_masks:
         res["masks"] = masks
     return res

@@ -20,6 +20,14 @@ with counts (one kernel) and ``overlay`` (two kernels) on the same shape.  Where
 host computation a user would otherwise run (mask to the host, ``binary_erosion``,
 ``distance_transform_edt``, ``np.percentile`` per slice) is timed on ``--host-images`` images of
 each regime.  Prints one JSON line.
+
+``--components`` measures the connected-component post-processing (csrc/ccl.hip) at the same shape on
+three inputs: ``realistic`` (one disc per image plus scattered specks), ``percolation`` (a random
+mask at density 0.593, the site-percolation threshold: the most merging) and ``checkerboard`` under
+connectivity 4 (the most components, no merging).  Per input: ``connected_components``
+(stf_ccl_label), ``filter_components`` with a target and ``keep_largest`` (stf_ccl_filter), and for
+scale ``boundary_metrics`` on the same mask; once ``predict_masks`` with counts; and the ``predict``
+loop (UNet, two batches) with the options off and on.  Prints one JSON line.
 """
 import argparse
 import json
@@ -40,6 +48,7 @@ ap.add_argument("--size", type=int, default=256)
 ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--boundary", action="store_true", help="measure boundary_metrics instead")
+ap.add_argument("--components", action="store_true", help="measure the connected-component kernels instead")
 ap.add_argument("--host-images", type=int, default=8, help="images per regime of the scipy host timing")
 args = ap.parse_args()
 if not torch.cuda.is_available():
@@ -139,6 +148,77 @@ def timed(fn, iters):
     torch.cuda.synchronize()
     return a.elapsed_time(b) * 1e3 / iters           # us per call
 
+
+def component_masks():
+    """{name: (mask uint8, target int64, connectivity)} [B, H, W], seeded."""
+    g = torch.Generator().manual_seed(3)
+    yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
+    P, T = torch.zeros(B, H, W, dtype=torch.uint8), torch.zeros(B, H, W, dtype=torch.int64)
+    for b in range(B):
+        r = int(torch.randint(H // 12, H // 6, (1,), generator=g))
+        cy, cx = (int(v) for v in torch.randint(H // 4, 3 * H // 4, (2,), generator=g))
+        dy, dx = (int(v) for v in torch.randint(-4, 5, (2,), generator=g))
+        P[b] = ((yy - cy - dy) ** 2 + (xx - cx - dx) ** 2 <= r * r).to(torch.uint8)
+        T[b] = ((yy - cy) ** 2 + (xx - cx) ** 2 <= r * r).long()
+        sy, sx = torch.randint(0, H - 1, (40,), generator=g), torch.randint(0, W - 1, (40,), generator=g)
+        P[b, sy, sx] = 1                                   # 40 specks: single pixels, half of them 2 x 2
+        P[b, sy[:20] + 1, sx[:20]] = P[b, sy[:20], sx[:20] + 1] = P[b, sy[:20] + 1, sx[:20] + 1] = 1
+    perc = (torch.rand(B, H, W, generator=g) < 0.593).to(torch.uint8)
+    board = ((yy + xx) % 2 == 0).to(torch.uint8).expand(B, H, W).contiguous()
+    return {"realistic": (P, T, 8), "percolation": (perc, T, 8), "checkerboard": (board, T, 4)}
+
+
+if args.components:
+    import time
+    from stfunet import boundary_metrics, connected_components, filter_components
+    from stfunet.predict import predict
+    from stfunet.unet import UNet
+    data = {k: (m.cuda(), t.cuda(), c) for k, (m, t, c) in component_masks().items()}
+    legs = [("predict_masks_with_counts", lambda: predict_masks(logits, args.rule, 0, 0.5, target=target))]
+    for k, (m, t, c) in data.items():
+        legs += [(f"label_{k}", lambda m=m, c=c: connected_components(m, c)),
+                 (f"filter_{k}", lambda m=m, t=t, c=c: filter_components(m, True, 0, c, target=t)),
+                 (f"boundary_{k}", lambda m=m, t=t: boundary_metrics(m, t))]
+    for _, fn in legs:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name, _ in legs}
+    for _ in range(args.rounds):
+        for name, fn in legs:
+            us[name].append(timed(fn, args.iters) / B)
+    model = UNet(in_channels=8, num_classes=2).cuda()
+    loader = [(inputs.view(B, 1, 8, H, W), data["realistic"][1])] * 2
+
+    def loop_ms(flag):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        predict(model, loader, torch.device("cuda"), keep_largest=flag)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for flag in (False, True, False, True):
+        loop_ms(flag)
+    loop = {False: [], True: []}
+    for _ in range(args.rounds):
+        for flag in (False, True):
+            loop[flag].append(loop_ms(flag))
+    loop_med = {k: statistics.median(v) for k, v in loop.items()}
+    med = {k: statistics.median(v) for k, v in us.items()}
+    num = {k: connected_components(m, c)[1].double() for k, (m, _, c) in data.items()}
+    print(json.dumps({
+        "tool": "bench_predict", "leg": "components", "shape": [B, H, W], "rounds": args.rounds, "iters": args.iters,
+        "us_per_image": {k: round(v, 3) for k, v in med.items()},
+        "us_per_image_min_max": {k: [round(min(v), 3), round(max(v), 3)] for k, v in us.items()},
+        "mean_components": {k: float(v.mean()) for k, v in num.items()},
+        "foreground_fraction": {k: float(m.bool().double().mean()) for k, (m, _, _) in data.items()},
+        "predict_loop_ms": {"images": 2 * B, "plain": round(loop_med[False], 3),
+                            "keep_largest": round(loop_med[True], 3),
+                            "plain_min_max": [round(min(loop[False]), 3), round(max(loop[False]), 3)],
+                            "keep_largest_min_max": [round(min(loop[True]), 3), round(max(loop[True]), 3)],
+                            "added_us_per_image": round((loop_med[True] - loop_med[False]) * 1e3 / (2 * B), 2)},
+    }))
+    sys.exit(0)
 
 if args.boundary:
     from stfunet import boundary_metrics
