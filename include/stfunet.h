@@ -613,6 +613,12 @@ int stf_eval_counts_sm(const float* logits, const float* probs, const int64_t* t
 int stf_predict_mask(const float* logits, const int64_t* target, int B, int K, int64_t HW, int rule,
                      int channel, float threshold, int64_t ignore, uint8_t* mask, int64_t* counts,
                      stf_stream_t stream);
+/* The same pass on a plane of probabilities (rule "threshold"): mask = probs[:, channel] > threshold
+ * with no sigmoid; a NaN compares false, +inf is over every finite threshold.  Everything else
+ * (target, counts, ignore, the refusals) as stf_predict_mask.  An entry point of its own: rule
+ * codes other than 0 / 1 stay refused there. */
+int stf_predict_threshold(const float* probs, const int64_t* target, int B, int K, int64_t HW, int channel,
+                          float threshold, int64_t ignore, uint8_t* mask, int64_t* counts, stf_stream_t stream);
 /* Bytes of the scratch the overlay needs for B images of HW pixels (per-image min / max rows). */
 size_t stf_predict_overlay_scratch_bytes(int B, int64_t HW);
 /* The mask painted over one fp32 [H][W] plane per image, out uint8 [B][H][W][3].  Image b's
@@ -630,6 +636,29 @@ size_t stf_predict_overlay_scratch_bytes(int B, int64_t HW);
 int stf_predict_overlay(const float* frames, int64_t batch_stride, const uint8_t* mask, int B, int H,
                         int W, int c0, int c1, int c2, float alpha, int paint, uint8_t* out,
                         void* scratch, stf_stream_t stream);
+
+/* ---------------------------------------------------------------- mirror test-time augmentation
+ * The work around the model forwards of mirror TTA (INTEGRATION.md 2.2 states the definition):
+ * additive to ABI v17, fp32 only, one launch each, nothing allocated, no atomics (the same bits
+ * from run to run).  flip: bit 0 reverses the last axis W, bit 1 the axis before it, H.
+ *
+ * y = x with W and / or H reversed in each of `planes` contiguous fp32 [H][W] planes (torch.flip,
+ * bit for bit; flip 0 is a copy).  STF_EINVAL (nothing launched) for a NULL pointer, x == y, a size
+ * below 1, flip outside 0..3 or planes * H * W >= 2^31. */
+int stf_flip_planes(const float* x, int64_t planes, int H, int W, int flip, float* y, stf_stream_t stream);
+/* One view's logits [B][K][H][W] (computed on the flipped input) -> probabilities per pixel, every
+ * fp32 operation rounded on its own (no FMA):
+ *   rule 0 (argmax)   m = max_k z, e_k = expf(z_k - m), s = e_0 + e_1 + ... in ascending k,
+ *                     p_k = e_k / s: K planes;
+ *   rule 1 (sigmoid)  1 / (1 + expf(-z[channel])), stf_predict_mask's arithmetic: one plane;
+ * un-flipped (the value computed at (y, x) lands at (H-1-y if bit 1 else y, W-1-x if bit 0 else x))
+ * and folded into acc [B][K or 1][H][W]: acc = p when first != 0 (acc may arrive uninitialised),
+ * acc = acc + p otherwise; with views_if_last > 0 the stored value is that sum / (float)views_if_last
+ * (one fp32 divide).  The K logit planes are read once, acc is read (unless first) and written once.
+ * STF_EINVAL (nothing launched) for a NULL pointer, K outside 1..16, channel outside [0, K), a rule
+ * other than 0 / 1, flip outside 0..3, a size below 1, views_if_last < 0 or B * K * H * W >= 2^31. */
+int stf_tta_accumulate(const float* logits, int B, int K, int H, int W, int rule, int channel, int flip,
+                       int first, int views_if_last, float* acc, stf_stream_t stream);
 
 /* ---------------------------------------------------------------- boundary metrics
  * Per-image Hausdorff distance, its 95th percentile and the average symmetric surface distance of

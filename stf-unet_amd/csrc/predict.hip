@@ -49,6 +49,8 @@ STF_DEV void argmax_step(float x, unsigned k, float& best, unsigned& pred) {
 }
 // rule 1: torch.sigmoid in fp32, then > threshold (a NaN compares false)
 STF_DEV unsigned sigmoid_over(float x, float thr) { return 1.f / (1.f + expf(-x)) > thr ? 1u : 0u; }
+// rule 2: the plane holds probabilities already (a mean over views): > threshold, a NaN compares false
+STF_DEV unsigned over(float x, float thr) { return x > thr ? 1u : 0u; }
 
 STF_DEV void count(unsigned m, long t, long ignore, unsigned (&c)[3]) {
   if (ignore >= 0 && t == ignore) return;
@@ -58,7 +60,7 @@ STF_DEV void count(unsigned m, long t, long ignore, unsigned (&c)[3]) {
   c[2] += g;
 }
 
-// RULE 0 reads the K class planes, RULE 1 the one plane `logits` already points at (K == 1 here)
+// RULE 0 reads the K class planes, RULE 1 and 2 the one plane `logits` already points at (K == 1 here)
 template <int RULE, bool QUAD>
 __global__ __launch_bounds__(MT) void predict_mask_kernel(const float* __restrict__ logits, long img_stride,
                                                           const int64_t* __restrict__ target, int K, long HW,
@@ -84,6 +86,8 @@ __global__ __launch_bounds__(MT) void predict_mask_kernel(const float* __restric
       if (RULE == 1) {
         m0 = sigmoid_over(best.x, thr); m1 = sigmoid_over(best.y, thr);
         m2 = sigmoid_over(best.z, thr); m3 = sigmoid_over(best.w, thr);
+      } else if (RULE == 2) {
+        m0 = over(best.x, thr); m1 = over(best.y, thr); m2 = over(best.z, thr); m3 = over(best.w, thr);
       } else {
         for (int k = 1; k < K; ++k) {
           const float4 v = *reinterpret_cast<const float4*>(x + (long)k * HW + q * 4);
@@ -105,6 +109,8 @@ __global__ __launch_bounds__(MT) void predict_mask_kernel(const float* __restric
       unsigned m = 0;
       if (RULE == 1) {
         m = sigmoid_over(best, thr);
+      } else if (RULE == 2) {
+        m = over(best, thr);
       } else {
         for (int k = 1; k < K; ++k) argmax_step(x[(long)k * HW + i], k, best, m);
       }
@@ -256,12 +262,10 @@ void launch_mask(bool quad, int grid, hipStream_t s, const float* x, long img_st
                        K, HW, thr, ignore, bpi, mask, counts);
 }
 
-}  // namespace
-
-extern "C" int stf_predict_mask(const float* logits, const int64_t* target, int B, int K, int64_t HW, int rule,
-                                int channel, float threshold, int64_t ignore, uint8_t* mask, int64_t* counts,
-                                stf_stream_t stream) {
-  if (B < 0 || HW < 0 || K < 1 || K > MAXK || channel < 0 || channel >= K || (rule != 0 && rule != 1) || !logits ||
+// rules 0 and 1 are stf_predict_mask's, rule 2 stf_predict_threshold's
+int predict_mask(const float* logits, const int64_t* target, int B, int K, int64_t HW, int rule, int channel,
+                 float threshold, int64_t ignore, uint8_t* mask, int64_t* counts, stf_stream_t stream) {
+  if (B < 0 || HW < 0 || K < 1 || K > MAXK || channel < 0 || channel >= K || rule < 0 || rule > 2 || !logits ||
       !mask || (target && !counts))
     return STF_EINVAL;
   if (B == 0) return 0;
@@ -280,11 +284,29 @@ extern "C" int stf_predict_mask(const float* logits, const int64_t* target, int 
   if (rule == 0)
     launch_mask<0>(quad, grid, s, logits, img_stride, target, K, (long)HW, threshold, (long)ignore, bpi, mask,
                    (unsigned long long*)counts);
-  else
+  else if (rule == 1)
     launch_mask<1>(quad, grid, s, logits + (long)channel * HW, img_stride, target, 1, (long)HW, threshold,
+                   (long)ignore, bpi, mask, (unsigned long long*)counts);
+  else
+    launch_mask<2>(quad, grid, s, logits + (long)channel * HW, img_stride, target, 1, (long)HW, threshold,
                    (long)ignore, bpi, mask, (unsigned long long*)counts);
   STF_CHECK_LAUNCH();
   return 0;
+}
+
+}  // namespace
+
+extern "C" int stf_predict_mask(const float* logits, const int64_t* target, int B, int K, int64_t HW, int rule,
+                                int channel, float threshold, int64_t ignore, uint8_t* mask, int64_t* counts,
+                                stf_stream_t stream) {
+  if (rule != 0 && rule != 1) return STF_EINVAL;
+  return predict_mask(logits, target, B, K, HW, rule, channel, threshold, ignore, mask, counts, stream);
+}
+
+extern "C" int stf_predict_threshold(const float* probs, const int64_t* target, int B, int K, int64_t HW, int channel,
+                                     float threshold, int64_t ignore, uint8_t* mask, int64_t* counts,
+                                     stf_stream_t stream) {
+  return predict_mask(probs, target, B, K, HW, 2, channel, threshold, ignore, mask, counts, stream);
 }
 
 extern "C" size_t stf_predict_overlay_scratch_bytes(int B, int64_t HW) {

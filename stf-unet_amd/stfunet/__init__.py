@@ -10,11 +10,11 @@ from . import predict  # noqa: F401  (the module; its loop is stfunet.predict.pr
 from .loss import criterion  # noqa: F401
 from .optim import clip_grad_norm_  # noqa: F401
 from .predict import (boundary_metrics, connected_components, distance_transform_sq, filter_components,  # noqa: F401
-                      image_metrics, overlay, predict_masks)
+                      flip_planes, image_metrics, overlay, predict_masks, predict_tta, tta_probabilities)
 from .resize import upsample_logits  # noqa: F401
 from .stf_lstm_unet import STFLSTMUNet  # noqa: F401
 from .unet import UNet  # noqa: F401
 
 __all__ = ["STFLSTMUNet", "UNet", "boundary_metrics", "clip_grad_norm_", "connected_components", "criterion",
-           "distance_transform_sq", "filter_components", "image_metrics", "overlay", "predict", "predict_masks",
-           "upsample_logits"]
+           "distance_transform_sq", "filter_components", "flip_planes", "image_metrics", "overlay", "predict",
+           "predict_masks", "predict_tta", "tta_probabilities", "upsample_logits"]

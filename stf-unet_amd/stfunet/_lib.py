@@ -179,6 +179,9 @@ _SIGS = {
     "stf_predict_overlay_scratch_bytes": (c_size_t, [c_int, c_int64]),
     "stf_predict_overlay": (c_int, [P, c_int64, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, P, P,
                                     P]),
+    "stf_predict_threshold": (c_int, [P, P, c_int, c_int, c_int64, c_int, c_float, c_int64, P, P, P]),
+    "stf_flip_planes": (c_int, [P, c_int64, c_int, c_int, c_int, P, P]),
+    "stf_tta_accumulate": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "stf_boundary_scratch_bytes": (c_size_t, [c_int, c_int, c_int]),
     "stf_boundary_metrics": (c_int, [P, P, c_int, c_int, c_int, c_int64, P, P, P, P]),
     "stf_edt_sq": (c_int, [P, P, c_int, c_int, c_int, P, P, P]),

@@ -17,6 +17,9 @@ gfx950 kernels of ``csrc/predict.hip``:
   through ``merge_images``, train_utils/merge_tumor_images.py:94-120)
 * ``predict``         the loop: eval mode, ``no_grad``, ``preprocess_input``, forward, masks,
   counts when the loader yields targets, one PNG per slice when ``output_dir`` is given
+* ``flip_planes`` / ``tta_probabilities`` / ``predict_tta``  mirror test-time augmentation: the model
+  on the batch and its flipped copies, the un-flipped class probabilities averaged in a fixed order
+  (``csrc/tta.hip``), and ``predict``'s loop with each batch's mask taken from that mean
 
 ``predict(model, loader, device, rule="sigmoid", channel=0, paint=0)`` reproduces test.py bit for
 bit (it thresholds channel 0 and inverts the mask before painting, :75-76), except that the
@@ -33,7 +36,9 @@ import torch
 from ._lib import call, load, stream
 from .nhwc import _p
 
-RULES = {"argmax": 0, "sigmoid": 1}
+RULES = {"argmax": 0, "sigmoid": 1, "threshold": 2}
+VIEWS = {"none": 0, "w": 1, "h": 2, "hw": 3}        # flip code: bit 0 = the last axis W, bit 1 = H
+ALL_VIEWS = ("none", "w", "h", "hw")
 MAX_CLASSES = 16
 MAX_SIDE = 4096                  # boundary metrics / distance transform: 1 <= H, W <= 4096
 MAX_PIXELS = 1 << 31             # ... and B * H * W below this
@@ -62,6 +67,8 @@ def predict_masks(outputs, rule="argmax", channel=0, threshold=0.5, target=None,
 
     ``rule="argmax"``: the class id of the first maximum (``torch.argmax(outputs, 1)``).
     ``rule="sigmoid"``: ``torch.sigmoid(outputs[:, channel]) > threshold`` in fp32.
+    ``rule="threshold"``: ``outputs[:, channel] > threshold`` with no sigmoid, for planes that hold
+    probabilities already (``tta_probabilities``); a NaN compares false.
     With ``target`` (``[B, H, W]`` integers) also returns ``int64 [B, 3]`` per-image counts
     (|P&T|, |P|, |T|) with P = mask > 0 and T = target > 0; pixels whose target equals
     ``ignore_index`` are left out of all three."""
@@ -85,9 +92,14 @@ def predict_masks(outputs, rule="argmax", channel=0, threshold=0.5, target=None,
     if target is not None:
         target = target.detach().to(device=x.device, dtype=torch.int64).contiguous()
         counts = torch.empty((B, 3), dtype=torch.int64, device=x.device)
+    ignore = -1 if ignore_index is None else ignore_index
     with torch.cuda.device(x.device):
-        call("stf_predict_mask", _p(x), _p(target), B, K, H * W, RULES[rule], channel, threshold,
-             -1 if ignore_index is None else ignore_index, _p(mask), _p(counts), stream())
+        if rule == "threshold":
+            call("stf_predict_threshold", _p(x), _p(target), B, K, H * W, channel, threshold, ignore, _p(mask),
+                 _p(counts), stream())
+        else:
+            call("stf_predict_mask", _p(x), _p(target), B, K, H * W, RULES[rule], channel, threshold, ignore,
+                 _p(mask), _p(counts), stream())
     return mask if target is None else (mask, counts)
 
 
@@ -332,29 +344,126 @@ def shown_frame(inputs):
     raise ValueError(f"model input must be [B, T, C, H, W] or [B, C, H, W], not {tuple(inputs.shape)}")
 
 
-def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5, ignore_index=None,
-            output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5, paint=1, keep_masks=False,
-            boundary=False, spacing=1.0, keep_largest=False, min_size=0, connectivity=8):
-    """The inference loop of test.py:146-176 for any batch size.
+def parse_views(tta):
+    """The view set of a ``tta`` / ``views`` argument: None for ``None`` / ``False`` (off),
+    ``("none", "w", "h", "hw")`` for ``True``, else the given non-empty tuple or list of distinct
+    views, in its order."""
+    if tta is None or tta is False:
+        return None
+    if tta is True:
+        return ALL_VIEWS
+    if not isinstance(tta, (tuple, list)):
+        raise ValueError(f"views must be True, None / False or a tuple of views from {ALL_VIEWS}, not {tta!r}")
+    views = tuple(tta)
+    if not views:
+        raise ValueError("the view set is empty")
+    for v in views:
+        if not isinstance(v, str):
+            raise ValueError(f"a view must be a string from {ALL_VIEWS}, not {v!r}")
+        if v not in VIEWS:
+            raise ValueError(f"unknown view {v!r} (one of {ALL_VIEWS})")
+    if len(set(views)) != len(views):
+        raise ValueError(f"the view set repeats a view: {views}")
+    return views
 
-    The loader yields ``inputs`` or ``(inputs, targets)`` (targets may be None).  Returns a dict:
-    ``num`` slices seen and, when targets came, per-image ``dice`` / ``iou`` (float64 device
-    tensors in slice order) with their means ``mean_dice`` / ``mean_iou`` (None otherwise).
-    With ``output_dir`` every slice is written as ``{prefix}_{idx}.png`` (RGB, ``idx`` the running
-    slice index); that is the loop's only device-to-host copy, one per batch.  ``keep_masks=True``
-    adds ``masks``, the list of each batch's ``uint8 [B, H, W]`` device mask.
-    ``boundary=True`` adds, when targets came, ``boundary_metrics`` of every mask against its target:
-    per-image ``hd`` / ``hd95`` / ``assd`` (NaN where the mask or the target is empty), their means
-    over the defined images ``mean_hd`` / ``mean_hd95`` / ``mean_assd`` (NaN when there is none) and
-    ``num_boundary``, the number of defined images -- all device tensors, no host synchronisation.
-    ``keep_largest=True`` and / or ``min_size > 0`` clean every batch's mask with
-    ``filter_components`` (at ``connectivity``) before anything consumes it: ``dice`` / ``iou`` come
-    from the filter's counts, and the boundary metrics, the overlays and ``masks`` see the filtered
-    mask.  The result then gains ``num_components``, an int64 device tensor in slice order: the
-    components of each mask before filtering.  No device-to-host copy is added.  With both options
-    off nothing of this runs and the result has no such key."""
+
+def _check_view(view):
+    if not isinstance(view, str) or view not in VIEWS:
+        raise ValueError(f"unknown view {view!r} (one of {ALL_VIEWS})")
+    return VIEWS[view]
+
+
+def flip_planes(x, view):
+    """``x`` (fp32 device tensor, at least 2-D; made contiguous first if it is not) with the axes of
+    ``view`` reversed in every ``H x W`` plane of its last two dimensions: a new tensor, bit for bit
+    ``torch.flip`` (``"w"``: dims (-1,), ``"h"``: (-2,), ``"hw"``: both, ``"none"``: a copy)."""
+    code = _check_view(view)
+    if x.dim() < 2:
+        raise ValueError(f"flip_planes needs at least 2 dimensions, not {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"flip_planes takes an fp32 tensor, not {x.dtype}")
+    if x.numel() >= MAX_PIXELS:
+        raise ValueError(f"flip_planes: the tensor must hold fewer than 2^31 elements, not {x.numel()}")
+    _device_only(x, "flip_planes")
+    x = x.detach().contiguous()
+    y = torch.empty_like(x)
+    if x.numel():
+        H, W = x.shape[-2:]
+        with torch.cuda.device(x.device):
+            call("stf_flip_planes", _p(x), x.numel() // (H * W), H, W, code, _p(y), stream())
+    return y
+
+
+def _check_tta_rule(rule):
+    if rule not in ("argmax", "sigmoid"):
+        raise ValueError(f"test-time augmentation averages the probabilities of rule 'argmax' (softmax) or "
+                         f"'sigmoid', not {rule!r}")
+
+
+def _accumulate(logits, rule, channel, view, acc, first, views_if_last):
+    """One ``stf_tta_accumulate`` launch on checked tensors; allocates ``acc`` when it is None."""
+    B, K, H, W = logits.shape
+    if acc is None:
+        acc = torch.empty((B, K if rule == "argmax" else 1, H, W), dtype=torch.float32, device=logits.device)
+    if logits.numel():
+        with torch.cuda.device(logits.device):
+            call("stf_tta_accumulate", _p(logits), B, K, H, W, RULES[rule], channel, VIEWS[view], int(first),
+                 views_if_last, _p(acc), stream())
+    return acc
+
+
+def tta_probabilities(model, inputs, views=True, rule="argmax", channel=0):
+    """Mean class probabilities of ``model`` over mirrored views of ``inputs`` (``[B, C, H, W]`` or
+    ``[B, T, C, H, W]``, already in the model's input format): fp32 ``[B, K, h, w]`` for
+    ``rule="argmax"`` (softmax over the K classes), ``[B, 1, h, w]`` for ``rule="sigmoid"`` (the
+    sigmoid of ``channel``).
+
+    For every view in order the model runs on the flipped copy, and one pass turns its logits into
+    probabilities, un-flips them and adds them to the sum; the pass of the last view divides by the
+    number of views.  One ``flip_planes`` launch (none for ``"none"``) and one accumulate launch per
+    view around the forwards, a fixed order and no atomics: the same bits from run to run, no host
+    synchronisation.  Runs in eval mode under ``no_grad`` and puts the model's training mode back."""
+    views = parse_views(views)
+    if views is None:
+        raise ValueError("tta_probabilities needs a view set (True or a tuple of views)")
+    _check_tta_rule(rule)
+    _device_only(inputs, "tta_probabilities")
+    x = inputs.detach().float()
+    was_training = model.training
+    model.eval()
+    acc = None
+    try:
+        with torch.no_grad():
+            for i, view in enumerate(views):
+                z = model(x if view == "none" else flip_planes(x, view))
+                if isinstance(z, dict):
+                    z = z["out"]
+                if z.dim() != 4:
+                    raise ValueError(f"logits must be [B, K, H, W], not {tuple(z.shape)}")
+                if not 1 <= z.shape[1] <= MAX_CLASSES:
+                    raise ValueError(f"1..{MAX_CLASSES} classes are supported, not {z.shape[1]}")
+                if not 0 <= channel < z.shape[1]:
+                    raise ValueError(f"channel {channel} is outside [0, {z.shape[1]})")
+                if z.numel() >= MAX_PIXELS:
+                    raise ValueError(f"logits must hold fewer than 2^31 elements, not {z.numel()}")
+                z = z.detach().float().contiguous()
+                acc = _accumulate(z, rule, channel, view, acc, i == 0, len(views) if i == len(views) - 1 else 0)
+    finally:
+        model.train(was_training)
+    return acc
+
+
+def _predict(model, data_loader, device, views, keep_probs, rule="argmax", channel=0, threshold=0.5,
+             ignore_index=None, output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5, paint=1,
+             keep_masks=False, boundary=False, spacing=1.0, keep_largest=False, min_size=0, connectivity=8):
+    """The loop of ``predict`` (``views`` None) and ``predict_tta`` (``views`` a checked view set)."""
     if rule not in RULES:
         raise ValueError(f"unknown rule {rule!r} (one of {sorted(RULES)})")
+    mask_rule, mask_channel = rule, channel
+    if views is not None:
+        _check_tta_rule(rule)
+        if rule == "sigmoid":                       # the mean probability is one plane: mean > threshold
+            mask_rule, mask_channel = "threshold", 0
     color = _check_paint(color, alpha, paint)
     if boundary:
         spacing = _check_spacing(spacing)
@@ -365,15 +474,20 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
         from PIL import Image
         os.makedirs(output_dir, exist_ok=True)
     model.eval()
-    all_counts, all_boundary, all_num, masks, idx = [], [], [], [], 0
+    all_counts, all_boundary, all_num, masks, probs, idx = [], [], [], [], [], 0
     with torch.no_grad():
         for batch in data_loader:
             inputs, targets = batch if isinstance(batch, (tuple, list)) else (batch, None)
             inputs = preprocess_input(inputs, model).to(device)
-            outputs = model(inputs)
+            if views is None:
+                outputs = model(inputs)
+            else:
+                outputs = tta_probabilities(model, inputs, views, rule, channel)
+                if keep_probs:
+                    probs.append(outputs)
             if targets is not None:
                 targets = targets.to(device)
-                mask, counts = predict_masks(outputs, rule, channel, threshold, target=targets,
+                mask, counts = predict_masks(outputs, mask_rule, mask_channel, threshold, target=targets,
                                              ignore_index=ignore_index)
                 if components:
                     mask, counts, num = _filter(mask, targets, keep_largest, min_size, connectivity, ignore_index)
@@ -382,7 +496,7 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
                 if boundary:
                     all_boundary.append(boundary_metrics(mask, targets, ignore_index, spacing))
             else:
-                mask = predict_masks(outputs, rule, channel, threshold)
+                mask = predict_masks(outputs, mask_rule, mask_channel, threshold)
                 if components:
                     mask, _, num = _filter(mask, None, keep_largest, min_size, connectivity, None)
                     all_num.append(num)
@@ -407,4 +521,51 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
         res["num_components"] = torch.cat(all_num).to(torch.int64) if all_num else None
     if keep_masks:
         res["masks"] = masks
+    if keep_probs:
+        res["probs"] = probs
     return res
+
+
+def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5, ignore_index=None,
+            output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5, paint=1, keep_masks=False,
+            boundary=False, spacing=1.0, keep_largest=False, min_size=0, connectivity=8):
+    """The inference loop of test.py:146-176 for any batch size.
+
+    The loader yields ``inputs`` or ``(inputs, targets)`` (targets may be None).  Returns a dict:
+    ``num`` slices seen and, when targets came, per-image ``dice`` / ``iou`` (float64 device
+    tensors in slice order) with their means ``mean_dice`` / ``mean_iou`` (None otherwise).
+    With ``output_dir`` every slice is written as ``{prefix}_{idx}.png`` (RGB, ``idx`` the running
+    slice index); that is the loop's only device-to-host copy, one per batch.  ``keep_masks=True``
+    adds ``masks``, the list of each batch's ``uint8 [B, H, W]`` device mask.
+    ``boundary=True`` adds, when targets came, ``boundary_metrics`` of every mask against its target:
+    per-image ``hd`` / ``hd95`` / ``assd`` (NaN where the mask or the target is empty), their means
+    over the defined images ``mean_hd`` / ``mean_hd95`` / ``mean_assd`` (NaN when there is none) and
+    ``num_boundary``, the number of defined images -- all device tensors, no host synchronisation.
+    ``keep_largest=True`` and / or ``min_size > 0`` clean every batch's mask with
+    ``filter_components`` (at ``connectivity``) before anything consumes it: ``dice`` / ``iou`` come
+    from the filter's counts, and the boundary metrics, the overlays and ``masks`` see the filtered
+    mask.  The result then gains ``num_components``, an int64 device tensor in slice order: the
+    components of each mask before filtering.  No device-to-host copy is added.  With both options
+    off nothing of this runs and the result has no such key.
+    ``predict_tta`` is this loop with mirror test-time augmentation."""
+    return _predict(model, data_loader, device, None, False, rule, channel, threshold, ignore_index, output_dir,
+                    prefix, color, alpha, paint, keep_masks, boundary, spacing, keep_largest, min_size, connectivity)
+
+
+def predict_tta(model, data_loader, device, tta=True, keep_probs=False, **options):
+    """``predict`` with mirror test-time augmentation: ``options`` are ``predict``'s keywords.
+
+    Each batch's mask comes from ``tta_probabilities(model, inputs, tta, rule, channel)``: its
+    first maximum over the classes for ``rule="argmax"``, ``mean > threshold`` for ``rule="sigmoid"``
+    (``predict_masks``' rule ``"threshold"``).  Counts, ``ignore_index``, the component filter, the
+    boundary metrics, the overlays (painted on the un-flipped frame) and ``keep_masks`` see that mask
+    as ``predict``'s see the plain one.  ``tta``: ``True`` for ``("none", "w", "h", "hw")`` or a
+    non-empty tuple of distinct views, applied in the order given; ``None`` / ``False`` is plain
+    ``predict``, which then runs nothing of this.  ``keep_probs=True`` (only with ``tta`` on) adds
+    ``probs``, the list of each batch's mean probabilities."""
+    views = parse_views(tta)
+    if keep_probs and views is None:
+        raise ValueError("keep_probs needs test-time augmentation (tta)")
+    if views is None:
+        return predict(model, data_loader, device, **options)
+    return _predict(model, data_loader, device, views, bool(keep_probs), **options)

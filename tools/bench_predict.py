@@ -28,6 +28,14 @@ connectivity 4 (the most components, no merging).  Per input: ``connected_compon
 (stf_ccl_label), ``filter_components`` with a target and ``keep_largest`` (stf_ccl_filter), and for
 scale ``boundary_metrics`` on the same mask; once ``predict_masks`` with counts; and the ``predict``
 loop (UNet, two batches) with the options off and on.  Prints one JSON line.
+
+``--tta`` measures the work mirror test-time augmentation adds around the forwards (csrc/tta.hip) at
+the same shape: ``flip_planes`` of the 64 x 8 x 256^2 input per view, and ``stf_tta_accumulate`` on
+64 x K x 256^2 logits for K = 2 and 16 (a middle view: K planes read, K planes read and written; the
+sigmoid rule: one plane read, one read and written), each as achieved GB/s against those bytes, with
+``predict_masks`` (K planes read, one byte written per pixel) in the same rounds for scale.  Then the
+``predict_tta`` loop (UNet, one batch, four views) against four plain forwards of the same batch.
+Prints one JSON line.
 """
 import argparse
 import json
@@ -49,6 +57,7 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--boundary", action="store_true", help="measure boundary_metrics instead")
 ap.add_argument("--components", action="store_true", help="measure the connected-component kernels instead")
+ap.add_argument("--tta", action="store_true", help="measure the test-time-augmentation kernels instead")
 ap.add_argument("--host-images", type=int, default=8, help="images per regime of the scipy host timing")
 args = ap.parse_args()
 if not torch.cuda.is_available():
@@ -167,6 +176,73 @@ def component_masks():
     board = ((yy + xx) % 2 == 0).to(torch.uint8).expand(B, H, W).contiguous()
     return {"realistic": (P, T, 8), "percolation": (perc, T, 8), "checkerboard": (board, T, 4)}
 
+
+if args.tta:
+    import time
+    from stfunet import flip_planes, predict_tta
+    from stfunet._lib import call, stream
+    from stfunet.unet import UNet
+    HW = H * W
+    legs = []                                             # (name, fn, bytes per call)
+    for v in ("none", "w", "h", "hw"):
+        legs.append((f"flip_{v}", lambda v=v: flip_planes(inputs, v), 2 * inputs.numel() * 4))
+    for k in (2, 16):
+        z = torch.randn(B, k, H, W, device="cuda") * 2
+        acc = torch.zeros(B, k, H, W, device="cuda")
+        acc1 = torch.zeros(B, 1, H, W, device="cuda")
+
+        def accumulate(code, rule=0, z=z, acc=acc, k=k):
+            call("stf_tta_accumulate", z.data_ptr(), B, k, H, W, rule, 0, code, 0, 0, acc.data_ptr(), stream())
+
+        for code, v in ((0, "none"), (1, "w"), (3, "hw")):
+            legs.append((f"accumulate_K{k}_{v}", lambda code=code, f=accumulate: f(code), 3 * k * B * HW * 4))
+        legs.append((f"accumulate_sigmoid_K{k}_hw", lambda f=accumulate, a=acc1: f(3, 1, acc=a), 3 * B * HW * 4))
+        legs.append((f"predict_masks_K{k}", lambda z=z: predict_masks(z, "argmax"), B * HW * (4 * k + 1)))
+    for _, fn, _ in legs:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name, _, _ in legs}
+    for _ in range(args.rounds):
+        for name, fn, _ in legs:
+            us[name].append(timed(fn, args.iters))
+    med = {k: statistics.median(v) for k, v in us.items()}
+    nbytes = {name: n for name, _, n in legs}
+    model = UNet(in_channels=8, num_classes=2).cuda().eval()
+    raw = inputs.view(B, 1, 8, H, W)
+
+    def four_forwards():
+        with torch.no_grad():
+            for _ in range(4):
+                model(inputs)
+
+    def loop_ms(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    loops = {"four_forwards": four_forwards, "predict_tta": lambda: predict_tta(model, [raw], torch.device("cuda")),
+             "predict_plain": lambda: predict_tta(model, [raw], torch.device("cuda"), tta=None)}
+    for fn in list(loops.values()) * 2:
+        loop_ms(fn)
+    loop = {k: [] for k in loops}
+    for _ in range(args.rounds):
+        for k, fn in loops.items():
+            loop[k].append(loop_ms(fn))
+    lmed = {k: statistics.median(v) for k, v in loop.items()}
+    print(json.dumps({
+        "tool": "bench_predict", "leg": "tta", "batch": B, "size": [H, W], "rounds": args.rounds, "iters": args.iters,
+        "us_per_call": {k: round(v, 1) for k, v in med.items()},
+        "us_min_max": {k: [round(min(v), 1), round(max(v), 1)] for k, v in us.items()},
+        "bytes": nbytes,
+        "GBps": {k: round(nbytes[k] / v / 1e3, 1) for k, v in med.items()},
+        "loop_ms": {k: round(v, 3) for k, v in lmed.items()},
+        "loop_ms_min_max": {k: [round(min(v), 3), round(max(v), 3)] for k, v in loop.items()},
+        "tta_over_four_forwards_ms": round(lmed["predict_tta"] - lmed["four_forwards"], 3),
+    }))
+    sys.exit(0)
 
 if args.components:
     import time
