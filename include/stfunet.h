@@ -329,6 +329,31 @@ int stf_loss_mc_fwd(const float* logits, const int64_t* target, int N, int H, in
 int stf_loss_mc_bwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
                     const float* class_weight, int ignore_index, int dice, const float* terms,
                     const float* grad_out, float* dlogits, stf_stream_t stream);
+/* The option criterion with a focal cross-entropy and a Tversky overlap, classes in 1..16 (additive:
+ * the ABI version stays 17; csrc/loss_focal.hip).  Arguments, terms layout and scratch size are those
+ * of stf_loss_mc_fwd / stf_loss_mc_bwd (stf_loss_ft_scratch_floats == stf_loss_mc_scratch_floats, 0
+ * for classes outside 1..16), with three floats after dice.  With q = p_t and nll = -log q:
+ *   CE_f = sum m w[t] (1-q)^focal_gamma nll / Wsum      (Wsum = sum m w[t]; focal_gamma = 0 is CE)
+ *   FP = sum m p - I, FN = sum m t - I                  per (image, class)
+ *   D    = (2I + eps) / (2I + 2 tversky_alpha FP + 2 tversky_beta FN + eps)
+ *                                                       (alpha = beta = 1/2 is Dice; D = 1 for an image
+ *                                                        with every pixel masked)
+ *   loss = CE_f + (dice ? 1 - mean_k mean_b D : 0)
+ * 1-q is formed from the other classes' exponentials, so it keeps its precision where q rounds to 1;
+ * where it is exactly 0 and focal_gamma > 0 the pixel's cross-entropy term and gradient are 0.
+ * Masked pixels get a stored 0, an all-masked batch a NaN loss, as above.  STF_EINVAL (nothing
+ * launched) for the refusals of stf_loss_mc_fwd / stf_loss_mc_bwd, a focal_gamma that is negative or
+ * not finite, a tversky_alpha or tversky_beta that is negative or not finite, or both 0 (also with
+ * dice == 0).  Deterministic (fixed summation order, no atomics), no host read-back. */
+int stf_loss_ft_scratch_floats(int N, int classes);
+int stf_loss_ft_fwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
+                    const float* class_weight, int ignore_index, int dice, float focal_gamma,
+                    float tversky_alpha, float tversky_beta, float* terms, float* loss,
+                    stf_stream_t stream);
+int stf_loss_ft_bwd(const float* logits, const int64_t* target, int N, int H, int W, int classes,
+                    const float* class_weight, int ignore_index, int dice, float focal_gamma,
+                    float tversky_alpha, float tversky_beta, const float* terms,
+                    const float* grad_out, float* dlogits, stf_stream_t stream);
 
 /* ---------------------------------------------------------------- optimizer
  * torch.optim.AdamW(lr, betas, eps, weight_decay) (train.py:230-237) over one

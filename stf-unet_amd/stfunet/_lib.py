@@ -146,6 +146,11 @@ _SIGS = {
     "stf_loss_mc_scratch_floats": (c_int, [c_int, c_int]),
     "stf_loss_mc_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P]),
     "stf_loss_mc_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, P, P, P, P]),
+    "stf_loss_ft_scratch_floats": (c_int, [c_int, c_int]),
+    "stf_loss_ft_fwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_float, c_float, c_float, P, P,
+                                P]),
+    "stf_loss_ft_bwd": (c_int, [P, P, c_int, c_int, c_int, c_int, P, c_int, c_int, c_float, c_float, c_float, P, P,
+                                P, P]),
     "stf_adamw": (c_int, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_float, c_float, c_float,
                           P]),
     "stf_adamw_dev": (c_int, [P, P, P, P, c_int64, P, c_float, c_float, c_float, c_float, P]),

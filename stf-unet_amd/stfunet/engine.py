@@ -313,10 +313,10 @@ def evaluate(model, data_loader, device, num_classes):
 
 def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler=None,
                     print_freq=10, scaler=None, *, loss_weight=None, dice=True, ignore_index=-100,
-                    max_grad_norm=None):
+                    max_grad_norm=None, focal_gamma=0.0, tversky=None):
     """The reference's loop (its positional signature and defaults); the keyword-only
-    ``loss_weight`` / ``dice`` / ``ignore_index`` go to ``criterion`` (``ignore_index=255`` for
-    batches whose targets ``collate_fn`` padded to a common size).
+    ``loss_weight`` / ``dice`` / ``ignore_index`` / ``focal_gamma`` / ``tversky`` go to ``criterion``
+    (``ignore_index=255`` for batches whose targets ``collate_fn`` padded to a common size).
 
     ``max_grad_norm`` (an addition; ``None``: the loop as it was): clip every step's gradients by
     their global L2 norm.  A ``stfunet.optim.AdamW`` gets it as its param-group option for the epoch
@@ -332,7 +332,7 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
     try:
         return _train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler,
                                 print_freq, scaler, loss_weight, dice, ignore_index, max_grad_norm, fused_clip,
-                                clip_grad_norm_)
+                                clip_grad_norm_, focal_gamma, tversky)
     finally:
         if fused_clip:
             for group, value in zip(optimizer.param_groups, previous):
@@ -340,7 +340,8 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
 
 
 def _train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler, print_freq, scaler,
-                     loss_weight, dice, ignore_index, max_grad_norm, fused_clip, clip_grad_norm_):
+                     loss_weight, dice, ignore_index, max_grad_norm, fused_clip, clip_grad_norm_, focal_gamma,
+                     tversky):
     model.train()
     logger = MetricLogger(delimiter="  ")
     logger.add_meter("lr", SmoothedValue(window_size=1, fmt="{value:.6f}"))
@@ -352,7 +353,7 @@ def _train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, 
         target = target.to(device)
         with torch.amp.autocast(device_type="cuda", enabled=scaler is not None):
             loss = criterion(model(image), target, loss_weight=loss_weight, num_classes=num_classes, dice=dice,
-                             ignore_index=ignore_index)
+                             ignore_index=ignore_index, focal_gamma=focal_gamma, tversky=tversky)
         optimizer.zero_grad()
         grad_norm = None
         if scaler is not None:

@@ -23,7 +23,21 @@ The reference's three options run on the device as well (``stf_loss_opt_fwd`` /
 
 Logits of 5 to 16 classes take the many-class kernels (``stf_loss_mc_fwd`` / ``stf_loss_mc_bwd``:
 the same formula, the options as run-time arguments); more than 16 is a ValueError.
+
+Two additions for lesion-sized foregrounds, after the reference's parameters (``stf_loss_ft_fwd`` /
+``stf_loss_ft_bwd``, one kernel family for 1 to 16 classes, every option above included):
+
+* ``focal_gamma > 0``: each pixel's cross-entropy term is multiplied by ``(1 - p_t) ** focal_gamma``
+  (``sum w[t] (1-p_t)^gamma nll / sum w[t]``: the denominator is unchanged), which down-weights the
+  mass of easy pixels.  0 is the plain cross-entropy.
+* ``tversky=(alpha, beta)``: the Tversky index ``(2I + eps) / (2I + 2 alpha FP + 2 beta FN + eps)``
+  in place of Dice, with ``FP = sum p - I`` and ``FN = sum t - I`` per (image, class); ``beta > alpha``
+  penalises missed foreground more than false alarms.  ``(0.5, 0.5)`` is Dice.  Needs ``dice=True``.
+
+With ``focal_gamma == 0`` and ``tversky is None`` the three routes above are taken exactly as before.
 """
+import math
+
 import torch
 
 from . import _lib
@@ -34,17 +48,21 @@ from ._lib import call, stream
 class _CEDice(torch.autograd.Function):
     """CE + Dice.  Up to four classes: the reference's default configuration (no class weights, no
     ignored target value, Dice on) calls the default entry points, anything else the option ones.
-    Five to sixteen classes: the many-class entry points in every configuration."""
+    Five to sixteen classes: the many-class entry points in every configuration.  A focal exponent
+    or a Tversky pair (``focal`` = (gamma, alpha, beta), else None): the focal / Tversky entry points
+    for every class count."""
 
     @staticmethod
-    def forward(ctx, logits, target, weight, ignore_index, dice):
+    def forward(ctx, logits, target, weight, ignore_index, dice, focal=None):
         logits = logits.detach().contiguous().float()
         target = target.contiguous()
         if target.dtype != torch.int64:
             target = target.long()
         N, K, H, W = logits.shape
         assert target.shape == (N, H, W), f"target {tuple(target.shape)} vs logits {tuple(logits.shape)}"
-        if K > 4:
+        if focal is not None:
+            scratch, fwd, ctx.bwd = "stf_loss_ft_scratch_floats", "stf_loss_ft_fwd", "stf_loss_ft_bwd"
+        elif K > 4:
             scratch, fwd, ctx.bwd = "stf_loss_mc_scratch_floats", "stf_loss_mc_fwd", "stf_loss_mc_bwd"
         elif weight is None and dice and ignore_index < 0:
             scratch, fwd, ctx.bwd, ctx.opts = "stf_loss_scratch_floats", "stf_loss_fwd", "stf_loss_bwd", ()
@@ -52,6 +70,8 @@ class _CEDice(torch.autograd.Function):
             scratch, fwd, ctx.bwd = "stf_loss_opt_scratch_floats", "stf_loss_opt_fwd", "stf_loss_opt_bwd"
         if ctx.bwd != "stf_loss_bwd":
             ctx.opts = (_p(weight) if weight is not None else None, ignore_index, int(dice))
+            if focal is not None:
+                ctx.opts += focal
             ctx.weight = weight                 # keeps the pointer in ctx.opts alive
         terms = torch.empty(getattr(_lib.load(), scratch)(N, K), dtype=torch.float32, device=logits.device)
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
@@ -66,7 +86,7 @@ class _CEDice(torch.autograd.Function):
         go = grad_out.detach().float().contiguous().reshape(1)
         dl = torch.empty_like(logits)
         call(ctx.bwd, _p(logits), _p(target), N, H, W, K, *ctx.opts, _p(terms), _p(go), _p(dl), stream())
-        return dl, None, None, None, None
+        return dl, None, None, None, None, None
 
 
 def _class_weight(weight, num_classes, device=None):
@@ -88,19 +108,45 @@ def _check_ignore(ignore_index, num_classes):
                          "result there is an accident of its one-hot encoding")
 
 
-def ce_dice_loss(logits, target, weight=None, ignore_index=-100, dice=True):
+def _focal_tversky(focal_gamma, tversky, dice):
+    """None for the defaults (``focal_gamma == 0`` and ``tversky is None``), else the three floats
+    (gamma, alpha, beta) of the focal / Tversky entry points; ValueError for a value they refuse."""
+    try:
+        gamma = float(focal_gamma)
+    except (TypeError, ValueError):
+        raise ValueError(f"focal_gamma={focal_gamma!r} is not a number") from None
+    if not (math.isfinite(gamma) and gamma >= 0):
+        raise ValueError(f"focal_gamma={focal_gamma!r} must be finite and >= 0")
+    if tversky is None:
+        return None if gamma == 0 else (gamma, 0.5, 0.5)
+    try:
+        alpha, beta = (float(v) for v in tversky)
+    except (TypeError, ValueError):
+        raise ValueError(f"tversky={tversky!r} must be None or a pair (alpha, beta)") from None
+    if not (math.isfinite(alpha) and math.isfinite(beta) and alpha >= 0 and beta >= 0):
+        raise ValueError(f"tversky={tversky!r}: alpha and beta must be finite and >= 0")
+    if alpha == 0 and beta == 0:
+        raise ValueError("tversky=(0, 0): alpha and beta must not both be 0")
+    if not dice:
+        raise ValueError("tversky replaces the Dice term: it needs dice=True")
+    return gamma, alpha, beta
+
+
+def ce_dice_loss(logits, target, weight=None, ignore_index=-100, dice=True, focal_gamma=0.0, tversky=None):
     ignore_index = int(ignore_index)
     K = logits.shape[1]
     check_num_classes(K)
     _check_ignore(ignore_index, K)
+    focal = _focal_tversky(focal_gamma, tversky, dice)
     weight = _class_weight(weight, K, logits.device)
     if not logits.is_cuda:
         raise RuntimeError("stfunet loss kernels need a ROCm device (no CPU fallback)")
-    return _CEDice.apply(logits, target, weight, ignore_index, bool(dice))
+    return _CEDice.apply(logits, target, weight, ignore_index, bool(dice), focal)
 
 
-def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool = True, ignore_index: int = -100):
-    """Same signature and reduction as the reference ``criterion``.
+def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool = True, ignore_index: int = -100,
+              focal_gamma: float = 0.0, tversky=None):
+    """Same signature and reduction as the reference ``criterion``, then ``focal_gamma`` and ``tversky``.
 
     The defaults (the configuration the reference trains with, train_and_eval.py:395) take the
     fused default kernels; ``loss_weight`` (a tensor or a sequence of ``num_classes`` floats),
@@ -108,11 +154,18 @@ def criterion(inputs, target, loss_weight=None, num_classes: int = 2, dice: bool
     ValueError for ``0 <= ignore_index < num_classes`` and for a weight vector whose length
     is not ``num_classes``.  A weight that is not yet a tensor on the logits' device is copied
     there on every call; a training loop converts it once (``engine.train_one_epoch`` does).
+
+    ``focal_gamma`` (>= 0) and ``tversky`` (None or a pair ``(alpha, beta)``, >= 0 and not both 0,
+    with ``dice=True``) are additions (module docstring); the same values go to every head.  Anything
+    but ``focal_gamma=0, tversky=None`` takes the focal / Tversky kernels.  ValueError for a value
+    outside those ranges.
     """
     check_num_classes(num_classes)
     _check_ignore(int(ignore_index), num_classes)
+    _focal_tversky(focal_gamma, tversky, dice)
     loss_weight = _class_weight(loss_weight, num_classes)
-    losses = {name: ce_dice_loss(x, target, loss_weight, ignore_index, dice) for name, x in inputs.items()}
+    losses = {name: ce_dice_loss(x, target, loss_weight, ignore_index, dice, focal_gamma, tversky)
+              for name, x in inputs.items()}
     if len(losses) == 1:
         return losses["out"]
     return losses["out"] + 0.5 * losses["aux"]

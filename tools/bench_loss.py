@@ -18,7 +18,14 @@ ratios.
 stf_head_mc_fwd, stf_head_mc_bwd) at the shape's N, H, W and --channels head inputs, one JSON line per class
 count with us per launch and TB/s on algorithmic bytes (loss fwd 4K+8, loss bwd 8K+8, head fwd 2C+4K, head bwd
 4C+4K bytes per pixel).  For K <= 4 the templated siblings (stf_loss_fwd/bwd, stf_head_fwd/bwd; of --base-lib
-when given) are timed in the same rounds and the line carries the four mc / sibling ratios."""
+when given) are timed in the same rounds and the line carries the four mc / sibling ratios.
+
+    python tools/bench_loss.py --focal [--classes 8] [--out FILE]
+
+--focal: the focal / Tversky pair (stf_loss_ft_fwd + stf_loss_ft_bwd, gamma = 2, (alpha, beta) = (0.3, 0.7)) against
+the option pair of the same build on the same logits, target (a W/8 band of 255) and class weights, interleaved:
+stf_loss_opt_* at the shape's K <= 4, stf_loss_mc_* for each count of --classes.  One JSON line per class count
+with us per launch, TB/s on the same byte model (fwd 4K+8, bwd 8K+8 bytes per pixel) and the ft / option ratios."""
 import argparse
 import ctypes
 import json
@@ -41,6 +48,7 @@ ap.add_argument("--shape", default="64,2,256,256")
 ap.add_argument("--out", default=None)
 ap.add_argument("--classes", default=None, help="comma-separated class counts: time the many-class passes")
 ap.add_argument("--channels", type=int, default=64)
+ap.add_argument("--focal", action="store_true", help="time the focal / Tversky pair against the option pair")
 args = ap.parse_args()
 
 N, K, H, W = (int(v) for v in args.shape.split(","))
@@ -53,6 +61,52 @@ if args.base_lib:
                  "stf_loss_opt_fwd", "stf_loss_opt_bwd"):
         getattr(base, name).restype, getattr(base, name).argtypes = _lib._SIGS[name]
 
+
+def focal_passes(K):
+    """Median us per launch of the option pair (opt for K <= 4, else mc) and of the focal / Tversky pair."""
+    sib = "opt" if K <= 4 else "mc"
+    gen = torch.Generator(device=dev).manual_seed(K)
+    x = torch.randn(N, K, H, W, device=dev, generator=gen) * 2
+    t = (torch.rand(N, H, W, device=dev, generator=gen) > 0.9).long() * (K - 1)
+    t[:, :, W - W // 8:] = 255                           # a collate-padded band
+    w = torch.linspace(0.5, 2.0, K, device=dev)
+    trm = torch.empty(lib.stf_loss_ft_scratch_floats(N, K), device=dev)
+    out1, one, dx = torch.empty(1, device=dev), torch.ones(1, device=dev), torch.empty_like(x)
+    head, ft = (_p(x), _p(t), N, H, W, K, _p(w), 255, 1), (2.0, 0.3, 0.7)
+    sfwd, sbwd = getattr(lib, f"stf_loss_{sib}_fwd"), getattr(lib, f"stf_loss_{sib}_bwd")
+    passes = {      # fwd first: it writes the terms the bwd reads
+        "fwd": (lambda: sfwd(*head, _p(trm), _p(out1), stream()),
+                lambda: lib.stf_loss_ft_fwd(*head, *ft, _p(trm), _p(out1), stream()), 4 * K + 8),
+        "bwd": (lambda: sbwd(*head, _p(trm), _p(one), _p(dx), stream()),
+                lambda: lib.stf_loss_ft_bwd(*head, *ft, _p(trm), _p(one), _p(dx), stream()), 8 * K + 8),
+    }
+
+    def timeit(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            rc = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        if rc != 0:
+            raise RuntimeError(f"launch failed: {rc}")
+        return e0.elapsed_time(e1) / args.reps * 1e3
+
+    P = N * H * W
+    res = {"shape": [N, K, H, W], "reps": args.reps, "rounds": args.rounds, "option_pair": f"stf_loss_{sib}",
+           "gamma": ft[0], "tversky": ft[1:]}
+    for name, (old, new, bpp) in passes.items():
+        for fn in (old, new, old, new):
+            timeit(fn)
+        times = [[timeit(old), timeit(new)] for _ in range(args.rounds)]
+        o, m = statistics.median(r[0] for r in times), statistics.median(r[1] for r in times)
+        res[name] = {"option_us": o, "option_min_us": min(r[0] for r in times), "option_TBps": bpp * P / o * 1e-6,
+                     "ft_us": m, "ft_min_us": min(r[1] for r in times), "ft_TBps": bpp * P / m * 1e-6,
+                     "ft_over_option": m / o}
+    res["pair"] = {"option_us": res["fwd"]["option_us"] + res["bwd"]["option_us"],
+                   "ft_us": res["fwd"]["ft_us"] + res["bwd"]["ft_us"]}
+    res["pair"]["ft_over_option"] = res["pair"]["ft_us"] / res["pair"]["option_us"]
+    return res
 
 
 def many_class_passes(K):
@@ -112,6 +166,15 @@ def many_class_passes(K):
             res[name].update({"sibling_us": o, "sibling_min_us": min(r[1] for r in times), "mc_over_sibling": m / o})
     return res
 
+
+if args.focal:
+    lines = [json.dumps(focal_passes(int(k))) for k in (args.classes.split(",") if args.classes else [K])]
+    print("\n".join(lines))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 
 if args.classes:
     for name in ("stf_head_fwd", "stf_head_bwd"):
