@@ -330,7 +330,7 @@ int stf_loss_mc_bwd(const float* logits, const int64_t* target, int N, int H, in
                     const float* class_weight, int ignore_index, int dice, const float* terms,
                     const float* grad_out, float* dlogits, stf_stream_t stream);
 /* The option criterion with a focal cross-entropy and a Tversky overlap, classes in 1..16 (additive:
- * the ABI version stays 17; csrc/loss_focal.hip).  Arguments, terms layout and scratch size are those
+ * the ABI version stays 17; csrc/loss.hip, FT=true).  Arguments, terms layout and scratch size are those
  * of stf_loss_mc_fwd / stf_loss_mc_bwd (stf_loss_ft_scratch_floats == stf_loss_mc_scratch_floats, 0
  * for classes outside 1..16), with three floats after dice.  With q = p_t and nll = -log q:
  *   CE_f = sum m w[t] (1-q)^focal_gamma nll / Wsum      (Wsum = sum m w[t]; focal_gamma = 0 is CE)

@@ -223,3 +223,22 @@ hipError_t memcpy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind 
 
 // Argument-validation failures are reported as this code (outside hipError_t's range).
 #define STF_EINVAL 100001
+
+// ---------------------------------------------------------------- class-count dispatch (head.hip, loss.hip)
+// EXPR with constexpr int KK = K_ for 1..4 classes; any other count returns STF_EINVAL from the caller
+#define STF_KDISPATCH(K_, EXPR)             \
+  switch (K_) {                             \
+    case 1: { constexpr int KK = 1; EXPR; } break; \
+    case 2: { constexpr int KK = 2; EXPR; } break; \
+    case 3: { constexpr int KK = 3; EXPR; } break; \
+    case 4: { constexpr int KK = 4; EXPR; } break; \
+    default: return STF_EINVAL;             \
+  }
+
+// EXPR with constexpr int KP = the padded bound (4, 8 or 16) of a run-time class count 1..16
+#define STF_KPDISPATCH(K_, EXPR)                          \
+  do {                                                    \
+    if ((K_) <= 4) { constexpr int KP = 4; EXPR; }        \
+    else if ((K_) <= 8) { constexpr int KP = 8; EXPR; }   \
+    else { constexpr int KP = 16; EXPR; }                 \
+  } while (0)

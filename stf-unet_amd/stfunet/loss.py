@@ -8,8 +8,7 @@ loop and its ``if sets_sum == 0`` host sync (dice_coefficient_loss.py:24-35)
 become two kernels with a branch-free empty-set rule; the scalar loss stays on
 the device.
 
-The reference's three options run on the device as well (``stf_loss_opt_fwd`` /
-``stf_loss_opt_bwd``; the default configuration keeps ``stf_loss_fwd`` / ``stf_loss_bwd``):
+The reference's three options run on the device as well:
 
 * ``loss_weight``: per-class weights of the cross-entropy (torch's weighted mean:
   ``sum w[t] nll / sum w[t]``); they do not enter the Dice term.
@@ -21,11 +20,7 @@ The reference's three options run on the device as well (``stf_loss_opt_fwd`` /
   ``F.cross_entropy`` gives -- not special-cased.
 * ``dice=False``: cross-entropy only.
 
-Logits of 5 to 16 classes take the many-class kernels (``stf_loss_mc_fwd`` / ``stf_loss_mc_bwd``:
-the same formula, the options as run-time arguments); more than 16 is a ValueError.
-
-Two additions for lesion-sized foregrounds, after the reference's parameters (``stf_loss_ft_fwd`` /
-``stf_loss_ft_bwd``, one kernel family for 1 to 16 classes, every option above included):
+Two additions for lesion-sized foregrounds, after the reference's parameters:
 
 * ``focal_gamma > 0``: each pixel's cross-entropy term is multiplied by ``(1 - p_t) ** focal_gamma``
   (``sum w[t] (1-p_t)^gamma nll / sum w[t]``: the denominator is unchanged), which down-weights the
@@ -34,7 +29,16 @@ Two additions for lesion-sized foregrounds, after the reference's parameters (``
   in place of Dice, with ``FP = sum p - I`` and ``FN = sum t - I`` per (image, class); ``beta > alpha``
   penalises missed foreground more than false alarms.  ``(0.5, 0.5)`` is Dice.  Needs ``dice=True``.
 
-With ``focal_gamma == 0`` and ``tversky is None`` the three routes above are taken exactly as before.
+The four routes, resolved in one place (``_route``), first match first; more than 16 classes is a
+ValueError:
+
+1. a focal exponent or a Tversky pair: ``stf_loss_ft_fwd`` / ``stf_loss_ft_bwd``, 1 to 16 classes, every
+   option included (anything but ``focal_gamma == 0`` and ``tversky is None``, ``(0.5, 0.5)`` too);
+2. 5 to 16 classes: ``stf_loss_mc_fwd`` / ``stf_loss_mc_bwd``, the same formula with the options as
+   run-time arguments (1. and 2. are one kernel family);
+3. up to 4 classes in the reference's default configuration (no class weights, no ignored target value,
+   Dice on): ``stf_loss_fwd`` / ``stf_loss_bwd``, which take no option arguments;
+4. up to 4 classes otherwise: ``stf_loss_opt_fwd`` / ``stf_loss_opt_bwd`` (one kernel family with 3.).
 """
 import math
 
@@ -45,12 +49,25 @@ from .nhwc import _p, check_num_classes
 from ._lib import call, stream
 
 
+def _route(K, weight, ignore_index, dice, focal):
+    """The entry points of one criterion call (module docstring, routes 1 to 4) and the option arguments
+    they take between ``classes`` and ``terms``: (scratch, fwd, bwd, opts).  ``focal`` is (gamma, alpha,
+    beta) or None."""
+    opts = (_p(weight) if weight is not None else None, ignore_index, int(dice))
+    if focal is not None:
+        infix, opts = "ft_", opts + tuple(focal)
+    elif K > 4:
+        infix = "mc_"
+    elif weight is None and dice and ignore_index < 0:
+        infix, opts = "", ()
+    else:
+        infix = "opt_"
+    return f"stf_loss_{infix}scratch_floats", f"stf_loss_{infix}fwd", f"stf_loss_{infix}bwd", opts
+
+
 class _CEDice(torch.autograd.Function):
-    """CE + Dice.  Up to four classes: the reference's default configuration (no class weights, no
-    ignored target value, Dice on) calls the default entry points, anything else the option ones.
-    Five to sixteen classes: the many-class entry points in every configuration.  A focal exponent
-    or a Tversky pair (``focal`` = (gamma, alpha, beta), else None): the focal / Tversky entry points
-    for every class count."""
+    """CE + Dice (+ focal / Tversky: ``focal`` = (gamma, alpha, beta), else None) through the entry points
+    ``_route`` resolves."""
 
     @staticmethod
     def forward(ctx, logits, target, weight, ignore_index, dice, focal=None):
@@ -60,19 +77,8 @@ class _CEDice(torch.autograd.Function):
             target = target.long()
         N, K, H, W = logits.shape
         assert target.shape == (N, H, W), f"target {tuple(target.shape)} vs logits {tuple(logits.shape)}"
-        if focal is not None:
-            scratch, fwd, ctx.bwd = "stf_loss_ft_scratch_floats", "stf_loss_ft_fwd", "stf_loss_ft_bwd"
-        elif K > 4:
-            scratch, fwd, ctx.bwd = "stf_loss_mc_scratch_floats", "stf_loss_mc_fwd", "stf_loss_mc_bwd"
-        elif weight is None and dice and ignore_index < 0:
-            scratch, fwd, ctx.bwd, ctx.opts = "stf_loss_scratch_floats", "stf_loss_fwd", "stf_loss_bwd", ()
-        else:
-            scratch, fwd, ctx.bwd = "stf_loss_opt_scratch_floats", "stf_loss_opt_fwd", "stf_loss_opt_bwd"
-        if ctx.bwd != "stf_loss_bwd":
-            ctx.opts = (_p(weight) if weight is not None else None, ignore_index, int(dice))
-            if focal is not None:
-                ctx.opts += focal
-            ctx.weight = weight                 # keeps the pointer in ctx.opts alive
+        scratch, fwd, ctx.bwd, ctx.opts = _route(K, weight, ignore_index, dice, focal)
+        ctx.weight = weight                     # keeps the pointer in ctx.opts alive
         terms = torch.empty(getattr(_lib.load(), scratch)(N, K), dtype=torch.float32, device=logits.device)
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         call(fwd, _p(logits), _p(target), N, H, W, K, *ctx.opts, _p(terms), _p(loss), stream())

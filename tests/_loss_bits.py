@@ -1,4 +1,5 @@
-"""Cases and digests of tests/golden/loss_bits.json (shared by its generator and its test).
+"""Cases and digests of tests/golden/loss_bits.json and loss_bits_manyclass.json (shared by their
+generator and their test).
 
 Every case is a seed and a shape; the inputs come from ``numpy.random.default_rng(seed)``.  A
 family is one pair of C entry points with one option set; ``digests`` runs forward then backward
@@ -23,10 +24,31 @@ SHAPES = [(2, 2, 136, 136),     # HW > 64 * 256: the forward's chunk loop takes 
 FAMILIES = {"default": None, "option": 1, "option_nodice": 0}      # name -> the dice argument
 
 
+# loss_bits_manyclass.json: the many-class (stf_loss_mc_*) and focal / Tversky (stf_loss_ft_*) entry points.
+# name -> (entry-point infix, the dice argument, (gamma, alpha, beta) or ())
+MC_FAMILIES = {"mc": ("mc", 1, ()), "mc_nodice": ("mc", 0, ()),
+               "ft": ("ft", 1, (2.0, 0.3, 0.7)), "ft_tversky_only": ("ft", 1, (0.0, 0.3, 0.7)),
+               "ft_focal_nodice": ("ft", 0, (0.5, 0.5, 0.5))}
+MC_SHAPES = [((2, 7, 136, 136), ("mc", "ft")),      # the forward's second, ragged chunk trip; KP = 8 with K < KP
+             ((65, 5, 8, 8), ("mc", "ft")),         # the finalize's second block of 64 images
+             ((3, 16, 16, 24), ("mc", "ft")),       # KP = 16 full
+             ((3, 9, 16, 24), ("mc", "ft")),        # KP = 16 ragged
+             ((33, 5, 256, 256), ("mc",)),          # 8192 / 33 = 248 blocks of 256 threads < HW: the backward's
+             ((33, 2, 256, 256), ("ft",)),          # grid-stride loop takes a second trip
+             ((2, 1, 16, 16), ("ft",)),             # K = 1 in KP = 4
+             ((2, 3, 16, 16), ("ft",)),             # K = 3 in KP = 4
+             ((2, 4, 16, 16), ("mc",)),             # KP = 4 full (a direct call: legal for the C entry point)
+             ((3, 7, 24, 16), ("mc_nodice", "ft_tversky_only", "ft_focal_nodice"))]
+
+
 def cases():
     out = [(f, s) for s in SHAPES for f in ("default", "option")]
     out.append(("option_nodice", (3, 4, 16, 24)))
     return out
+
+
+def mc_cases():
+    return [(f, s) for s, fams in MC_SHAPES for f in fams]
 
 
 def case_id(family, shape):
@@ -74,6 +96,14 @@ def digests(family, shape, dev="cuda"):
         lead = N * K * 3 + 1
         call("stf_loss_fwd", _p(x), _p(t), N, H, W, K, _p(terms), _p(loss), stream())
         call("stf_loss_bwd", _p(x), _p(t), N, H, W, K, _p(terms), _p(go), _p(dl), stream())
+    elif family in MC_FAMILIES:
+        ep, dice, ft = MC_FAMILIES[family]
+        w = torch.from_numpy(weight).to(dev)
+        terms = torch.zeros(getattr(lib, f"stf_loss_{ep}_scratch_floats")(N, K), device=dev)
+        lead = N * K * 3 + 2
+        opts = (_p(w), IGNORE, dice, *ft)
+        call(f"stf_loss_{ep}_fwd", _p(x), _p(t), N, H, W, K, *opts, _p(terms), _p(loss), stream())
+        call(f"stf_loss_{ep}_bwd", _p(x), _p(t), N, H, W, K, *opts, _p(terms), _p(go), _p(dl), stream())
     else:
         dice = FAMILIES[family]
         w = torch.from_numpy(weight).to(dev)

@@ -25,7 +25,13 @@ when given) are timed in the same rounds and the line carries the four mc / sibl
 --focal: the focal / Tversky pair (stf_loss_ft_fwd + stf_loss_ft_bwd, gamma = 2, (alpha, beta) = (0.3, 0.7)) against
 the option pair of the same build on the same logits, target (a W/8 band of 255) and class weights, interleaved:
 stf_loss_opt_* at the shape's K <= 4, stf_loss_mc_* for each count of --classes.  One JSON line per class count
-with us per launch, TB/s on the same byte model (fwd 4K+8, bwd 8K+8 bytes per pixel) and the ft / option ratios."""
+with us per launch, TB/s on the same byte model (fwd 4K+8, bwd 8K+8 bytes per pixel) and the ft / option ratios.
+
+    python tools/bench_loss.py --pair mc|ft --base-lib PATH [--shape 64,8,256,256] [--out FILE]
+
+--pair: the many-class (stf_loss_mc_*) or the focal / Tversky (stf_loss_ft_*, gamma = 2, (0.3, 0.7)) fwd + bwd pair
+of --base-lib's build and of this tree's on the same inputs (class weights, a W/8 band of 255), in turn inside each
+round.  One JSON line with every round's times, the medians, each build's own spread and new / base."""
 import argparse
 import ctypes
 import json
@@ -49,6 +55,8 @@ ap.add_argument("--out", default=None)
 ap.add_argument("--classes", default=None, help="comma-separated class counts: time the many-class passes")
 ap.add_argument("--channels", type=int, default=64)
 ap.add_argument("--focal", action="store_true", help="time the focal / Tversky pair against the option pair")
+ap.add_argument("--pair", choices=("mc", "ft"), default=None,
+                help="A/B of the many-class or the focal / Tversky pair against --base-lib's")
 args = ap.parse_args()
 
 N, K, H, W = (int(v) for v in args.shape.split(","))
@@ -167,8 +175,64 @@ def many_class_passes(K):
     return res
 
 
+def pair_ab(fam):
+    """The fwd + bwd pair of stf_loss_<fam>_* (mc or ft) of the base build and of this tree, in turn inside
+    each round: medians, each build's own round-to-round spread (max - min) / median, and new / base."""
+    gen = torch.Generator(device=dev).manual_seed(K)
+    x = torch.randn(N, K, H, W, device=dev, generator=gen) * 2
+    t = (torch.rand(N, H, W, device=dev, generator=gen) > 0.9).long() * (K - 1)
+    t[:, :, W - W // 8:] = 255                           # a collate-padded band
+    w = torch.linspace(0.5, 2.0, K, device=dev)
+    trm = torch.empty(lib.stf_loss_mc_scratch_floats(N, K), device=dev)
+    out1, one, dx = torch.empty(1, device=dev), torch.ones(1, device=dev), torch.empty_like(x)
+    opts = (_p(x), _p(t), N, H, W, K, _p(w), 255, 1) + ((2.0, 0.3, 0.7) if fam == "ft" else ())
+
+    def pair_on(l):
+        fwd, bwd = getattr(l, f"stf_loss_{fam}_fwd"), getattr(l, f"stf_loss_{fam}_bwd")
+
+        def run():
+            rc = fwd(*opts, _p(trm), _p(out1), stream()) or bwd(*opts, _p(trm), _p(one), _p(dx), stream())
+            if rc != 0:
+                raise RuntimeError(f"launch failed: {rc}")
+        return run
+
+    def timeit(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / args.reps * 1e3
+
+    old, new = pair_on(base), pair_on(lib)
+    for fn in (old, new, old, new):
+        timeit(fn)
+    times = [[timeit(old), timeit(new)] for _ in range(args.rounds)]
+    tb, tn = [r[0] for r in times], [r[1] for r in times]
+    mb, mn = statistics.median(tb), statistics.median(tn)
+    return {"pair": f"stf_loss_{fam}", "shape": [N, K, H, W], "reps": args.reps, "rounds": args.rounds,
+            "base_lib": args.base_lib, "base_us": tb, "new_us": tn,
+            "base_pair_us": {"median": mb, "min": min(tb), "spread": (max(tb) - min(tb)) / mb},
+            "new_pair_us": {"median": mn, "min": min(tn), "spread": (max(tn) - min(tn)) / mn},
+            "new_over_base": mn / mb}
+
+
+if args.pair:
+    if not args.base_lib:
+        sys.exit("--pair needs --base-lib")
+    for name in (f"stf_loss_{args.pair}_fwd", f"stf_loss_{args.pair}_bwd"):
+        getattr(base, name).restype, getattr(base, name).argtypes = _lib._SIGS[name]
+    line = json.dumps(pair_ab(args.pair))
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+    sys.exit(0)
+
 if args.focal:
-    lines = [json.dumps(focal_passes(int(k))) for k in (args.classes.split(",") if args.classes else [K])]
+    lines =[json.dumps(focal_passes(int(k))) for k in (args.classes.split(",") if args.classes else [K])]
     print("\n".join(lines))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
