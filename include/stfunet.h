@@ -421,6 +421,32 @@ int stf_adamw_clip(float* p, const float* g, float* m, float* v, int64_t n, floa
                    const float* grad_scale, const float* found_inf, const float* clip, float beta1,
                    float beta2, float eps, float weight_decay, stf_stream_t stream);
 
+/* Exponential moving average of the weights in one fp32 shadow buffer (16-B aligned).  A segment
+ * is `len` fp32 elements of the model at `model` (4-B aligned is enough: a 16-B aligned pointer
+ * moves as float4, any other element by element) and their place in the shadow, element offset
+ * `off`: off >= 0 and a multiple of 4, len >= 0 (0: skipped).  Segments overlap neither in the
+ * model nor in the shadow.  Only elements inside a segment are read or written, on either side.
+ * The table is taken twice, like stf_grad_norm's: `segs` in DEVICE memory for the kernel and
+ * `segs_host`, the same `count` entries on the host, for the checks and the grid. */
+typedef struct stf_ema_seg {
+  float* model;
+  int64_t off;
+  int64_t len;
+} stf_ema_seg;
+/* shadow = shadow + w * (model - shadow) for every element of every segment, in fp32 (the
+ * difference rounds once, the multiply-add once), ONE launch for the whole table.  w == 1 writes
+ * the model's bits, w == 0 leaves the shadow's bits; a fixed assignment of elements to
+ * workgroups, no atomics.
+ * STF_EINVAL, nothing launched: a NULL pointer, count < 1, shadow not 16-B aligned, a negative
+ * off or len, off % 4 != 0, a NULL (or not 4-B aligned) model in a segment with len > 0, w NaN
+ * or outside [0, 1]. */
+int stf_ema_update(float* shadow, const stf_ema_seg* segs, const stf_ema_seg* segs_host, int count,
+                   float w, stf_stream_t stream);
+/* Exchanges model and shadow element by element as raw bits (-0.0 and NaN payloads survive), in
+ * place, ONE launch; twice restores both sides.  Same argument checks. */
+int stf_ema_swap(float* shadow, const stf_ema_seg* segs, const stf_ema_seg* segs_host, int count,
+                 stf_stream_t stream);
+
 /* ---------------------------------------------------------------- layout
  * x [N][C][H][W] fp32 -> NHWC bf16 with Cpad (>= C, multiple of 8) channels,
  * zero-filled (preprocess_input output, train_and_eval.py:9-22). */

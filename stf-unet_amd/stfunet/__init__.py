@@ -7,6 +7,7 @@ kernels through the C ABI in ``include/stfunet.h``.
 """
 from . import _lib  # noqa: F401
 from . import predict  # noqa: F401  (the module; its loop is stfunet.predict.predict)
+from .ema import WeightEMA  # noqa: F401
 from .loss import criterion  # noqa: F401
 from .optim import clip_grad_norm_  # noqa: F401
 from .predict import (boundary_metrics, connected_components, distance_transform_sq, filter_components,  # noqa: F401
@@ -15,6 +16,6 @@ from .resize import upsample_logits  # noqa: F401
 from .stf_lstm_unet import STFLSTMUNet  # noqa: F401
 from .unet import UNet  # noqa: F401
 
-__all__ = ["STFLSTMUNet", "UNet", "boundary_metrics", "clip_grad_norm_", "connected_components", "criterion",
-           "distance_transform_sq", "filter_components", "flip_planes", "image_metrics", "overlay", "predict",
+__all__ = ["STFLSTMUNet", "UNet", "WeightEMA", "boundary_metrics", "clip_grad_norm_", "connected_components",
+           "criterion", "distance_transform_sq", "filter_components", "flip_planes", "image_metrics", "overlay", "predict",
            "predict_masks", "predict_tta", "tta_probabilities", "upsample_logits"]

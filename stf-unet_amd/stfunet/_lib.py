@@ -109,6 +109,11 @@ class Seg(ctypes.Structure):
     _fields_ = [("off", c_int64), ("len", c_int64)]
 
 
+class EmaSeg(ctypes.Structure):
+    """stf_ema_seg: ``len`` fp32 elements of the model at ``model``, at element offset ``off`` of the shadow."""
+    _fields_ = [("model", P), ("off", c_int64), ("len", c_int64)]
+
+
 # name -> (restype, argtypes)
 _SIGS = {
     "stf_igemm_stat_tiles": (c_int, [ctypes.POINTER(IgemmArgs)]),
@@ -159,6 +164,8 @@ _SIGS = {
     "stf_grad_norm": (c_int, [P, P, P, c_int, P, c_float, P, P, P]),
     "stf_grad_scale": (c_int, [P, P, P, c_int, P, P]),
     "stf_adamw_clip": (c_int, [P, P, P, P, c_int64, P, P, P, P, c_float, c_float, c_float, c_float, P]),
+    "stf_ema_update": (c_int, [P, P, P, c_int, c_float, P]),
+    "stf_ema_swap": (c_int, [P, P, P, c_int, P]),
     "stf_pack_input": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, P]),
     "stf_pack_weight": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
     "stf_pack_weights": (c_int, [P, c_int, c_int64, P]),

@@ -281,7 +281,12 @@ def eval_update(out, target, confmat, dice):
         dice.count += 1
 
 
-def evaluate(model, data_loader, device, num_classes):
+def evaluate(model, data_loader, device, num_classes, *, ema=None):
+    """``ema`` (a ``stfunet.WeightEMA``; ``None``: the loop as it was): evaluate the averaged weights,
+    exchanged into the model for the loop and back after it."""
+    if ema is not None:
+        with ema.averaged():
+            return evaluate(model, data_loader, device, num_classes)
     model.eval()
     confmat = ConfusionMatrix(num_classes)
     dice = DiceCoefficient(num_classes=num_classes, ignore_index=255)
@@ -313,7 +318,7 @@ def evaluate(model, data_loader, device, num_classes):
 
 def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler=None,
                     print_freq=10, scaler=None, *, loss_weight=None, dice=True, ignore_index=-100,
-                    max_grad_norm=None, focal_gamma=0.0, tversky=None):
+                    max_grad_norm=None, focal_gamma=0.0, tversky=None, ema=None):
     """The reference's loop (its positional signature and defaults); the keyword-only
     ``loss_weight`` / ``dice`` / ``ignore_index`` / ``focal_gamma`` / ``tversky`` go to ``criterion``
     (``ignore_index=255`` for batches whose targets ``collate_fn`` padded to a common size).
@@ -322,7 +327,10 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
     their global L2 norm.  A ``stfunet.optim.AdamW`` gets it as its param-group option for the epoch
     (the clip runs inside the update, no ``unscale_``; the previous value is put back at the end);
     any other optimizer gets ``scaler.unscale_`` and ``stfunet.optim.clip_grad_norm_`` before its
-    step.  The logger gains a ``grad_norm`` meter, read in the same host read as the loss."""
+    step.  The logger gains a ``grad_norm`` meter, read in the same host read as the loss.
+
+    ``ema`` (a ``stfunet.WeightEMA``; ``None``: the loop as it was): ``ema.update()`` after every
+    optimizer step, a step the GradScaler or a non-finite clip norm skipped included."""
     from .optim import AdamW, clip_grad_norm_
     fused_clip = max_grad_norm is not None and isinstance(optimizer, AdamW)
     if fused_clip:
@@ -332,7 +340,7 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
     try:
         return _train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler,
                                 print_freq, scaler, loss_weight, dice, ignore_index, max_grad_norm, fused_clip,
-                                clip_grad_norm_, focal_gamma, tversky)
+                                clip_grad_norm_, focal_gamma, tversky, ema)
     finally:
         if fused_clip:
             for group, value in zip(optimizer.param_groups, previous):
@@ -341,7 +349,7 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
 
 def _train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler, print_freq, scaler,
                      loss_weight, dice, ignore_index, max_grad_norm, fused_clip, clip_grad_norm_, focal_gamma,
-                     tversky):
+                     tversky, ema=None):
     model.train()
     logger = MetricLogger(delimiter="  ")
     logger.add_meter("lr", SmoothedValue(window_size=1, fmt="{value:.6f}"))
@@ -368,6 +376,8 @@ def _train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, 
             if max_grad_norm is not None and not fused_clip:
                 grad_norm = clip_grad_norm_([p for g in optimizer.param_groups for p in g["params"]], max_grad_norm)
             optimizer.step()
+        if ema is not None:
+            ema.update()
         lr_scheduler.step()
         lr = optimizer.param_groups[0]["lr"]
         if max_grad_norm is None:
@@ -447,24 +457,29 @@ def print_eval(eval_metrics):
     print(f"Mean recall: {mm['mrecall']:.4f}")
 
 
-def checkpoint_dict(model, optimizer, lr_scheduler, epoch, args, scaler=None):
+def checkpoint_dict(model, optimizer, lr_scheduler, epoch, args, scaler=None, *, ema=None):
     """train.py:304-311: {'model', 'optimizer', 'lr_scheduler', 'epoch', 'args'} plus
-    'scaler' when training with --amp (a GradScaler)."""
+    'scaler' when training with --amp (a GradScaler) and 'ema' when a ``stfunet.WeightEMA`` is given."""
     save = {"model": model.state_dict(), "optimizer": optimizer.state_dict(),
             "lr_scheduler": lr_scheduler.state_dict(), "epoch": epoch, "args": args}
     if scaler is not None:
         save["scaler"] = scaler.state_dict()
+    if ema is not None:
+        save["ema"] = ema.state_dict()
     return save
 
 
-def resume_from(checkpoint, model, optimizer, lr_scheduler, scaler=None):
+def resume_from(checkpoint, model, optimizer, lr_scheduler, scaler=None, *, ema=None):
     """train.py:249-256: load model / optimizer / scheduler (and the GradScaler under
-    --amp) and return the next epoch."""
+    --amp; the weight average when both ``ema`` and the checkpoint's 'ema' key are there) and
+    return the next epoch."""
     model.load_state_dict(checkpoint["model"])
     optimizer.load_state_dict(checkpoint["optimizer"])
     lr_scheduler.load_state_dict(checkpoint["lr_scheduler"])
     if scaler is not None and "scaler" in checkpoint:
         scaler.load_state_dict(checkpoint["scaler"])
+    if ema is not None and "ema" in checkpoint:
+        ema.load_state_dict(checkpoint["ema"])
     return checkpoint["epoch"] + 1
 
 
