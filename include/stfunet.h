@@ -766,6 +766,41 @@ int stf_ccl_filter(const uint8_t* mask, const int64_t* target, int B, int H, int
                    int keep_largest, int64_t min_size, int64_t ignore_index, uint8_t* out, int64_t* counts,
                    int32_t* num, void* scratch, stf_stream_t stream);
 
+/* ---------------------------------------------------------------- connected components of volumes
+ * The same for stacked slices.  mask uint8 [N][H][W] is cut into
+ * V volumes of consecutive slices by starts int32 [V + 1]: strictly ascending, starts[0] = 0,
+ * starts[V] = N.  The table is taken twice, like stf_grad_norm's: starts_dev in DEVICE memory, which
+ * the kernels read, and starts_host, the same V + 1 entries on the host, which the call validates
+ * before it returns.  Every volume is labelled on its own (volumes never touch, whatever their
+ * adjacent slices hold): foreground is mask != 0, outside the volume is background, connectivity is
+ * 6, 18 or 26 = scipy.ndimage.generate_binary_structure(3, 1 | 2 | 3).
+ * Additive to ABI v17.  Limits: 1 <= V <= N, 1 <= H, W <= 4096, N * H * W < 2^31.  STF_EINVAL
+ * (nothing launched) for a NULL required pointer, a size outside the limits, V < 1, a host starts
+ * that is not strictly ascending from 0 to N, a connectivity other than 6, 18 or 26, min_size < 0,
+ * counts without target, out == mask, a labels, num or starts that is not 4-byte aligned, or a
+ * scratch, counts or target that is not 8-byte aligned (mask and out may sit at any byte).
+ * No entry point allocates, reads back or waits between workgroups; the number of launches is
+ * fixed; atomics are integer only, so the results are the same bits from run to run.  All outputs
+ * are OVERWRITTEN and may arrive uninitialised, the scratch too.
+ *
+ * Bytes of the scratch either call needs, a multiple of 8 (0 outside the limits). */
+size_t stf_ccl3d_scratch_bytes(int N, int H, int W, int V);
+/* labels int32 [N][H][W]: 0 on the background, 1..n on the components, numbered per volume in raster
+ * order (z, y, x) of each component's first voxel (scipy.ndimage.label's numbering; a volume of
+ * depth 1 gets stf_ccl_label's labels with 6 -> 4 and 18, 26 -> 8); num int32 [V] = n. */
+int stf_ccl3d_label(const uint8_t* mask, int N, int H, int W, const int32_t* starts_dev,
+                    const int32_t* starts_host, int V, int connectivity, int32_t* labels, int32_t* num,
+                    void* scratch, stf_stream_t stream);
+/* stf_ccl_filter's contract per volume instead of per image: min_size is in voxels and applies
+ * first, keep_largest keeps the volume's largest component (equal areas: the one whose first voxel
+ * comes first in raster order), a surviving voxel keeps its value.  counts (int64 [V][3], or NULL;
+ * needs target int64 [N][H][W]) = (|P' & T|, |P'|, |T|) over the volume with stf_predict_mask's
+ * ignore rule; num (or NULL) int32 [V]: the number of components BEFORE filtering. */
+int stf_ccl3d_filter(const uint8_t* mask, const int64_t* target, int N, int H, int W,
+                     const int32_t* starts_dev, const int32_t* starts_host, int V, int connectivity,
+                     int keep_largest, int64_t min_size, int64_t ignore_index, uint8_t* out, int64_t* counts,
+                     int32_t* num, void* scratch, stf_stream_t stream);
+
 /* ---------------------------------------------------------------- PK maps (extended Tofts)
  * pk_fitting.py ToftsModelFitter, all fp32.  The host builds
  * the reference's constant tables exactly as the reference does (pk_fitting.py:

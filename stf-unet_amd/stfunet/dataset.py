@@ -22,6 +22,7 @@ PNGs; for JPEG or colour files the two decoders / luma rules can differ by one l
 (unpinned).  A missing PK map reads as zeros, as in the reference (:226-228).
 """
 import os
+import re
 
 import numpy as np
 import torch
@@ -114,6 +115,31 @@ class DriveDataset(Dataset):
             return self.transforms.plan(list(frames), list(masks), list(params))
         xs, ts = zip(*batch)
         return torch.stack(xs), cat_list(ts, fill_value=255)
+
+
+def _natural_key(name):
+    """Sort key under which digit runs compare as numbers: ``2.png`` before ``10.png``."""
+    return [(0, int(t), "") if t.isdigit() else (1, 0, t) for t in re.split(r"(\d+)", name) if t]
+
+
+def volume_order(dataset):
+    """``(indices, depths, patient_ids)`` that put a ``DriveDataset`` into volume order: its samples
+    grouped by ``patient_id`` in first-appearance order and, inside a patient, sorted by the slice
+    file's name with a natural sort.  The dataset itself keeps ``os.listdir`` order, which is neither
+    grouped nor sorted by slice.  ``Subset(dataset, indices)`` with ``shuffle=False`` then yields
+    ``depths[0]`` slices of ``patient_ids[0]``, ``depths[1]`` of the next and so on, which is what
+    ``stfunet.predict.predict_volumes`` takes.  Host only."""
+    groups = {}
+    for i, item in enumerate(dataset.patient_data):
+        groups.setdefault(item["patient_id"], []).append(i)
+    indices, depths = [], []
+    for members in groups.values():
+        def name(i):
+            return os.path.basename(dataset.patient_data[i]["image_paths"][0])
+        members.sort(key=lambda i: (_natural_key(name(i)), name(i)))
+        indices += members
+        depths.append(len(members))
+    return indices, depths, list(groups)
 
 
 def cat_list(images, fill_value=0):

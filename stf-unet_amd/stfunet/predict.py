@@ -20,6 +20,9 @@ gfx950 kernels of ``csrc/predict.hip``:
 * ``flip_planes`` / ``tta_probabilities`` / ``predict_tta``  mirror test-time augmentation: the model
   on the batch and its flipped copies, the un-flipped class probabilities averaged in a fixed order
   (``csrc/tta.hip``), and ``predict``'s loop with each batch's mask taken from that mean
+* ``connected_components_3d`` / ``filter_components_3d`` / ``predict_volumes``  the same labels and
+  clean-up per volume of stacked slices (6 / 18 / 26 connectivity, ``csrc/ccl3d.hip``), and the loop
+  that groups a patient's slices: 3-D post-processing and per-volume (per-case) Dice / IoU
 
 ``predict(model, loader, device, rule="sigmoid", channel=0, paint=0)`` reproduces test.py bit for
 bit (it thresholds channel 0 and inverts the mask before painting, :75-76), except that the
@@ -298,6 +301,126 @@ def filter_components(mask, keep_largest=False, min_size=0, connectivity=8, targ
     return out if target is None else (out, counts)
 
 
+CONNECTIVITIES_3D = (6, 18, 26)
+
+
+def _check_components_3d(connectivity, min_size=0):
+    if isinstance(connectivity, bool) or connectivity not in CONNECTIVITIES_3D:
+        raise ValueError(f"connectivity must be 6 (faces), 18 (faces and edges) or 26 (faces, edges and corners), "
+                         f"not {connectivity!r}")
+    _, min_size = _check_components(8, min_size)
+    return int(connectivity), min_size
+
+
+def _check_depths(depths, total=None):
+    """``depths`` as a list of ints: positive integers (no bools) that sum to ``total`` when that is
+    given; ``None`` is one volume of ``total`` slices."""
+    if depths is None:
+        depths = [total] if total else []
+    elif isinstance(depths, (str, bytes, numbers.Number)):
+        raise ValueError(f"depths must be a sequence of positive integers, not {depths!r}")
+    else:
+        try:
+            depths = list(depths)
+        except TypeError:
+            raise ValueError(f"depths must be a sequence of positive integers, not {depths!r}") from None
+    for d in depths:
+        if isinstance(d, bool) or not isinstance(d, numbers.Integral) or d < 1:
+            raise ValueError(f"depths must be positive integers, not {d!r}")
+    depths = [int(d) for d in depths]
+    if total is not None and sum(depths) != total:
+        raise ValueError(f"depths sum to {sum(depths)}, but there are {total} slices")
+    return depths
+
+
+def _starts(depths, device):
+    """The volume table of the 3-D entry points: (host int32 [V + 1], its device copy)."""
+    host = torch.zeros(len(depths) + 1, dtype=torch.int32)
+    host[1:] = torch.tensor(depths, dtype=torch.int64).cumsum(0)
+    return host, host.to(device)
+
+
+def _ccl3d_scratch(N, H, W, V, device):
+    nbytes = load().stf_ccl3d_scratch_bytes(N, H, W, V)
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def connected_components_3d(mask, depths=None, connectivity=26):
+    """``(labels int32 [N, H, W], num int32 [V])``: the connected components of the volumes of
+    ``mask`` (``[N, H, W]`` bool or any integer, nonzero = foreground), a stack of slices cut into
+    ``V = len(depths)`` volumes of ``depths[v]`` consecutive slices (``None``: one volume), each
+    volume on its own -- volumes never touch, whatever their adjacent slices hold.
+
+    ``connectivity`` 6 joins face neighbours, 18 faces and edges, 26 faces, edges and corners; voxels
+    outside the volume are background.  ``labels`` is 0 on the background and 1..n on the components,
+    numbered per volume in raster order (z, y, x) of each component's first voxel --
+    ``scipy.ndimage.label(volume, generate_binary_structure(3, 1, 2 or 3))`` -- and ``num[v]`` is n.
+    Integers only: the same bits from run to run."""
+    N, H, W = _check_bhw(mask, "mask")
+    connectivity, _ = _check_components_3d(connectivity)
+    depths = _check_depths(depths, N)
+    mask = _as_u8(mask.detach(), "mask")
+    _device_only(mask, "connected_components_3d")
+    V = len(depths)
+    labels = torch.empty((N, H, W), dtype=torch.int32, device=mask.device)
+    num = torch.empty((V,), dtype=torch.int32, device=mask.device)
+    if N:
+        host, dev = _starts(depths, mask.device)
+        scratch = _ccl3d_scratch(N, H, W, V, mask.device)
+        with torch.cuda.device(mask.device):
+            call("stf_ccl3d_label", _p(mask), N, H, W, _p(dev), host.data_ptr(), V, connectivity, _p(labels), _p(num),
+                 _p(scratch), stream())
+    return labels, num
+
+
+def _filter3d(mask, target, depths, keep_largest, min_size, connectivity, ignore_index):
+    """``stf_ccl3d_filter`` on a checked uint8 device mask and checked depths: (filtered mask, counts
+    or None, num int32 [V])."""
+    N, H, W = mask.shape
+    dev, V = mask.device, len(depths)
+    out = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    num = torch.empty((V,), dtype=torch.int32, device=dev)
+    counts = None
+    if target is not None:
+        target = target.detach().to(device=dev, dtype=torch.int64).contiguous()
+        counts = torch.empty((V, 3), dtype=torch.int64, device=dev)
+    if N:
+        host, starts = _starts(depths, dev)
+        scratch = _ccl3d_scratch(N, H, W, V, dev)
+        with torch.cuda.device(dev):
+            call("stf_ccl3d_filter", _p(mask), _p(target), N, H, W, _p(starts), host.data_ptr(), V, connectivity,
+                 int(bool(keep_largest)), min_size, -1 if ignore_index is None else ignore_index, _p(out), _p(counts),
+                 _p(num), _p(scratch), stream())
+    return out, counts, num
+
+
+def filter_components_3d(mask, depths=None, keep_largest=False, min_size=0, connectivity=26, target=None,
+                         ignore_index=None):
+    """``uint8 [N, H, W]``: ``filter_components`` per volume instead of per image.  ``mask`` is a stack
+    of slices cut into volumes by ``depths`` as in ``connected_components_3d``.
+
+    A component passes when it has at least ``min_size`` voxels and, with ``keep_largest``, it is the
+    largest of its volume; of several largest ones the one whose first voxel comes first in raster
+    order (z, y, x) is kept.  ``min_size`` applies first.  A voxel that stays keeps its own value.
+    With ``target`` (``[N, H, W]`` integers) returns ``(mask, counts)``, ``counts`` the ``int64 [V, 3]``
+    (|P&T|, |P|, |T|) of the filtered mask summed over each volume with ``predict_masks``' rules;
+    ``image_metrics(counts)`` is then the per-volume Dice / IoU."""
+    N, H, W = _check_bhw(mask, "mask")
+    connectivity, min_size = _check_components_3d(connectivity, min_size)
+    depths = _check_depths(depths, N)
+    if target is not None:
+        if tuple(target.shape) != (N, H, W):
+            raise ValueError(f"target {tuple(target.shape)} does not match the mask's {(N, H, W)}")
+        if target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
+            raise ValueError(f"target must be an integer tensor, not {target.dtype}")
+    mask = _as_u8(mask.detach(), "mask")
+    _device_only(mask, "filter_components_3d")
+    if target is not None:
+        _device_only(target, "filter_components_3d")
+    out, counts, _ = _filter3d(mask, target, depths, keep_largest, min_size, connectivity, ignore_index)
+    return out if target is None else (out, counts)
+
+
 def overlay(frames, mask, color=(0, 255, 0), alpha=0.5, paint=1):
     """``uint8 [B, H, W, 3]``: ``frames`` normalised to 0..255 per image, with ``color`` blended
     at ``alpha`` into the pixels where the mask is non-zero (``paint=1``) or zero (``paint=0``).
@@ -550,6 +673,117 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
     ``predict_tta`` is this loop with mirror test-time augmentation."""
     return _predict(model, data_loader, device, None, False, rule, channel, threshold, ignore_index, output_dir,
                     prefix, color, alpha, paint, keep_masks, boundary, spacing, keep_largest, min_size, connectivity)
+
+
+def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argmax", channel=0, threshold=0.5,
+                    ignore_index=None, keep_largest=False, min_size=0, connectivity=26, keep_masks=False):
+    """The inference loop over volumes: the loader yields slices in volume order -- ``depths[0]``
+    slices of volume 0, then volume 1 and so on (``stfunet.dataset.volume_order`` puts a
+    ``DriveDataset`` into that order); batches may straddle volume boundaries.
+
+    Every batch gets a forward (``tta_probabilities`` when ``tta`` is set, as in ``predict_tta``) and
+    ``predict_masks``.  With ``keep_largest=True`` and / or ``min_size > 0`` the masks and targets
+    are held on the device until their volume is complete; all volumes a batch completes are cleaned
+    by one ``filter_components_3d`` call (at ``connectivity``, ``min_size`` in voxels), so the memory
+    held is bounded by the largest volume plus one batch.  With both options off no labelling kernel
+    runs and the per-volume counts are the per-slice counts summed by volume on the device.
+
+    Returns a dict of device tensors in volume order, with no host synchronisation in the loop:
+    ``num`` slices seen, ``num_volumes``, per-volume ``dice`` / ``iou`` (from the counts summed over
+    the volume's slices: the per-case numbers) with ``mean_dice`` / ``mean_iou`` over the volumes
+    (all None without targets), ``num_components`` (int64 ``[V]``, the components of each volume
+    before filtering; only with a component option on) and, with ``keep_masks``, ``masks``, a list
+    of ``V`` ``uint8 [D_v, H, W]`` masks.  Raises ``ValueError`` when the loader's slice total is not
+    ``sum(depths)``.
+
+    Not here: boundary metrics in 3-D (HD95 with slice spacing), overlays (``keep_masks=True`` and
+    ``overlay`` cover them) and anisotropic connectivity."""
+    if rule not in RULES:
+        raise ValueError(f"unknown rule {rule!r} (one of {sorted(RULES)})")
+    views = parse_views(tta)
+    mask_rule, mask_channel = rule, channel
+    if views is not None:
+        _check_tta_rule(rule)
+        if rule == "sigmoid":                       # the mean probability is one plane: mean > threshold
+            mask_rule, mask_channel = "threshold", 0
+    connectivity, min_size = _check_components_3d(connectivity, min_size)
+    if depths is None:
+        raise ValueError("depths must be a sequence of positive integers, one per volume, not None")
+    depths = _check_depths(depths)
+    components = bool(keep_largest) or min_size > 0
+    V, total = len(depths), sum(depths)
+    from .engine import preprocess_input
+    model.eval()
+    slice_volume = torch.repeat_interleave(torch.arange(V), torch.tensor(depths, dtype=torch.int64)).to(device)
+    vol_counts = None                               # options off: int64 [V, 3], summed as the slices come
+    held_masks, held_targets, held, done = [], [], 0, 0   # options on: slices of volumes not yet complete
+    all_counts, all_num, masks, idx, with_targets = [], [], [], 0, None
+    with torch.no_grad():
+        for batch in data_loader:
+            inputs, targets = batch if isinstance(batch, (tuple, list)) else (batch, None)
+            if with_targets is None:
+                with_targets = targets is not None
+            elif with_targets != (targets is not None):
+                raise ValueError("the loader yields targets for some batches and none for others")
+            inputs = preprocess_input(inputs, model).to(device)
+            outputs = model(inputs) if views is None else tta_probabilities(model, inputs, views, rule, channel)
+            if targets is not None:
+                targets = targets.to(device)
+                mask, counts = predict_masks(outputs, mask_rule, mask_channel, threshold, target=targets,
+                                             ignore_index=ignore_index)
+            else:
+                mask = predict_masks(outputs, mask_rule, mask_channel, threshold)
+            B = mask.shape[0]
+            if idx + B > total:
+                raise ValueError(f"the loader yields more than the {total} slices of depths")
+            if not components:
+                if targets is not None:
+                    if vol_counts is None:
+                        vol_counts = torch.zeros((V, 3), dtype=torch.int64, device=counts.device)
+                    vol_counts.index_add_(0, slice_volume[idx:idx + B], counts)
+                if keep_masks:
+                    masks.append(mask)
+            else:
+                held_masks.append(mask)
+                if targets is not None:
+                    held_targets.append(targets)
+                held += B
+                k = take = 0                         # the volumes this batch completes, and their slices
+                while done + k < V and take + depths[done + k] <= held:
+                    take += depths[done + k]
+                    k += 1
+                if k:
+                    m = torch.cat(held_masks) if len(held_masks) > 1 else held_masks[0]
+                    t = None
+                    if targets is not None:
+                        t = torch.cat(held_targets) if len(held_targets) > 1 else held_targets[0]
+                    out, counts, num = _filter3d(m[:take], None if t is None else t[:take], depths[done:done + k],
+                                                 keep_largest, min_size, connectivity, ignore_index)
+                    all_num.append(num)
+                    if counts is not None:
+                        all_counts.append(counts)
+                    if keep_masks:
+                        masks.extend(out.split(depths[done:done + k]))
+                    held_masks = [m[take:]] if take < held else []
+                    held_targets = [t[take:]] if t is not None and take < held else []
+                    held -= take
+                    done += k
+            idx += B
+    if idx != total:
+        raise ValueError(f"the loader yielded {idx} slices, but depths sum to {total}")
+    res = {"num": idx, "num_volumes": V, "dice": None, "iou": None, "mean_dice": None, "mean_iou": None}
+    if not components and keep_masks:
+        masks = list(torch.cat(masks).split(depths)) if masks else []
+    if components and all_counts:
+        vol_counts = torch.cat(all_counts)
+    if vol_counts is not None:
+        dice, iou = image_metrics(vol_counts)
+        res.update(dice=dice, iou=iou, mean_dice=dice.mean(), mean_iou=iou.mean())
+    if components:
+        res["num_components"] = torch.cat(all_num).to(torch.int64) if all_num else None
+    if keep_masks:
+        res["masks"] = masks
+    return res
 
 
 def predict_tta(model, data_loader, device, tta=True, keep_probs=False, **options):

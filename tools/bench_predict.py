@@ -29,6 +29,12 @@ connectivity 4 (the most components, no merging).  Per input: ``connected_compon
 scale ``boundary_metrics`` on the same mask; once ``predict_masks`` with counts; and the ``predict``
 loop (UNet, two batches) with the options off and on.  Prints one JSON line.
 
+``--components3d`` measures the volume-level post-processing (csrc/ccl3d.hip) on the same three inputs
+stacked as ``--batch`` slices (128 for the record) in 1 and in 8 volumes: ``connected_components_3d``
+(stf_ccl3d_label) and ``filter_components_3d`` with a target and ``keep_largest`` (stf_ccl3d_filter) at
+connectivity 26 (6 for the checkerboard), next to the 2-D ``connected_components`` /
+``filter_components`` on the same slices in the same rounds.  Prints one JSON line.
+
 ``--tta`` measures the work mirror test-time augmentation adds around the forwards (csrc/tta.hip) at
 the same shape: ``flip_planes`` of the 64 x 8 x 256^2 input per view, and ``stf_tta_accumulate`` on
 64 x K x 256^2 logits for K = 2 and 16 (a middle view: K planes read, K planes read and written; the
@@ -57,6 +63,7 @@ ap.add_argument("--rounds", type=int, default=7)
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--boundary", action="store_true", help="measure boundary_metrics instead")
 ap.add_argument("--components", action="store_true", help="measure the connected-component kernels instead")
+ap.add_argument("--components3d", action="store_true", help="measure the volume-level component kernels instead")
 ap.add_argument("--tta", action="store_true", help="measure the test-time-augmentation kernels instead")
 ap.add_argument("--host-images", type=int, default=8, help="images per regime of the scipy host timing")
 args = ap.parse_args()
@@ -293,6 +300,42 @@ if args.components:
                             "plain_min_max": [round(min(loop[False]), 3), round(max(loop[False]), 3)],
                             "keep_largest_min_max": [round(min(loop[True]), 3), round(max(loop[True]), 3)],
                             "added_us_per_image": round((loop_med[True] - loop_med[False]) * 1e3 / (2 * B), 2)},
+    }))
+    sys.exit(0)
+
+if args.components3d:
+    from stfunet import connected_components, connected_components_3d, filter_components, filter_components_3d
+    data = {k: (m.cuda(), t.cuda(), c) for k, (m, t, c) in component_masks().items()}
+    volumes = [v for v in (1, 8) if B % v == 0]
+    legs = []
+    for k, (m, t, c) in data.items():
+        c3 = 26 if c == 8 else 6
+        legs += [(f"label2d_{k}", lambda m=m, c=c: connected_components(m, c)),
+                 (f"filter2d_{k}", lambda m=m, t=t, c=c: filter_components(m, True, 0, c, target=t))]
+        for v in volumes:
+            d = [B // v] * v
+            legs += [(f"label3d_V{v}_{k}", lambda m=m, d=d, c3=c3: connected_components_3d(m, d, c3)),
+                     (f"filter3d_V{v}_{k}",
+                      lambda m=m, t=t, d=d, c3=c3: filter_components_3d(m, d, True, 0, c3, target=t))]
+    for _, fn in legs:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name, _ in legs}
+    for _ in range(args.rounds):
+        for name, fn in legs:
+            us[name].append(timed(fn, args.iters))
+    med = {k: statistics.median(v) for k, v in us.items()}
+    num = {f"V{v}_{k}": connected_components_3d(m, [B // v] * v, 26 if c == 8 else 6)[1].double().mean().item()
+           for k, (m, _, c) in data.items() for v in volumes}
+    print(json.dumps({
+        "tool": "bench_predict", "leg": "components3d", "shape": [B, H, W], "volumes": volumes,
+        "rounds": args.rounds, "iters": args.iters,
+        "us_per_call": {k: round(v, 1) for k, v in med.items()},
+        "us_per_call_min_max": {k: [round(min(v), 1), round(max(v), 1)] for k, v in us.items()},
+        "ratio_3d_over_2d": {f"{op}_V{v}_{k}": round(med[f"{op}3d_V{v}_{k}"] / med[f"{op}2d_{k}"], 2)
+                             for op in ("label", "filter") for v in volumes for k in data},
+        "mean_components_per_volume": num,
     }))
     sys.exit(0)
 
