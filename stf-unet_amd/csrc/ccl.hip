@@ -1,31 +1,64 @@
-// Connected components of binary masks on the device: labels in
-// scipy.ndimage.label's numbering, and the post-processing filter of the usual segmentation recipe
-// (keep the largest component, drop components below a size) with the per-image counts of the
-// filtered mask.  Every image of the uint8 [B][H][W] batch is labelled on its own; foreground is
-// mask != 0, connectivity 4 or 8, background outside the image.
+// Connected components of binary masks on the device:
+// labels in scipy.ndimage.label's numbering, and the post-processing filter of the usual
+// segmentation recipe (keep the largest component, drop components below a size) with the counts
+// of the filtered mask.  One kernel family serves two geometries, chosen at compile time (VOL):
+//   volumes  the uint8 [N][H][W] stack is cut into V volumes of consecutive slices by starts
+//            int32 [V + 1] (strictly ascending, starts[0] = 0, starts[V] = N; the host copy is
+//            validated, the device copy is what the kernels read); connectivity 6 / 18 / 26 is
+//            scipy's generate_binary_structure(3, 1 | 2 | 3).
+//   images   every slice is a volume one slice deep: {v = z, z0 = z} with no table, no search and
+//            no earlier slice; connectivity 4 / 8 is generate_binary_structure(2, 1 | 2).
+// Every volume is labelled on its own: foreground is mask != 0, outside the volume is background.
 //
-// The state is one int32 parent per pixel, L[p] (in-image linear index p = y W + x < 2^24; -1 on the
-// background), with the invariant L[p] <= p.  A fixed sequence of launches, none of which waits for
-// another workgroup, reads anything back or allocates:
-//   init      one wave per image row walks the row's 64-pixel chunks.  The foreground of a chunk is a
-//             ballot word; every pixel's parent is the first pixel of its horizontal run (clz on the
-//             zeros below the lane; a run that reaches the chunk's first pixel inherits the start the
+// State.  One int32 parent per voxel, L[g], holding the IN-VOLUME linear index
+// p = (z - z0) H W + y W + x of another voxel of the same component (z0 = the volume's first slice;
+// -1 on the background).  Invariant: L[p] <= p at all times, and L[p] is a member of p's component.
+//
+// Neighbours.  Row (z, y) is united with its "earlier" neighbour rows under in-row offsets:
+//
+//   level  connectivity   (z, y-1)     (z-1, y)     (z-1, y-1) and (z-1, y+1)
+//     1      4 |  6       {0}          {0}          --
+//     2      8 | 18       {-1,0,1}     {-1,0,1}     {0}
+//     3        | 26       {-1,0,1}     {-1,0,1}     {-1,0,1}
+//
+// (z-1, .) only when z > z0 -- never for an image, whose rows of the table end after the first
+// column -- and y +- 1 only inside [0, H).  Every offset set contains 0.  That is why one
+// de-duplication holds for any pair of rows: with `cur` and `up` the two rows' foreground, two runs
+// that touch under {-1,0,1} either overlap in some column (then the first column of the overlap is
+// the one pair V picks) or meet only corner to corner (then exactly one of DL / DR fires, at the
+// run's end, because `~up` and `~curL` / `~curR` exclude every pair an overlap or a nearer column
+// already covers).  Under {0} alone only V applies.  One union per touching pair of runs.
+//
+// Launches, none of which waits for another workgroup, reads anything back or allocates:
+//   init      one wave per row walks the row's 64-voxel chunks.  The foreground of a chunk is a
+//             ballot word; every voxel's parent is the first voxel of its horizontal run (clz on the
+//             zeros below the lane; a run that reaches the chunk's first voxel inherits the start the
 //             wave carries over the seam).  Only run starts are ever roots, so only they are ever the
 //             target of an atomic.  Zeroes the area words when the filter needs them.
-//   merge     one wave per row y >= 1, the row and the row above as bit words (lane c keeps word c).
-//             Bit arithmetic picks one pixel pair per touching pair of runs (below); each pair is
-//             united by find + atomicMin.  Integer atomics only, so the partition does not depend on
-//             the order of arrival, and the root of a tree is the smallest index of its component:
-//             every link points from a larger index to a smaller one of the same component.
-//   compress  one wave per row: every foreground pixel follows parents to its root and stores it; the
-//             first lane of every run segment of a chunk adds the segment's length to area[root]
-//             (filter only; one integer atomic per run and chunk, not per pixel).
-//   scan      one workgroup per image walks the image in raster order with a carry: "is a root"
-//             (L[p] == p) is scanned exclusively.  For the labels the 1-based rank is stored at the
-//             root: ranks follow each component's first pixel in raster order, scipy's numbering.  For
-//             the filter the same walk selects the largest area, ties to the smaller root.  The
-//             carry's final value is the number of components.
-//   labels / filter   one pass over the pixels writes the output (and the filter's counts).
+//   merge     one wave per row: the row and up to four neighbour rows as bit words (lane c keeps
+//             word c), one find + atomicMin union per touching pair of runs (merge_rows).
+//   compress  every voxel's parent becomes its root; area[root] += run segment lengths (filter).
+//   rank      images: one workgroup per image walks it in raster order with a carry (root_walk):
+//             "is a root" (L[p] == p) is scanned exclusively; the labels store the 1-based rank at
+//             the root, the filter selects the largest key (area << 32) | (0x7FFFFFFF - root) in the
+//             same walk -- the largest area, ties to the smaller root; the carry's final value is
+//             the number of components.  Volumes: the same walk per slice, in two levels, so that a
+//             workgroup's walk stays one slice long whatever the depth: `slice` counts each slice's
+//             roots (and finds its best key), `volume` (one wave per volume) turns the counts into
+//             the rank before each slice, the volume's total and its best key's root, and for the
+//             labels `slice` walks again from that prefix.  Raster order (z, y, x) of the roots = of
+//             each component's first voxel: scipy's numbering.
+//   labels / filter   one pass over the voxels writes the output (and the filter's counts).
+// Images: five launches for the labels, five and the counts' memset for the filter.  Volumes: seven,
+// and six and the memset.
+//
+// Termination.  find walks v -> L[v] while L[v] < v, so v strictly decreases; unite replaces the pair
+// (a, b) by two indices below max(a, b) (see unite).  Both compare unsigned and stop on any word
+// that broke the invariant, so no memory content can make them loop or leave the volume.
+//
+// Order-free result.  Integer atomics only.  Every link points from a larger index to a smaller one
+// of the same component, so the root of a tree is the smallest index of its component whatever
+// order the atomics arrive in; ranks, areas (integer adds) and the selection follow from the roots.
 //
 // Visibility.  Launch boundaries make each launch's stores visible to the next, so only merge has
 // concurrent writers of words it reads.  There a parent read may be stale (another XCD's L2, this
@@ -37,26 +70,139 @@
 // save iterations; correctness does not rest on it.  compress starts after merge has finished:
 // roots no longer change, and its in-place stores replace a parent by another ancestor of the same
 // tree, so a concurrent find that reads either value still reaches the root.
+// None of these arguments uses where a neighbour lies: which rows merge unites changes the
+// partition, not the properties.  Links never leave the volume because every index is relative to
+// z0 and no united pair spans two volumes.
+//
+// Bounds do not depend on the device copy of starts being right: the first slice of a row's volume
+// is clamped to [0, z], so every index stays inside [0, the voxel's own index], and the volume
+// number stays inside [0, V).
 //
 // Integer only: the same code in both storage builds.
-#include "ccl_common.h"
+#include "common.h"
 #include "../../include/stfunet.h"
 
 namespace {
 
-constexpr unsigned ROOT_MAX = 0xFFFFFFu;   // in-image indices fit 24 bits
+constexpr int BT = 256;                 // threads per workgroup of the row passes: one wave per row
+constexpr int RT = 1024;                // threads of the raster walks
+constexpr int NK = 4;                   // consecutive voxels per thread and step of the walks
+constexpr int MAXDIM = 4096;
+constexpr unsigned ROOT_TOP = 0x7FFFFFFFu;   // in-volume indices fit 31 bits
 
-// rows = B * H.  L [B][H][W] = first pixel of the pixel's horizontal run, -1 on the background;
-// area (or NULL) [B][H][W] = 0.
+typedef unsigned long long u64;
+
+STF_DEV u64 shfl_up1(u64 v, int lane) {
+  const u64 t = __shfl_up(v, 1, 64);
+  return lane == 0 ? 0ull : t;
+}
+STF_DEV u64 shfl_down1(u64 v, int lane) {
+  const u64 t = __shfl_down(v, 1, 64);
+  return lane == 63 ? 0ull : t;
+}
+
+// The foreground of one row as bit words, lane c keeping word c (W <= 4096 = 64 words); bits at
+// x >= W are zero.
+STF_DEV u64 row_word(const uint8_t* __restrict__ row, int W, int lane) {
+  const int nw = (W + 63) >> 6;
+  u64 mine = 0;
+  for (int c = 0; c < nw; ++c) {
+    const int x = c * 64 + lane;
+    const u64 w = __ballot(x < W && row[x] != 0);
+    if (lane == c) mine = w;
+  }
+  return mine;
+}
+
+// The root of foreground voxel v.  ATOMIC: relaxed agent-scope loads (merge, concurrent writers);
+// otherwise plain loads (compress).
+template <bool ATOMIC>
+STF_DEV int find_root(const int* L, int v) {
+  for (;;) {
+    const int p = ATOMIC ? __hip_atomic_load(L + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : L[v];
+    if ((unsigned)p >= (unsigned)v) return v;
+    v = p;
+  }
+}
+
+// Unite the components of foreground voxels a and b.
+// Terminates on its own: every turn replaces the pair (a, b) by (old, lo) with old < hi and
+// lo < hi, so max(a, b) strictly decreases and is bounded by 0; no turn waits for another thread.
+// Correct whatever find returned, as long as a and b are members of the two components: if hi was a
+// root, the atomicMin links it under lo and the two trees are one.  If it was not (another thread
+// linked it first, or find read a stale parent), the atomicMin returns its true parent old and leaves
+// L[hi] = min(old, lo); either way hi stays linked to one of the two and the other two, old and lo,
+// remain to be united, which the next turn does.
+STF_DEV void unite(int* L, int a, int b) {
+  a = find_root<true>(L, a);
+  b = find_root<true>(L, b);
+  while (a != b) {
+    const int hi = a > b ? a : b, lo = a > b ? b : a;
+    const int old = atomicMin(&L[hi], lo);
+    if ((unsigned)old >= (unsigned)hi) break;                       // hi was a root: linked
+    a = old;
+    b = lo;
+  }
+}
+
+STF_DEV int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+STF_DEV u64 wave_max(u64 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const u64 t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+
+// The keep-largest key: the largest area wins, ties go to the smaller root; 0 = no component
+// (areas are >= 1).
+STF_DEV u64 key_of(int area, int root) { return ((u64)(unsigned)area << 32) | (u64)(ROOT_TOP - (unsigned)root); }
+STF_DEV int root_of(u64 key) { return key ? (int)(ROOT_TOP - (unsigned)(key & 0xFFFFFFFFull)) : -1; }
+
+struct Vol {
+  int v;        // the volume of slice z
+  int z0;       // its first slice, 0 <= z0 <= z
+};
+
+// wave-uniform.  Volumes: the largest v with starts[v] <= z.  Images: slice z is volume z.
+template <bool VOL>
+STF_DEV Vol volume_of(const int* __restrict__ starts, int V, int z) {
+  if constexpr (!VOL) {
+    return {z, z};
+  } else {
+    int lo = 0, hi = V;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (starts[mid] <= z) lo = mid; else hi = mid;
+    }
+    int z0 = starts[lo];
+    if ((unsigned)z0 > (unsigned)z) z0 = z;
+    return {lo, z0};
+  }
+}
+
+// rows = N * H.  L = in-volume index of the first voxel of the voxel's horizontal run, -1 on the
+// background; area (or NULL) = 0.
+template <bool VOL>
 __global__ __launch_bounds__(BT) void ccl_init_kernel(const uint8_t* __restrict__ mask, long rows, int H, int W,
-                                                      int* __restrict__ L, int* __restrict__ area) {
+                                                      const int* __restrict__ starts, int V, int* __restrict__ L,
+                                                      int* __restrict__ area) {
   const int lane = threadIdx.x & 63;
   const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
   if (r >= rows) return;                                            // whole waves leave: no barrier below
-  const int y = (int)(r % H);
+  const int z = (int)(r / H);
+  const int y = (int)(r - (long)z * H);
+  const Vol vol = volume_of<VOL>(starts, V, z);
+  const int rowp = ((z - vol.z0) * H + y) * W;                      // < N H W < 2^31
   const long base = r * (long)W;
   const int nw = (W + 63) >> 6;
-  int carry = -1;                       // start of the run that reaches the previous chunk's last pixel
+  int carry = -1;                       // start of the run that reaches the previous chunk's last voxel
   for (int c = 0; c < nw; ++c) {
     const int x = c * 64 + lane;
     const bool in = x < W;
@@ -65,7 +211,7 @@ __global__ __launch_bounds__(BT) void ccl_init_kernel(const uint8_t* __restrict_
     const u64 zeros_below = ~w & ((1ull << lane) - 1);
     const int start = zeros_below ? c * 64 + 64 - __builtin_clzll(zeros_below) : (carry >= 0 ? carry : c * 64);
     if (in) {
-      L[base + x] = fg ? y * W + start : -1;
+      L[base + x] = fg ? rowp + start : -1;
       if (area) area[base + x] = 0;
     }
     const int last = __shfl(start, 63, 64);
@@ -73,89 +219,129 @@ __global__ __launch_bounds__(BT) void ccl_init_kernel(const uint8_t* __restrict_
   }
 }
 
-// One union per touching pair of runs of rows y - 1 and y.  With cur / up the rows' foreground:
-//   vertical    cur[x] & up[x], unless cur[x-1] & up[x-1] (the same two runs, united at x - 1 or before)
-//   diagonals   (connectivity 8) cur[x] & up[x-1], unless up[x] (the upper run reaches x: vertical at
-//               x) or cur[x-1] (vertical at x - 1); cur[x] & up[x+1], unless up[x] or cur[x+1].
-__global__ __launch_bounds__(BT) void ccl_merge_kernel(const uint8_t* __restrict__ mask, long rows, int H, int W,
-                                                       int conn8, int* L) {
-  const int lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  const long b = r / H;
-  const int y = (int)(r - b * H);
-  if (y == 0) return;                                               // wave-uniform
-  int* Li = L + b * (long)H * W;
-  const u64 cur = row_word(mask + r * (long)W, W, lane), up = row_word(mask + (r - 1) * (long)W, W, lane);
-  const u64 curL = (cur << 1) | (shfl_up1(cur, lane) >> 63);        // bit i = pixel x - 1
-  const u64 upL = (up << 1) | (shfl_up1(up, lane) >> 63);
-  const u64 curR = (cur >> 1) | (shfl_down1(cur, lane) << 63);      // bit i = pixel x + 1
-  const u64 upR = (up >> 1) | (shfl_down1(up, lane) << 63);
-  const u64 V = cur & up & ~(curL & upL);
-  const u64 DL = conn8 ? cur & upL & ~up & ~curL : 0ull;
-  const u64 DR = conn8 ? cur & upR & ~up & ~curR : 0ull;
+// The only union picker: one union per touching pair of runs of the row `cur` (in-volume index of
+// its first voxel: rowp) and the neighbour row `up`, which lies `delta` voxels earlier; diag: offsets
+// {-1, 0, 1}, else {0}.
+STF_DEV void merge_rows(int* Lv, u64 cur, u64 curL, u64 curR, const uint8_t* __restrict__ uprow, int W, int lane,
+                        int rowp, int delta, bool diag) {
+  const u64 up = row_word(uprow, W, lane);
+  const u64 upL = (up << 1) | (shfl_up1(up, lane) >> 63);           // bit i = voxel x - 1
+  const u64 upR = (up >> 1) | (shfl_down1(up, lane) << 63);         // bit i = voxel x + 1
+  const u64 Vt = cur & up & ~(curL & upL);
+  const u64 DL = diag ? cur & upL & ~up & ~curL : 0ull;
+  const u64 DR = diag ? cur & upR & ~up & ~curR : 0ull;
   const int nw = (W + 63) >> 6;
   for (int c = 0; c < nw; ++c) {
-    const u64 v = __shfl(V, c, 64), dl = __shfl(DL, c, 64), dr = __shfl(DR, c, 64);
+    const u64 v = __shfl(Vt, c, 64), dl = __shfl(DL, c, 64), dr = __shfl(DR, c, 64);
     if (!(v | dl | dr)) continue;                                   // wave-uniform
-    const int p = y * W + c * 64 + lane;
-    if ((v >> lane) & 1) unite(Li, p, p - W);
-    if ((dl >> lane) & 1) unite(Li, p, p - W - 1);                  // x >= 1: bit 0 of word 0 of upL is zero
-    if ((dr >> lane) & 1) unite(Li, p, p - W + 1);                  // x + 1 < W: up has no bit at x >= W
+    const int p = rowp + c * 64 + lane;
+    if ((v >> lane) & 1) unite(Lv, p, p - delta);
+    if ((dl >> lane) & 1) unite(Lv, p, p - delta - 1);              // x >= 1: bit 0 of word 0 of upL is zero
+    if ((dr >> lane) & 1) unite(Lv, p, p - delta + 1);              // x + 1 < W: up has no bit at x >= W
   }
 }
 
-// L[p] = root of p, in place.  area (or NULL; zero on entry): area[root] += pixels, one add per run
-// segment of a chunk.
-__global__ __launch_bounds__(BT) void ccl_compress_kernel(long rows, int H, int W, int* L, int* area) {
+// level: the row of the neighbour table.  An image has no earlier slice: only (z, y-1) remains.
+template <bool VOL>
+__global__ __launch_bounds__(BT) void ccl_merge_kernel(const uint8_t* __restrict__ mask, long rows, int H, int W,
+                                                       const int* __restrict__ starts, int V, int level, int* L) {
   const int lane = threadIdx.x & 63;
   const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
   if (r >= rows) return;
-  const long b = r / H;
-  const int y = (int)(r - b * H);
-  int* Li = L + b * (long)H * W;
+  const int z = (int)(r / H);
+  const int y = (int)(r - (long)z * H);
+  const Vol vol = volume_of<VOL>(starts, V, z);
+  const bool above = y > 0, below = y + 1 < H, back = VOL && z > vol.z0;   // wave-uniform
+  if (!above && !back) return;
+  const int HW = H * W;
+  int* Lv = L + (long)vol.z0 * HW;
+  const uint8_t* row = mask + r * (long)W;
+  const int rowp = ((z - vol.z0) * H + y) * W;
+  const u64 cur = row_word(row, W, lane);
+  const u64 curL = (cur << 1) | (shfl_up1(cur, lane) >> 63);
+  const u64 curR = (cur >> 1) | (shfl_down1(cur, lane) << 63);
+  if (above) merge_rows(Lv, cur, curL, curR, row - W, W, lane, rowp, W, level >= 2);
+  if (back) {
+    const uint8_t* prev = row - (long)HW;
+    merge_rows(Lv, cur, curL, curR, prev, W, lane, rowp, HW, level >= 2);
+    if (level >= 2) {
+      if (above) merge_rows(Lv, cur, curL, curR, prev - W, W, lane, rowp, HW + W, level >= 3);
+      if (below) merge_rows(Lv, cur, curL, curR, prev + W, W, lane, rowp, HW - W, level >= 3);
+    }
+  }
+}
+
+// L[g] = root of the voxel, in place.  area (or NULL; zero on entry): area[root] += voxels, per run
+// segment of a chunk or, with CARRY, per row (below).  A volume's area is below 2^31: it fits the
+// int32 word.  Images add per segment: measured at 256 x 256, the carried sum halves the time of a
+// percolation mask's filter but costs the checkerboard's 4 to 6 % (profiles/ccl_family/README.md).
+template <bool VOL, bool CARRY>
+__global__ __launch_bounds__(BT) void ccl_compress_kernel(long rows, int H, int W, const int* __restrict__ starts,
+                                                          int V, int* L, int* area) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const Vol vol = volume_of<VOL>(starts, V, (int)(r / H));
+  const long vbase = (long)vol.z0 * H * W;
+  int* Lv = L + vbase;
   const int nw = (W + 63) >> 6;
+  int hot = -1, hot_sum = 0;            // wave-uniform: a root and the voxels of this row collected for it
   for (int c = 0; c < nw; ++c) {
     const int x = c * 64 + lane;
-    const int v = x < W ? Li[y * W + x] : -1;
+    const int v = x < W ? L[r * (long)W + x] : -1;
     const bool fg = v >= 0;
     int root = v;
     if (fg) {
-      root = find_root<false>(Li, v);
-      Li[y * W + x] = root;
+      root = find_root<false>(Lv, v);
+      L[r * (long)W + x] = root;
     }
     if (area) {
       const u64 w = __ballot(fg);
-      if (fg && (lane == 0 || !((w >> (lane - 1)) & 1))) {
-        const u64 t = ~(w >> lane);                                 // zero only for lane 0 of a full word
-        atomicAdd(&area[b * (long)H * W + root], t ? __builtin_ctzll(t) : 64);
+      const bool first = fg && (lane == 0 || !((w >> (lane - 1)) & 1));
+      const u64 t = ~(w >> lane);                                   // zero only for lane 0 of a full word
+      const int len = first ? (t ? __builtin_ctzll(t) : 64) : 0;
+      // A spanning component would take one add per run segment of the whole volume at one
+      // address.  With CARRY the segments of the chunk's first root are summed in the wave and
+      // carried along the row while the next chunk starts with the same root; the other segments
+      // add on their own, as all of them do without CARRY.
+      const u64 adds = CARRY ? __ballot(first) : 0ull;
+      if (!CARRY) {
+        if (first) atomicAdd(&area[vbase + root], len);
+      } else if (adds) {                                            // wave-uniform
+        const int r0 = __shfl(root, __builtin_ctzll(adds), 64);
+        const bool same = first && root == r0;
+        const int s = wave_sum_i(same ? len : 0);
+        if (r0 != hot) {
+          if (lane == 0 && hot_sum) atomicAdd(&area[vbase + hot], hot_sum);
+          hot = r0;
+          hot_sum = 0;
+        }
+        hot_sum += s;
+        if (first && !same) atomicAdd(&area[vbase + root], len);
       }
     }
   }
+  if (area && lane == 0 && hot_sum) atomicAdd(&area[vbase + hot], hot_sum);
 }
 
-// One workgroup per image.  select == 0: aux[root] = 1-based rank of the root in raster order.
-// select != 0: aux holds the areas; sel[b] = the root of the largest area, ties to the smaller root
-// (-1 without a component).  num (or NULL) [b] = number of roots.
-__global__ __launch_bounds__(RT) void ccl_scan_kernel(const int* __restrict__ L, int* __restrict__ aux, int HW,
-                                                      int select, int* __restrict__ num, int* __restrict__ sel) {
+// The raster walk of one workgroup of RT threads over one slice: word i of Lz (i < HW) is a root
+// when it holds its own in-volume index own + i.  "Is a root" is scanned exclusively, starting at
+// `carry`; every root p is handed to at_root(p, its 1-based rank), and the return value is carry +
+// the slice's roots, in every thread.
+template <class F>
+STF_DEV int root_walk(const int* Lz, int HW, int own, int carry, F at_root) {
   __shared__ int wtot[RT / 64];
-  __shared__ u64 wbest[RT / 64];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int* Li = L + (long)blockIdx.x * HW;
-  int* Ai = aux + (long)blockIdx.x * HW;
-  int carry = 0;
-  u64 best = 0;                                                     // (area << 32) | (ROOT_MAX - root); 0 = none
   for (int base = 0; base < HW; base += RT * NK) {
     const int i0 = base + tid * NK;
     bool root[NK];
-    int cnt = 0;
+    int c = 0;
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
-      root[k] = i0 + k < HW && Li[i0 + k] == i0 + k;
-      cnt += root[k];
+      root[k] = i0 + k < HW && Lz[i0 + k] == own + i0 + k;
+      c += root[k];
     }
-    int inc = cnt;
+    int inc = c;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
       const int t = __shfl_up(inc, o, 64);
@@ -170,172 +356,374 @@ __global__ __launch_bounds__(RT) void ccl_scan_kernel(const int* __restrict__ L,
       before += w < wv ? t : 0;
       total += t;
     }
-    int run = carry + before + inc - cnt;
+    int run = carry + before + inc - c;
 #pragma unroll
     for (int k = 0; k < NK; ++k) {
       if (!root[k]) continue;
       ++run;
-      if (select) {
-        const u64 key = ((u64)(unsigned)Ai[i0 + k] << 32) | (u64)(ROOT_MAX - (unsigned)(i0 + k));
-        best = key > best ? key : best;
-      } else {
-        Ai[i0 + k] = run;
-      }
+      at_root(own + i0 + k, run);
     }
     carry += total;
     __syncthreads();                                                // wtot is free again
   }
-  if (select) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const u64 t = __shfl_xor(best, o, 64);
-      best = t > best ? t : best;
+  return carry;
+}
+
+// The workgroup's largest key in two steps: every thread of the RT publishes (each wave's maximum
+// goes to wbest, a barrier follows), then thread 0 folds the waves' maxima into its own.
+STF_DEV u64 publish_max(u64 best, u64* wbest) {
+  best = wave_max(best);
+  if ((threadIdx.x & 63) == 0) wbest[threadIdx.x >> 6] = best;
+  __syncthreads();
+  return best;
+}
+STF_DEV u64 fold_max(u64 best, const u64* wbest) {
+  for (int w = 1; w < RT / 64; ++w) best = wbest[w] > best ? wbest[w] : best;
+  return best;
+}
+
+// Images: one workgroup per image.  !SELECT: aux[root] = 1-based rank of the root in raster order.
+// SELECT: aux holds the areas; sel[b] = the root of the largest key (-1 without a component).
+// num (or NULL) [b] = number of roots.
+template <bool SELECT>
+__global__ __launch_bounds__(RT) void ccl_scan_kernel(const int* __restrict__ L, int* __restrict__ aux, int HW,
+                                                      int* __restrict__ num, int* __restrict__ sel) {
+  __shared__ u64 wbest[RT / 64];
+  const int b = blockIdx.x;
+  int* Ai = aux + (long)b * HW;
+  u64 best = 0;
+  const int n = root_walk(L + (long)b * HW, HW, 0, 0, [&](int p, int rank) {
+    if (SELECT) {
+      const u64 key = key_of(Ai[p], p);
+      best = key > best ? key : best;
+    } else {
+      Ai[p] = rank;
     }
-    if (lane == 0) wbest[wv] = best;
-    __syncthreads();
-  }
-  if (tid != 0) return;
-  if (num) num[blockIdx.x] = carry;
-  if (select) {
-    for (int w = 1; w < RT / 64; ++w) best = wbest[w] > best ? wbest[w] : best;
-    sel[blockIdx.x] = best ? (int)(ROOT_MAX - (unsigned)(best & 0xFFFFFFFFull)) : -1;
-  }
+  });
+  if (SELECT) best = publish_max(best, wbest);
+  if (threadIdx.x != 0) return;
+  if (num) num[b] = n;
+  if (SELECT) sel[b] = root_of(fold_max(best, wbest));
 }
 
+// Volumes: one workgroup per slice.
+//   COUNT   cnt[z] = roots in the slice; bestz (or NULL) [z] = the largest key among them.
+//   !COUNT  aux[root] = 1-based rank in the volume, the carry starting at cnt[z], which by then
+//           holds the roots of the volume's earlier slices (ccl3d_volume_kernel).
+template <bool COUNT>
+__global__ __launch_bounds__(RT) void ccl_slice_kernel(const int* __restrict__ L, int* __restrict__ aux, int HW,
+                                                       const int* __restrict__ starts, int V, int* __restrict__ cnt,
+                                                       u64* __restrict__ bestz) {
+  __shared__ u64 wbest[RT / 64];
+  const int z = blockIdx.x;
+  const Vol vol = volume_of<true>(starts, V, z);
+  int* Av = aux + (long)vol.z0 * HW;
+  u64 best = 0;
+  const int n = root_walk(L + (long)z * HW, HW, (z - vol.z0) * HW, COUNT ? 0 : cnt[z], [&](int p, int rank) {
+    if (COUNT) {
+      if (bestz) {
+        const u64 key = key_of(Av[p], p);
+        best = key > best ? key : best;
+      }
+    } else {
+      Av[p] = rank;
+    }
+  });
+  if (!COUNT) return;
+  if (bestz) best = publish_max(best, wbest);                       // workgroup-uniform
+  if (threadIdx.x != 0) return;
+  cnt[z] = n;
+  if (bestz) bestz[z] = fold_max(best, wbest);
+}
+
+// One wave per volume over its slices in order: cnt[z] becomes the number of roots in the volume's
+// earlier slices, num (or NULL) [v] the volume's total; with bestz, sel[v] = the root of the largest
+// key (-1 without a component).
+__global__ __launch_bounds__(64) void ccl3d_volume_kernel(const int* __restrict__ starts, int N, int* __restrict__ cnt,
+                                                          const u64* __restrict__ bestz, int* __restrict__ num,
+                                                          int* __restrict__ sel) {
+  const int lane = threadIdx.x, v = blockIdx.x;
+  int za = starts[v], zb = starts[v + 1];
+  za = za < 0 ? 0 : za;
+  zb = zb > N ? N : zb;
+  int carry = 0;
+  u64 best = 0;
+  for (int z0 = za; z0 < zb; z0 += 64) {
+    const int z = z0 + lane;
+    const int c = z < zb ? cnt[z] : 0;
+    int inc = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += t;
+    }
+    if (z < zb) {
+      cnt[z] = carry + inc - c;
+      if (bestz) best = bestz[z] > best ? bestz[z] : best;
+    }
+    carry += __shfl(inc, 63, 64);
+  }
+  if (bestz) best = wave_max(best);
+  if (lane != 0) return;
+  if (num) num[v] = carry;
+  if (bestz) sel[v] = root_of(best);
+}
+
+template <bool VOL>
 __global__ __launch_bounds__(BT) void ccl_labels_kernel(const int* __restrict__ L, const int* __restrict__ rank,
-                                                        long n, long HW, int* __restrict__ labels) {
-  const long i = (long)blockIdx.x * BT + threadIdx.x;
-  if (i >= n) return;
-  const int v = L[i];
-  labels[i] = v < 0 ? 0 : rank[i / HW * HW + v];
+                                                        long rows, int H, int W, const int* __restrict__ starts,
+                                                        int V, int* __restrict__ labels) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const Vol vol = volume_of<VOL>(starts, V, (int)(r / H));
+  const int* Rv = rank + (long)vol.z0 * H * W;
+  for (int x = lane; x < W; x += 64) {
+    const long i = r * (long)W + x;
+    const int v = L[i];
+    labels[i] = v < 0 ? 0 : Rv[v];
+  }
 }
 
-// out = mask where the pixel's component passes, 0 elsewhere; counts (or NULL; zero on entry)
-// [B][3] += (|P' & T|, |P'|, |T|) of the row with stf_predict_mask's rules.
+// rows of one slice per wave of the filter pass: a volume's three count words take one add per
+// group, not per row; an image's rows are few enough
+template <bool VOL>
+constexpr int FR = VOL ? 16 : 1;
+
+// out = mask where the voxel's component passes, 0 elsewhere; counts (or NULL; zero on entry)
+// [V][3] += (|P' & T|, |P'|, |T|) with stf_predict_mask's rules.  One wave per group of R rows of one
+// slice (groups = N * ceil(H / R)).
+template <bool VOL, int R>
 __global__ __launch_bounds__(BT) void ccl_filter_kernel(const uint8_t* __restrict__ mask,
-                                                        const int64_t* __restrict__ target, long rows, int H, int W,
+                                                        const int64_t* __restrict__ target, long groups, int H, int W,
+                                                        const int* __restrict__ starts, int V,
                                                         const int* __restrict__ L, const int* __restrict__ area,
                                                         const int* __restrict__ sel, int keep_largest, long min_size,
                                                         long ignore, uint8_t* __restrict__ out,
                                                         u64* __restrict__ counts) {
   const int lane = threadIdx.x & 63;
-  const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
-  if (r >= rows) return;
-  const long b = r / H;
-  const int* Ai = area + b * (long)H * W;
-  const int largest = keep_largest ? sel[b] : -1;
+  const long g = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
+  if (g >= groups) return;
+  const int per = (H + R - 1) / R;
+  const int z = (int)(g / per);
+  const int y0 = (int)(g - (long)z * per) * R;
+  const int y1 = y0 + R < H ? y0 + R : H;
+  const Vol vol = volume_of<VOL>(starts, V, z);
+  const int* Av = area + (long)vol.z0 * H * W;
+  const int largest = keep_largest ? sel[vol.v] : -1;
   int ni = 0, np = 0, nt = 0;
-  for (int x = lane; x < W; x += 64) {
-    const long i = r * (long)W + x;
-    const int v = L[i];
-    const bool pass = v >= 0 && (long)Ai[v] >= min_size && (!keep_largest || v == largest);
-    const uint8_t m = pass ? mask[i] : (uint8_t)0;
-    out[i] = m;
-    if (counts) {
-      const long tv = target[i];
-      const bool keep = !(ignore >= 0 && tv == ignore);
-      const bool p = keep && m != 0, t = keep && tv > 0;
-      ni += p && t;
-      np += p;
-      nt += t;
+  for (int y = y0; y < y1; ++y) {
+    const long row = ((long)z * H + y) * W;
+    for (int x = lane; x < W; x += 64) {
+      const long i = row + x;
+      const int v = L[i];
+      const bool pass = v >= 0 && (long)Av[v] >= min_size && (!keep_largest || v == largest);
+      const uint8_t m = pass ? mask[i] : (uint8_t)0;
+      out[i] = m;
+      if (counts) {
+        const long tv = target[i];
+        const bool keep = !(ignore >= 0 && tv == ignore);
+        const bool p = keep && m != 0, t = keep && tv > 0;
+        ni += p && t;
+        np += p;
+        nt += t;
+      }
     }
   }
   if (!counts) return;                                              // wave-uniform
   ni = wave_sum_i(ni);
   np = wave_sum_i(np);
   nt = wave_sum_i(nt);
-  if (lane == 0 && ni) atomicAdd(&counts[b * 3], (u64)ni);
-  if (lane == 1 && np) atomicAdd(&counts[b * 3 + 1], (u64)np);
-  if (lane == 2 && nt) atomicAdd(&counts[b * 3 + 2], (u64)nt);
+  if (lane == 0 && ni) atomicAdd(&counts[vol.v * 3], (u64)ni);
+  if (lane == 1 && np) atomicAdd(&counts[vol.v * 3 + 1], (u64)np);
+  if (lane == 2 && nt) atomicAdd(&counts[vol.v * 3 + 2], (u64)nt);
 }
 
-// B, H, W inside the limits and B * H * W < 2^31
-inline bool sizes_ok(int B, int H, int W) {
-  if (B < 1 || H < 1 || W < 1 || H > MAXDIM || W > MAXDIM) return false;
-  return (long)B * H * W < (1L << 31);
+// ---------------------------------------------------------------- host side
+inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+inline unsigned row_grid(long rows) { return (unsigned)((rows + BT / 64 - 1) / (BT / 64)); }
+
+// N, H, W, V inside the limits and N * H * W < 2^31 (images: V = N)
+inline bool sizes_ok(int N, int H, int W, int V) {
+  if (N < 1 || H < 1 || W < 1 || H > MAXDIM || W > MAXDIM || V < 1 || V > N) return false;
+  return (long)N * H * W < (1L << 31);
 }
 
-// scratch: [selected root int32 [B], 256-B rounded][parents int32 [n]][ranks or areas int32 [n]]
+// strictly ascending from 0 to N
+inline bool starts_ok(const int32_t* starts, int V, int N) {
+  if (starts[0] != 0 || starts[V] != N) return false;
+  for (int v = 0; v < V; ++v)
+    if (starts[v] >= starts[v + 1]) return false;
+  return true;
+}
+
+// What all four entry points refuse before anything is launched, from the arguments they share:
+// the row of the neighbour table for `connectivity`, 0 to refuse.  num may be NULL here.
+template <bool VOL>
+int level_or_refuse(const void* mask, int N, int H, int W, const int32_t* starts_dev, const int32_t* starts_host,
+                    int V, int connectivity, const void* num, const void* scratch) {
+  if (!mask || !scratch || !sizes_ok(N, H, W, V)) return 0;
+  if (((uintptr_t)scratch & 7) || ((uintptr_t)num & 3)) return 0;
+  if (VOL) {
+    if (!starts_dev || !starts_host || ((uintptr_t)starts_dev & 3) || ((uintptr_t)starts_host & 3)) return 0;
+    if (!starts_ok(starts_host, V, N)) return 0;
+    return connectivity == 6 ? 1 : connectivity == 18 ? 2 : connectivity == 26 ? 3 : 0;
+  }
+  return connectivity == 4 ? 1 : connectivity == 8 ? 2 : 0;
+}
+
+// scratch: [selected root int32 [V], 256-B rounded]
+//          volumes only: [roots per slice int32 [N], 256-B rounded][best key per slice u64 [N], 256-B rounded]
+//          [parents int32 [n]][ranks or areas int32 [n]]
 struct Scratch {
   int* sel;
+  int* cnt;
+  u64* best;
   int* L;
   int* aux;
 };
-inline Scratch carve(void* scratch, int B, long n) {
+template <bool VOL>
+size_t scratch_bytes(int N, int H, int W, int V) {
+  if (!sizes_ok(N, H, W, V)) return 0;
+  size_t head = round_up((size_t)V * sizeof(int), 256);
+  if (VOL) head += round_up((size_t)N * sizeof(int), 256) + round_up((size_t)N * sizeof(u64), 256);
+  return round_up(head + (size_t)N * H * W * 2 * sizeof(int), 8);
+}
+template <bool VOL>
+Scratch carve(void* scratch, int N, int V, long n) {
   char* p = (char*)scratch;
-  Scratch s;
-  s.sel = (int*)p;
-  p += round_up((size_t)B * sizeof(int), 256);
+  Scratch s = {(int*)p, nullptr, nullptr, nullptr, nullptr};
+  p += round_up((size_t)V * sizeof(int), 256);
+  if (VOL) {
+    s.cnt = (int*)p;
+    p += round_up((size_t)N * sizeof(int), 256);
+    s.best = (u64*)p;
+    p += round_up((size_t)N * sizeof(u64), 256);
+  }
   s.L = (int*)p;
   s.aux = s.L + n;
   return s;
 }
 
-// init, merge, compress: afterwards L holds every pixel's root (and aux the areas when with_area)
-int label_roots(const uint8_t* mask, int B, int H, int W, int connectivity, const Scratch& sc, bool with_area,
-                hipStream_t s) {
-  const long rows = (long)B * H;
+// init, merge, compress: afterwards L holds every voxel's root (and aux the areas when with_area)
+template <bool VOL>
+int label_roots(const uint8_t* mask, int N, int H, int W, const int* starts, int V, int level, const Scratch& sc,
+                bool with_area, hipStream_t s) {
+  const long rows = (long)N * H;
   int* area = with_area ? sc.aux : nullptr;
-  hipLaunchKernelGGL(ccl_init_kernel, dim3(row_grid(rows)), dim3(BT), 0, s, mask, rows, H, W, sc.L, area);
+  hipLaunchKernelGGL(ccl_init_kernel<VOL>, dim3(row_grid(rows)), dim3(BT), 0, s, mask, rows, H, W, starts, V, sc.L,
+                     area);
   STF_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ccl_merge_kernel, dim3(row_grid(rows)), dim3(BT), 0, s, mask, rows, H, W,
-                     connectivity == 8 ? 1 : 0, sc.L);
+  hipLaunchKernelGGL(ccl_merge_kernel<VOL>, dim3(row_grid(rows)), dim3(BT), 0, s, mask, rows, H, W, starts, V, level,
+                     sc.L);
   STF_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ccl_compress_kernel, dim3(row_grid(rows)), dim3(BT), 0, s, rows, H, W, sc.L, area);
+  hipLaunchKernelGGL((ccl_compress_kernel<VOL, VOL>), dim3(row_grid(rows)), dim3(BT), 0, s, rows, H, W, starts, V,
+                     sc.L, area);
+  STF_CHECK_LAUNCH();
+  return 0;
+}
+
+// The rank passes between compress and the output pass.  Afterwards num (or NULL) holds the
+// component counts and, with_area, sc.sel the selected roots; otherwise sc.aux holds the ranks.
+template <bool VOL>
+int rank_roots(int N, int H, int W, const int* starts, int V, const Scratch& sc, bool with_area, int32_t* num,
+               hipStream_t s) {
+  const int* L = sc.L;
+  if (!VOL) {
+    if (with_area)
+      hipLaunchKernelGGL(ccl_scan_kernel<true>, dim3((unsigned)N), dim3(RT), 0, s, L, sc.aux, H * W, num, sc.sel);
+    else
+      hipLaunchKernelGGL(ccl_scan_kernel<false>, dim3((unsigned)N), dim3(RT), 0, s, L, sc.aux, H * W, num, sc.sel);
+    STF_CHECK_LAUNCH();
+    return 0;
+  }
+  u64* best = with_area ? sc.best : nullptr;
+  hipLaunchKernelGGL(ccl_slice_kernel<true>, dim3((unsigned)N), dim3(RT), 0, s, L, sc.aux, H * W, starts, V, sc.cnt,
+                     best);
+  STF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(ccl3d_volume_kernel, dim3((unsigned)V), dim3(64), 0, s, starts, N, sc.cnt, (const u64*)best, num,
+                     sc.sel);
+  STF_CHECK_LAUNCH();
+  if (with_area) return 0;
+  hipLaunchKernelGGL(ccl_slice_kernel<false>, dim3((unsigned)N), dim3(RT), 0, s, L, sc.aux, H * W, starts, V, sc.cnt,
+                     best);
+  STF_CHECK_LAUNCH();
+  return 0;
+}
+
+template <bool VOL>
+int label(const uint8_t* mask, int N, int H, int W, const int32_t* starts_dev, const int32_t* starts_host, int V,
+          int connectivity, int32_t* labels, int32_t* num, void* scratch, stf_stream_t stream) {
+  const int level = level_or_refuse<VOL>(mask, N, H, W, starts_dev, starts_host, V, connectivity, num, scratch);
+  if (!level || !labels || !num || ((uintptr_t)labels & 3)) return STF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long rows = (long)N * H;
+  const Scratch sc = carve<VOL>(scratch, N, V, rows * W);
+  int rc = label_roots<VOL>(mask, N, H, W, starts_dev, V, level, sc, false, s);
+  if (rc) return rc;
+  rc = rank_roots<VOL>(N, H, W, starts_dev, V, sc, false, num, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(ccl_labels_kernel<VOL>, dim3(row_grid(rows)), dim3(BT), 0, s, (const int*)sc.L,
+                     (const int*)sc.aux, rows, H, W, starts_dev, V, labels);
+  STF_CHECK_LAUNCH();
+  return 0;
+}
+
+template <bool VOL>
+int filter(const uint8_t* mask, const int64_t* target, int N, int H, int W, const int32_t* starts_dev,
+           const int32_t* starts_host, int V, int connectivity, int keep_largest, int64_t min_size,
+           int64_t ignore_index, uint8_t* out, int64_t* counts, int32_t* num, void* scratch, stf_stream_t stream) {
+  const int level = level_or_refuse<VOL>(mask, N, H, W, starts_dev, starts_host, V, connectivity, num, scratch);
+  if (!level || !out || min_size < 0 || (counts && !target) || out == mask) return STF_EINVAL;
+  if (((uintptr_t)counts & 7) || ((uintptr_t)target & 7)) return STF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const Scratch sc = carve<VOL>(scratch, N, V, (long)N * H * W);
+  if (counts) {
+    hipError_t e = stf::memset_async(counts, 0, (size_t)V * 3 * sizeof(int64_t), s);
+    if (e != hipSuccess) return (int)e;
+  }
+  int rc = label_roots<VOL>(mask, N, H, W, starts_dev, V, level, sc, true, s);
+  if (rc) return rc;
+  rc = rank_roots<VOL>(N, H, W, starts_dev, V, sc, true, num, s);
+  if (rc) return rc;
+  constexpr int R = FR<VOL>;
+  const long groups = (long)N * ((H + R - 1) / R);
+  hipLaunchKernelGGL((ccl_filter_kernel<VOL, R>), dim3(row_grid(groups)), dim3(BT), 0, s, mask,
+                     counts ? target : nullptr, groups, H, W, starts_dev, V, (const int*)sc.L, (const int*)sc.aux,
+                     (const int*)sc.sel, keep_largest ? 1 : 0, (long)min_size, (long)ignore_index, out, (u64*)counts);
   STF_CHECK_LAUNCH();
   return 0;
 }
 
 }  // namespace
 
-extern "C" size_t stf_ccl_scratch_bytes(int B, int H, int W) {
-  if (!sizes_ok(B, H, W)) return 0;
-  const size_t n = (size_t)B * H * W;
-  return round_up(round_up((size_t)B * sizeof(int), 256) + n * 2 * sizeof(int), 8);
-}
+extern "C" size_t stf_ccl_scratch_bytes(int B, int H, int W) { return scratch_bytes<false>(B, H, W, B); }
+
+extern "C" size_t stf_ccl3d_scratch_bytes(int N, int H, int W, int V) { return scratch_bytes<true>(N, H, W, V); }
 
 extern "C" int stf_ccl_label(const uint8_t* mask, int B, int H, int W, int connectivity, int32_t* labels,
                              int32_t* num, void* scratch, stf_stream_t stream) {
-  if (!mask || !labels || !num || !scratch || !sizes_ok(B, H, W)) return STF_EINVAL;
-  if (connectivity != 4 && connectivity != 8) return STF_EINVAL;
-  if (((uintptr_t)scratch & 7) || ((uintptr_t)labels & 3) || ((uintptr_t)num & 3)) return STF_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const long n = (long)B * H * W;
-  const Scratch sc = carve(scratch, B, n);
-  const int rc = label_roots(mask, B, H, W, connectivity, sc, false, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ccl_scan_kernel, dim3((unsigned)B), dim3(RT), 0, s, (const int*)sc.L, sc.aux, H * W, 0, num,
-                     sc.sel);
-  STF_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ccl_labels_kernel, dim3((unsigned)((n + BT - 1) / BT)), dim3(BT), 0, s, (const int*)sc.L,
-                     (const int*)sc.aux, n, (long)H * W, labels);
-  STF_CHECK_LAUNCH();
-  return 0;
+  return label<false>(mask, B, H, W, nullptr, nullptr, B, connectivity, labels, num, scratch, stream);
 }
 
 extern "C" int stf_ccl_filter(const uint8_t* mask, const int64_t* target, int B, int H, int W, int connectivity,
                               int keep_largest, int64_t min_size, int64_t ignore_index, uint8_t* out,
                               int64_t* counts, int32_t* num, void* scratch, stf_stream_t stream) {
-  if (!mask || !out || !scratch || !sizes_ok(B, H, W)) return STF_EINVAL;
-  if ((connectivity != 4 && connectivity != 8) || min_size < 0 || (counts && !target) || out == mask)
-    return STF_EINVAL;
-  if (((uintptr_t)scratch & 7) || ((uintptr_t)counts & 7) || ((uintptr_t)target & 7) || ((uintptr_t)num & 3))
-    return STF_EINVAL;
-  hipStream_t s = (hipStream_t)stream;
-  const long n = (long)B * H * W, rows = (long)B * H;
-  const Scratch sc = carve(scratch, B, n);
-  if (counts) {
-    hipError_t e = stf::memset_async(counts, 0, (size_t)B * 3 * sizeof(int64_t), s);
-    if (e != hipSuccess) return (int)e;
-  }
-  const int rc = label_roots(mask, B, H, W, connectivity, sc, true, s);
-  if (rc) return rc;
-  hipLaunchKernelGGL(ccl_scan_kernel, dim3((unsigned)B), dim3(RT), 0, s, (const int*)sc.L, sc.aux, H * W, 1, num,
-                     sc.sel);
-  STF_CHECK_LAUNCH();
-  hipLaunchKernelGGL(ccl_filter_kernel, dim3(row_grid(rows)), dim3(BT), 0, s, mask, counts ? target : nullptr, rows,
-                     H, W, (const int*)sc.L, (const int*)sc.aux, (const int*)sc.sel, keep_largest ? 1 : 0,
-                     (long)min_size, (long)ignore_index, out, (u64*)counts);
-  STF_CHECK_LAUNCH();
-  return 0;
+  return filter<false>(mask, target, B, H, W, nullptr, nullptr, B, connectivity, keep_largest, min_size,
+                       ignore_index, out, counts, num, scratch, stream);
+}
+
+extern "C" int stf_ccl3d_label(const uint8_t* mask, int N, int H, int W, const int32_t* starts_dev,
+                               const int32_t* starts_host, int V, int connectivity, int32_t* labels, int32_t* num,
+                               void* scratch, stf_stream_t stream) {
+  return label<true>(mask, N, H, W, starts_dev, starts_host, V, connectivity, labels, num, scratch, stream);
+}
+
+extern "C" int stf_ccl3d_filter(const uint8_t* mask, const int64_t* target, int N, int H, int W,
+                                const int32_t* starts_dev, const int32_t* starts_host, int V, int connectivity,
+                                int keep_largest, int64_t min_size, int64_t ignore_index, uint8_t* out, int64_t* counts,
+                                int32_t* num, void* scratch, stf_stream_t stream) {
+  return filter<true>(mask, target, N, H, W, starts_dev, starts_host, V, connectivity, keep_largest, min_size,
+                      ignore_index, out, counts, num, scratch, stream);
 }

@@ -21,7 +21,7 @@ gfx950 kernels of ``csrc/predict.hip``:
   on the batch and its flipped copies, the un-flipped class probabilities averaged in a fixed order
   (``csrc/tta.hip``), and ``predict``'s loop with each batch's mask taken from that mean
 * ``connected_components_3d`` / ``filter_components_3d`` / ``predict_volumes``  the same labels and
-  clean-up per volume of stacked slices (6 / 18 / 26 connectivity, ``csrc/ccl3d.hip``), and the loop
+  clean-up per volume of stacked slices (6 / 18 / 26 connectivity, the same ``csrc/ccl.hip``), and the loop
   that groups a patient's slices: 3-D post-processing and per-volume (per-case) Dice / IoU
 
 ``predict(model, loader, device, rule="sigmoid", channel=0, paint=0)`` reproduces test.py bit for
@@ -52,6 +52,27 @@ def _device_only(t, what):
     if not t.is_cuda:
         raise RuntimeError(f"stfunet.predict.{what} runs the gfx950 predict kernels: tensors must be on a ROCm "
                            "device (no CPU fallback)")
+
+
+def _check_target_shape(target, shape):
+    if tuple(target.shape) != tuple(shape):
+        raise ValueError(f"target {tuple(target.shape)} does not match the mask's {tuple(shape)}")
+
+
+def _check_target_dtype(target):
+    if target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
+        raise ValueError(f"target must be an integer tensor, not {target.dtype}")
+
+
+def _check_target(target, shape):
+    """``target`` must be an integer tensor of the mask's ``shape``."""
+    _check_target_shape(target, shape)
+    _check_target_dtype(target)
+
+
+def _ignore(ignore_index):
+    """The entry points' ``ignore_index``: -1 for none."""
+    return -1 if ignore_index is None else ignore_index
 
 
 def _check_paint(color, alpha, paint):
@@ -95,14 +116,13 @@ def predict_masks(outputs, rule="argmax", channel=0, threshold=0.5, target=None,
     if target is not None:
         target = target.detach().to(device=x.device, dtype=torch.int64).contiguous()
         counts = torch.empty((B, 3), dtype=torch.int64, device=x.device)
-    ignore = -1 if ignore_index is None else ignore_index
     with torch.cuda.device(x.device):
         if rule == "threshold":
-            call("stf_predict_threshold", _p(x), _p(target), B, K, H * W, channel, threshold, ignore, _p(mask),
-                 _p(counts), stream())
-        else:
-            call("stf_predict_mask", _p(x), _p(target), B, K, H * W, RULES[rule], channel, threshold, ignore,
+            call("stf_predict_threshold", _p(x), _p(target), B, K, H * W, channel, threshold, _ignore(ignore_index),
                  _p(mask), _p(counts), stream())
+        else:
+            call("stf_predict_mask", _p(x), _p(target), B, K, H * W, RULES[rule], channel, threshold,
+                 _ignore(ignore_index), _p(mask), _p(counts), stream())
     return mask if target is None else (mask, counts)
 
 
@@ -159,12 +179,10 @@ def boundary_metrics(mask, target, ignore_index=None, spacing=1.0):
     directions, times ``spacing``: HD their maximum, HD95 numpy's linear 95th percentile of all of
     them, ASSD half the sum of the two directions' means (MedPy's hd / hd95 / assd).  An image
     with an empty mask or target gets NaN in all three."""
-    if tuple(mask.shape) != tuple(target.shape):
-        raise ValueError(f"target {tuple(target.shape)} does not match the mask's {tuple(mask.shape)}")
+    _check_target_shape(target, mask.shape)
     B, H, W = _check_bhw(mask, "mask")
     spacing = _check_spacing(spacing)
-    if target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
-        raise ValueError(f"target must be an integer tensor, not {target.dtype}")
+    _check_target_dtype(target)
     mask = _as_u8(mask.detach(), "mask")
     _device_only(mask, "boundary_metrics")
     _device_only(target, "boundary_metrics")
@@ -175,8 +193,8 @@ def boundary_metrics(mask, target, ignore_index=None, spacing=1.0):
         target = target.detach().to(device=dev, dtype=torch.int64).contiguous()
         scratch = _boundary_scratch(B, H, W, dev)
         with torch.cuda.device(dev):
-            call("stf_boundary_metrics", _p(mask), _p(target), B, H, W, -1 if ignore_index is None else ignore_index,
-                 _p(out), _p(counts), _p(scratch), stream())
+            call("stf_boundary_metrics", _p(mask), _p(target), B, H, W, _ignore(ignore_index), _p(out), _p(counts),
+                 _p(scratch), stream())
         if spacing != 1.0:
             out = out * spacing
     hd, hd95, assd = out.unbind(1)
@@ -227,80 +245,6 @@ def _check_components(connectivity, min_size=0):
     return int(connectivity), int(min_size)
 
 
-def _ccl_scratch(B, H, W, device):
-    nbytes = load().stf_ccl_scratch_bytes(B, H, W)
-    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
-
-
-def connected_components(mask, connectivity=8):
-    """``(labels int32 [B, H, W], num int32 [B])``: the connected components of every image of
-    ``mask`` (``[B, H, W]`` bool or any integer, nonzero = foreground), each image on its own.
-
-    ``connectivity`` 4 joins edge neighbours, 8 edges and corners; pixels outside the image are
-    background.  ``labels`` is 0 on the background and 1..n on the components, numbered per image in
-    raster order of each component's first pixel -- ``scipy.ndimage.label(mask[b],
-    generate_binary_structure(2, 1 or 2))`` -- and ``num[b]`` is n.  Integers only: the same bits
-    from run to run."""
-    B, H, W = _check_bhw(mask, "mask")
-    connectivity, _ = _check_components(connectivity)
-    mask = _as_u8(mask.detach(), "mask")
-    _device_only(mask, "connected_components")
-    labels = torch.empty((B, H, W), dtype=torch.int32, device=mask.device)
-    num = torch.empty((B,), dtype=torch.int32, device=mask.device)
-    if B:
-        scratch = _ccl_scratch(B, H, W, mask.device)
-        with torch.cuda.device(mask.device):
-            call("stf_ccl_label", _p(mask), B, H, W, connectivity, _p(labels), _p(num), _p(scratch), stream())
-    return labels, num
-
-
-def _filter(mask, target, keep_largest, min_size, connectivity, ignore_index):
-    """``stf_ccl_filter`` on a checked uint8 device mask: (filtered mask, counts or None, num int32 [B])."""
-    B, H, W = mask.shape
-    dev = mask.device
-    out = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
-    num = torch.empty((B,), dtype=torch.int32, device=dev)
-    counts = None
-    if target is not None:
-        target = target.detach().to(device=dev, dtype=torch.int64).contiguous()
-        counts = torch.empty((B, 3), dtype=torch.int64, device=dev)
-    if B:
-        scratch = _ccl_scratch(B, H, W, dev)
-        with torch.cuda.device(dev):
-            call("stf_ccl_filter", _p(mask), _p(target), B, H, W, connectivity, int(bool(keep_largest)), min_size,
-                 -1 if ignore_index is None else ignore_index, _p(out), _p(counts), _p(num), _p(scratch), stream())
-    return out, counts, num
-
-
-def filter_components(mask, keep_largest=False, min_size=0, connectivity=8, target=None, ignore_index=None):
-    """``uint8 [B, H, W]``: ``mask`` (``[B, H, W]`` bool or any integer, nonzero = foreground) with the
-    components that do not pass set to 0, each image on its own.
-
-    A component (``connected_components``) passes when its area is at least ``min_size`` pixels and,
-    with ``keep_largest``, it is the largest of its image; of several largest ones the one whose first
-    pixel comes first in raster order is kept (``np.argmax(np.bincount(labels.ravel())[1:])``).
-    ``min_size`` applies first: an image whose largest component is smaller comes out empty.  A pixel
-    that stays keeps its own value, so a mask of class ids keeps them (integer masks wider than
-    uint8 are reduced to 0 / 1 first).  With ``target`` (``[B, H, W]`` integers) returns ``(mask,
-    counts)``, ``counts`` the ``int64 [B, 3]`` (|P&T|, |P|, |T|) of the filtered mask with
-    ``predict_masks``' rules (``ignore_index`` pixels left out of all three, but labelled like any
-    other pixel).  With neither option set the output equals the input; the call still runs the
-    kernels."""
-    B, H, W = _check_bhw(mask, "mask")
-    connectivity, min_size = _check_components(connectivity, min_size)
-    if target is not None:
-        if tuple(target.shape) != (B, H, W):
-            raise ValueError(f"target {tuple(target.shape)} does not match the mask's {(B, H, W)}")
-        if target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
-            raise ValueError(f"target must be an integer tensor, not {target.dtype}")
-    mask = _as_u8(mask.detach(), "mask")
-    _device_only(mask, "filter_components")
-    if target is not None:
-        _device_only(target, "filter_components")
-    out, counts, _ = _filter(mask, target, keep_largest, min_size, connectivity, ignore_index)
-    return out if target is None else (out, counts)
-
-
 CONNECTIVITIES_3D = (6, 18, 26)
 
 
@@ -340,9 +284,97 @@ def _starts(depths, device):
     return host, host.to(device)
 
 
-def _ccl3d_scratch(N, H, W, V, device):
-    nbytes = load().stf_ccl3d_scratch_bytes(N, H, W, V)
-    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+def _ccl_call(op, mask, depths, before, after):
+    """One component entry point on a checked uint8 device mask, with its scratch: ``stf_ccl_<op>``
+    per image (``depths`` None) or ``stf_ccl3d_<op>`` per volume of checked ``depths``.  ``before`` are
+    the arguments ahead of ``N, H, W``, ``after`` those from ``connectivity`` up to the scratch."""
+    N, H, W = mask.shape
+    dev = mask.device
+    with torch.cuda.device(dev):
+        if depths is None:
+            nbytes = load().stf_ccl_scratch_bytes(N, H, W)
+            scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+            call("stf_ccl_" + op, *before, N, H, W, *after, _p(scratch), stream())
+        else:
+            V = len(depths)
+            host, starts = _starts(depths, dev)               # the call reads the host table before it returns
+            nbytes = load().stf_ccl3d_scratch_bytes(N, H, W, V)
+            scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+            call("stf_ccl3d_" + op, *before, N, H, W, _p(starts), host.data_ptr(), V, *after, _p(scratch), stream())
+
+
+def _label(mask, depths, connectivity):
+    """``stf_ccl_label`` / ``stf_ccl3d_label`` on a checked uint8 device mask: (labels, num int32 [B or V])."""
+    N, H, W = mask.shape
+    labels = torch.empty((N, H, W), dtype=torch.int32, device=mask.device)
+    num = torch.empty((N if depths is None else len(depths),), dtype=torch.int32, device=mask.device)
+    if N:
+        _ccl_call("label", mask, depths, (_p(mask),), (connectivity, _p(labels), _p(num)))
+    return labels, num
+
+
+def _filter(mask, target, depths, keep_largest, min_size, connectivity, ignore_index):
+    """``stf_ccl_filter`` / ``stf_ccl3d_filter`` on a checked uint8 device mask: (filtered mask, counts
+    or None, num), counts and num per image (``depths`` None) or per volume."""
+    N, H, W = mask.shape
+    dev = mask.device
+    V = N if depths is None else len(depths)
+    out = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
+    num = torch.empty((V,), dtype=torch.int32, device=dev)
+    counts = None
+    if target is not None:
+        target = target.detach().to(device=dev, dtype=torch.int64).contiguous()
+        counts = torch.empty((V, 3), dtype=torch.int64, device=dev)
+    if N:
+        _ccl_call("filter", mask, depths, (_p(mask), _p(target)),
+                  (connectivity, int(bool(keep_largest)), min_size, _ignore(ignore_index), _p(out), _p(counts), _p(num)))
+    return out, counts, num
+
+
+def _checked_mask(mask, target, what):
+    """The uint8 device mask of a component call; ``target`` (or None) must match it and be on the device."""
+    if target is not None:
+        _check_target(target, mask.shape)
+    mask = _as_u8(mask.detach(), "mask")
+    _device_only(mask, what)
+    if target is not None:
+        _device_only(target, what)
+    return mask
+
+
+def connected_components(mask, connectivity=8):
+    """``(labels int32 [B, H, W], num int32 [B])``: the connected components of every image of
+    ``mask`` (``[B, H, W]`` bool or any integer, nonzero = foreground), each image on its own.
+
+    ``connectivity`` 4 joins edge neighbours, 8 edges and corners; pixels outside the image are
+    background.  ``labels`` is 0 on the background and 1..n on the components, numbered per image in
+    raster order of each component's first pixel -- ``scipy.ndimage.label(mask[b],
+    generate_binary_structure(2, 1 or 2))`` -- and ``num[b]`` is n.  Integers only: the same bits
+    from run to run."""
+    _check_bhw(mask, "mask")
+    connectivity, _ = _check_components(connectivity)
+    return _label(_checked_mask(mask, None, "connected_components"), None, connectivity)
+
+
+def filter_components(mask, keep_largest=False, min_size=0, connectivity=8, target=None, ignore_index=None):
+    """``uint8 [B, H, W]``: ``mask`` (``[B, H, W]`` bool or any integer, nonzero = foreground) with the
+    components that do not pass set to 0, each image on its own.
+
+    A component (``connected_components``) passes when its area is at least ``min_size`` pixels and,
+    with ``keep_largest``, it is the largest of its image; of several largest ones the one whose first
+    pixel comes first in raster order is kept (``np.argmax(np.bincount(labels.ravel())[1:])``).
+    ``min_size`` applies first: an image whose largest component is smaller comes out empty.  A pixel
+    that stays keeps its own value, so a mask of class ids keeps them (integer masks wider than
+    uint8 are reduced to 0 / 1 first).  With ``target`` (``[B, H, W]`` integers) returns ``(mask,
+    counts)``, ``counts`` the ``int64 [B, 3]`` (|P&T|, |P|, |T|) of the filtered mask with
+    ``predict_masks``' rules (``ignore_index`` pixels left out of all three, but labelled like any
+    other pixel).  With neither option set the output equals the input; the call still runs the
+    kernels."""
+    _check_bhw(mask, "mask")
+    connectivity, min_size = _check_components(connectivity, min_size)
+    mask = _checked_mask(mask, target, "filter_components")
+    out, counts, _ = _filter(mask, target, None, keep_largest, min_size, connectivity, ignore_index)
+    return out if target is None else (out, counts)
 
 
 def connected_components_3d(mask, depths=None, connectivity=26):
@@ -359,39 +391,7 @@ def connected_components_3d(mask, depths=None, connectivity=26):
     N, H, W = _check_bhw(mask, "mask")
     connectivity, _ = _check_components_3d(connectivity)
     depths = _check_depths(depths, N)
-    mask = _as_u8(mask.detach(), "mask")
-    _device_only(mask, "connected_components_3d")
-    V = len(depths)
-    labels = torch.empty((N, H, W), dtype=torch.int32, device=mask.device)
-    num = torch.empty((V,), dtype=torch.int32, device=mask.device)
-    if N:
-        host, dev = _starts(depths, mask.device)
-        scratch = _ccl3d_scratch(N, H, W, V, mask.device)
-        with torch.cuda.device(mask.device):
-            call("stf_ccl3d_label", _p(mask), N, H, W, _p(dev), host.data_ptr(), V, connectivity, _p(labels), _p(num),
-                 _p(scratch), stream())
-    return labels, num
-
-
-def _filter3d(mask, target, depths, keep_largest, min_size, connectivity, ignore_index):
-    """``stf_ccl3d_filter`` on a checked uint8 device mask and checked depths: (filtered mask, counts
-    or None, num int32 [V])."""
-    N, H, W = mask.shape
-    dev, V = mask.device, len(depths)
-    out = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
-    num = torch.empty((V,), dtype=torch.int32, device=dev)
-    counts = None
-    if target is not None:
-        target = target.detach().to(device=dev, dtype=torch.int64).contiguous()
-        counts = torch.empty((V, 3), dtype=torch.int64, device=dev)
-    if N:
-        host, starts = _starts(depths, dev)
-        scratch = _ccl3d_scratch(N, H, W, V, dev)
-        with torch.cuda.device(dev):
-            call("stf_ccl3d_filter", _p(mask), _p(target), N, H, W, _p(starts), host.data_ptr(), V, connectivity,
-                 int(bool(keep_largest)), min_size, -1 if ignore_index is None else ignore_index, _p(out), _p(counts),
-                 _p(num), _p(scratch), stream())
-    return out, counts, num
+    return _label(_checked_mask(mask, None, "connected_components_3d"), depths, connectivity)
 
 
 def filter_components_3d(mask, depths=None, keep_largest=False, min_size=0, connectivity=26, target=None,
@@ -408,16 +408,8 @@ def filter_components_3d(mask, depths=None, keep_largest=False, min_size=0, conn
     N, H, W = _check_bhw(mask, "mask")
     connectivity, min_size = _check_components_3d(connectivity, min_size)
     depths = _check_depths(depths, N)
-    if target is not None:
-        if tuple(target.shape) != (N, H, W):
-            raise ValueError(f"target {tuple(target.shape)} does not match the mask's {(N, H, W)}")
-        if target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
-            raise ValueError(f"target must be an integer tensor, not {target.dtype}")
-    mask = _as_u8(mask.detach(), "mask")
-    _device_only(mask, "filter_components_3d")
-    if target is not None:
-        _device_only(target, "filter_components_3d")
-    out, counts, _ = _filter3d(mask, target, depths, keep_largest, min_size, connectivity, ignore_index)
+    mask = _checked_mask(mask, target, "filter_components_3d")
+    out, counts, _ = _filter(mask, target, depths, keep_largest, min_size, connectivity, ignore_index)
     return out if target is None else (out, counts)
 
 
@@ -576,53 +568,66 @@ def tta_probabilities(model, inputs, views=True, rule="argmax", channel=0):
     return acc
 
 
-def _predict(model, data_loader, device, views, keep_probs, rule="argmax", channel=0, threshold=0.5,
-             ignore_index=None, output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5, paint=1,
-             keep_masks=False, boundary=False, spacing=1.0, keep_largest=False, min_size=0, connectivity=8):
-    """The loop of ``predict`` (``views`` None) and ``predict_tta`` (``views`` a checked view set)."""
+def _batches(model, data_loader, device, tta, rule, channel, threshold, ignore_index):
+    """The head of the inference loops.  Checks ``rule`` against ``tta`` (a ``parse_views`` argument, or
+    its result) at once; the generator it returns yields, for every batch of the loader,
+    ``(inputs, targets, mask, counts, outputs)``: the preprocessed inputs and the targets (or None) on
+    the device, ``predict_masks`` of the forward -- of ``tta_probabilities`` with views -- with its
+    counts (None without targets), and what the mask was taken from.  The caller owns eval mode and
+    ``no_grad``."""
     if rule not in RULES:
         raise ValueError(f"unknown rule {rule!r} (one of {sorted(RULES)})")
+    views = parse_views(tta)
     mask_rule, mask_channel = rule, channel
     if views is not None:
         _check_tta_rule(rule)
         if rule == "sigmoid":                       # the mean probability is one plane: mean > threshold
             mask_rule, mask_channel = "threshold", 0
+    from .engine import preprocess_input
+
+    def batches():
+        for batch in data_loader:
+            inputs, targets = batch if isinstance(batch, (tuple, list)) else (batch, None)
+            inputs = preprocess_input(inputs, model).to(device)
+            outputs = model(inputs) if views is None else tta_probabilities(model, inputs, views, rule, channel)
+            counts = None
+            if targets is not None:
+                targets = targets.to(device)
+                mask, counts = predict_masks(outputs, mask_rule, mask_channel, threshold, target=targets,
+                                             ignore_index=ignore_index)
+            else:
+                mask = predict_masks(outputs, mask_rule, mask_channel, threshold)
+            yield inputs, targets, mask, counts, outputs
+
+    return batches()
+
+
+def _predict(model, data_loader, device, views, keep_probs, rule="argmax", channel=0, threshold=0.5,
+             ignore_index=None, output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5, paint=1,
+             keep_masks=False, boundary=False, spacing=1.0, keep_largest=False, min_size=0, connectivity=8):
+    """The loop of ``predict`` (``views`` None) and ``predict_tta`` (``views`` a checked view set)."""
+    batches = _batches(model, data_loader, device, views, rule, channel, threshold, ignore_index)
     color = _check_paint(color, alpha, paint)
     if boundary:
         spacing = _check_spacing(spacing)
     connectivity, min_size = _check_components(connectivity, min_size)
     components = bool(keep_largest) or min_size > 0
-    from .engine import preprocess_input
     if output_dir is not None:
         from PIL import Image
         os.makedirs(output_dir, exist_ok=True)
     model.eval()
     all_counts, all_boundary, all_num, masks, probs, idx = [], [], [], [], [], 0
     with torch.no_grad():
-        for batch in data_loader:
-            inputs, targets = batch if isinstance(batch, (tuple, list)) else (batch, None)
-            inputs = preprocess_input(inputs, model).to(device)
-            if views is None:
-                outputs = model(inputs)
-            else:
-                outputs = tta_probabilities(model, inputs, views, rule, channel)
-                if keep_probs:
-                    probs.append(outputs)
+        for inputs, targets, mask, counts, outputs in batches:
+            if keep_probs:
+                probs.append(outputs)
+            if components:
+                mask, counts, num = _filter(mask, targets, None, keep_largest, min_size, connectivity, ignore_index)
+                all_num.append(num)
             if targets is not None:
-                targets = targets.to(device)
-                mask, counts = predict_masks(outputs, mask_rule, mask_channel, threshold, target=targets,
-                                             ignore_index=ignore_index)
-                if components:
-                    mask, counts, num = _filter(mask, targets, keep_largest, min_size, connectivity, ignore_index)
-                    all_num.append(num)
                 all_counts.append(counts)
                 if boundary:
                     all_boundary.append(boundary_metrics(mask, targets, ignore_index, spacing))
-            else:
-                mask = predict_masks(outputs, mask_rule, mask_channel, threshold)
-                if components:
-                    mask, _, num = _filter(mask, None, keep_largest, min_size, connectivity, None)
-                    all_num.append(num)
             if output_dir is not None:
                 pics = overlay(shown_frame(inputs), mask, color, alpha, paint).cpu().numpy()
                 for j, pic in enumerate(pics):
@@ -698,41 +703,24 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
 
     Not here: boundary metrics in 3-D (HD95 with slice spacing), overlays (``keep_masks=True`` and
     ``overlay`` cover them) and anisotropic connectivity."""
-    if rule not in RULES:
-        raise ValueError(f"unknown rule {rule!r} (one of {sorted(RULES)})")
-    views = parse_views(tta)
-    mask_rule, mask_channel = rule, channel
-    if views is not None:
-        _check_tta_rule(rule)
-        if rule == "sigmoid":                       # the mean probability is one plane: mean > threshold
-            mask_rule, mask_channel = "threshold", 0
+    batches = _batches(model, data_loader, device, tta, rule, channel, threshold, ignore_index)
     connectivity, min_size = _check_components_3d(connectivity, min_size)
     if depths is None:
         raise ValueError("depths must be a sequence of positive integers, one per volume, not None")
     depths = _check_depths(depths)
     components = bool(keep_largest) or min_size > 0
     V, total = len(depths), sum(depths)
-    from .engine import preprocess_input
     model.eval()
     slice_volume = torch.repeat_interleave(torch.arange(V), torch.tensor(depths, dtype=torch.int64)).to(device)
     vol_counts = None                               # options off: int64 [V, 3], summed as the slices come
     held_masks, held_targets, held, done = [], [], 0, 0   # options on: slices of volumes not yet complete
     all_counts, all_num, masks, idx, with_targets = [], [], [], 0, None
     with torch.no_grad():
-        for batch in data_loader:
-            inputs, targets = batch if isinstance(batch, (tuple, list)) else (batch, None)
+        for _, targets, mask, counts, _ in batches:
             if with_targets is None:
                 with_targets = targets is not None
             elif with_targets != (targets is not None):
                 raise ValueError("the loader yields targets for some batches and none for others")
-            inputs = preprocess_input(inputs, model).to(device)
-            outputs = model(inputs) if views is None else tta_probabilities(model, inputs, views, rule, channel)
-            if targets is not None:
-                targets = targets.to(device)
-                mask, counts = predict_masks(outputs, mask_rule, mask_channel, threshold, target=targets,
-                                             ignore_index=ignore_index)
-            else:
-                mask = predict_masks(outputs, mask_rule, mask_channel, threshold)
             B = mask.shape[0]
             if idx + B > total:
                 raise ValueError(f"the loader yields more than the {total} slices of depths")
@@ -757,8 +745,8 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
                     t = None
                     if targets is not None:
                         t = torch.cat(held_targets) if len(held_targets) > 1 else held_targets[0]
-                    out, counts, num = _filter3d(m[:take], None if t is None else t[:take], depths[done:done + k],
-                                                 keep_largest, min_size, connectivity, ignore_index)
+                    out, counts, num = _filter(m[:take], None if t is None else t[:take], depths[done:done + k],
+                                               keep_largest, min_size, connectivity, ignore_index)
                     all_num.append(num)
                     if counts is not None:
                         all_counts.append(counts)

@@ -119,6 +119,29 @@ def stack_filter(stack, depths=None, keep_largest=False, min_size=0, connectivit
     return out, num, counts
 
 
+FLAT = {6: 4, 18: 8, 26: 8}                        # what a connectivity means inside one slice
+
+
+def depth_one_inputs():
+    """[(name, mask uint8 [B, H, W], target int64 [B, H, W] with values 0..2)]: the batches on which a
+    stack of depth-1 volumes must equal a batch of images -- one row chunk, three chunks per row, a
+    width of exactly one chunk and a single voxel, random at 0.5 and at 0.593, and the 2-D fixture
+    cases padded to a common size as one batch."""
+    from _components_ref import fixture_cases as cases2d
+    rng = np.random.default_rng(77)
+    out = []
+    for shape in ((6, 5, 70), (3, 9, 130), (4, 3, 64), (1, 1, 1)):
+        for fill in (0.5, 0.593):
+            out.append(("%dx%dx%d_f%g" % (shape + (fill,)), (rng.random(shape) < fill).astype(np.uint8)))
+    cases = cases2d()
+    H, W = max(c["mask"].shape[0] for c in cases), max(c["mask"].shape[1] for c in cases)
+    batch = np.zeros((len(cases), H, W), np.uint8)
+    for b, c in enumerate(cases):
+        batch[b, :c["mask"].shape[0], :c["mask"].shape[1]] = c["mask"]
+    out.append(("fixture2d", batch))
+    return [(name, m, rng.integers(0, 3, m.shape).astype(np.int64)) for name, m in out]
+
+
 def fixture_cases():
     """The cases of tests/golden/components3d.npz: dicts with name, mask (uint8 [D, H, W]) and, per
     connectivity c in (6, 18, 26), scipy's ``labels{c}`` (int32 [D, H, W]) and ``n{c}``."""

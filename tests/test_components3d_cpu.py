@@ -13,13 +13,12 @@ import pytest
 import torch
 
 import _components_ref as ref2d
-from _components3d_ref import (CONNECTIVITIES, GOLDEN, counts_of, earlier_neighbours, filter_volume, fixture_cases,
-                               label, stack_filter, stack_label)
+from _components3d_ref import (CONNECTIVITIES, FLAT, GOLDEN, counts_of, depth_one_inputs, earlier_neighbours,
+                               filter_volume, fixture_cases, label, stack_filter, stack_label)
 from _dataset_util import make_tree
 
 CASES = fixture_cases()
 EINVAL = 100001
-FLAT = {6: 4, 18: 8, 26: 8}                        # what a connectivity means inside one slice
 
 
 def _generator():
@@ -89,6 +88,21 @@ def test_depth_one_volumes_are_the_2d_labels():
         for k in CONNECTIVITIES:
             labels, n = label(c["mask"][None], k)
             assert n == c[f"n{FLAT[k]}"] and np.array_equal(labels[0], c[f"labels{FLAT[k]}"])
+
+
+@pytest.mark.parametrize("name,m,t", depth_one_inputs(), ids=[i[0] for i in depth_one_inputs()])
+def test_depth_one_volumes_are_images_for_the_restatements(name, m, t):
+    """The premise of the GPU test of the same name, for the oracles alone and on its inputs: a stack of
+    depth-1 volumes under 6 / 18 / 26 is the batch of its slices under 4 / 8 / 8, labels, num, filtered
+    mask and counts."""
+    ones = [1] * m.shape[0]
+    for k in CONNECTIVITIES:
+        labels, num = stack_label(m, ones, k)
+        want, want_num = ref2d.batch_label(m, FLAT[k])
+        assert np.array_equal(labels, want) and np.array_equal(num, want_num)
+        got = stack_filter(m, ones, True, 3, k, t, 2)
+        want = ref2d.batch_filter(m, True, 3, FLAT[k], t, 2)
+        assert all(np.array_equal(a, b) for a, b in zip(got, want))
 
 
 def test_volumes_never_touch():

@@ -1,5 +1,5 @@
-"""Volume-level connected-component post-processing on the GPU (csrc/ccl3d.hip through the C entry
-points and stfunet.predict) against tests/golden/components3d.npz (scipy's labels) and the numpy
+"""Volume-level connected-component post-processing on the GPU (the volume kernels of csrc/ccl.hip through the C
+entry points and stfunet.predict) against tests/golden/components3d.npz (scipy's labels) and the numpy
 restatement of tests/_components3d_ref.py, which tests/test_components3d_cpu.py pins to that fixture.
 
 Everything is an integer, so every comparison is equality, element for element.
@@ -16,7 +16,7 @@ import pytest
 import torch
 
 import _launch_trace as lt
-from _components3d_ref import CONNECTIVITIES, LEVEL, fixture_cases, stack_filter, stack_label
+from _components3d_ref import CONNECTIVITIES, FLAT, LEVEL, depth_one_inputs, fixture_cases, stack_filter, stack_label
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -300,6 +300,24 @@ def test_ragged_volumes_in_one_call_equal_single_volume_calls():
             one = run_filter(m[e - d:e], None, k, True, 2, T[e - d:e], -1, 0xAA)
             assert np.array_equal(out[e - d:e], one[0]) and fnum[v] == one[1][0]
             assert np.array_equal(counts[v], one[2][0])
+
+
+# ---------------------------------------------------------------- one family: depth-1 volumes are images
+@pytest.mark.parametrize("name,m,t", depth_one_inputs(), ids=[i[0] for i in depth_one_inputs()])
+def test_depth_one_volumes_are_images(name, m, t):
+    """The volume instantiation on volumes one slice deep against the image instantiation on the same
+    slices, 6 / 18 / 26 against 4 / 8 / 8: labels, num, filtered mask and counts, bit for bit
+    (tests/test_components3d_cpu.py shows the same identity for the numpy oracles on these inputs)."""
+    from stfunet import connected_components, connected_components_3d, filter_components, filter_components_3d
+    d, target = torch.from_numpy(m).to(DEV), torch.from_numpy(t).to(DEV)
+    ones = [1] * m.shape[0]
+    for k in CONNECTIVITIES:
+        l3, n3 = connected_components_3d(d, ones, k)
+        l2, n2 = connected_components(d, FLAT[k])
+        assert torch.equal(l3, l2) and torch.equal(n3, n2)
+        f3, c3 = filter_components_3d(d, ones, True, 3, k, target=target, ignore_index=2)
+        f2, c2 = filter_components(d, True, 3, FLAT[k], target=target, ignore_index=2)
+        assert torch.equal(f3, f2) and torch.equal(c3, c2)
 
 
 # ---------------------------------------------------------------- the Python surface

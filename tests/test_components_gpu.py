@@ -235,6 +235,43 @@ def test_filter_min_size_and_keep_largest():
     check_filter(batch, 4, keep_largest=True, want_num=False)
 
 
+def _comb():
+    """uint8 [2, 4, 130].  Image 0: a spine over the full width of row 0 (three chunks, both seams)
+    with teeth down rows 1..3, one of them across the first seam, and between the teeth of chunk 0 two
+    components of their own on rows 2..3 that pass under a short tooth each -- so within one chunk of
+    rows 2 and 3 the run segments alternate between the spine's root and another, and row 3 starts
+    with a root that is not the spine's.  Image 1: full."""
+    m = np.zeros((2, 4, 130), np.uint8)
+    m[0, 0, :] = 1
+    for x in (40, 62, 63, 64, 65, 66, 100, 129):
+        m[0, 1:4, x] = 1                                          # long teeth
+    m[0, 1:3, 2] = 1                                              # a tooth that stops above row 3
+    m[0, 1, 10] = m[0, 1, 30] = 1                                 # short teeth
+    m[0, 3, 5:19] = m[0, 2, 5:8] = m[0, 2, 14:17] = 1             # component A, under the tooth at 10
+    m[0, 3, 24:37] = m[0, 2, 24:27] = m[0, 2, 34:37] = 2          # component B, under the tooth at 30
+    m[1] = 1
+    return m
+
+
+def test_exact_areas_of_a_comb_across_chunk_seams():
+    """The areas compress collects, whether every run segment adds on its own (images) or the
+    segments of a chunk's first root are summed in the wave and carried along the row (volumes; the
+    form is a compile-time parameter of the one body): min_size at each component's exact area keeps
+    it, one more removes it."""
+    m = _comb()
+    for k in BOTH:
+        labels, num = batch_label(m, k)
+        assert num.tolist() == [3, 1]
+        areas = np.bincount(labels[0].ravel())[1:].tolist()
+        assert areas == [int(m[0].astype(bool).sum()) - 20 - 19, 20, 19]     # the spine, A, B
+        for a in areas + [4 * 130]:
+            kept = check_filter(m, k, min_size=a)[0]
+            gone = check_filter(m, k, min_size=a + 1)[0]
+            assert kept.astype(bool).sum() - gone.astype(bool).sum() == a
+        out, _, _ = check_filter(m, k, keep_largest=True, min_size=areas[0])
+        assert np.array_equal(out[0] != 0, labels[0] == 1) and out[1].all()
+
+
 def test_filter_keeps_class_ids():
     m = np.zeros((20, 90), np.uint8)
     m[2:10, 5:40] = 1

@@ -29,7 +29,7 @@ connectivity 4 (the most components, no merging).  Per input: ``connected_compon
 scale ``boundary_metrics`` on the same mask; once ``predict_masks`` with counts; and the ``predict``
 loop (UNet, two batches) with the options off and on.  Prints one JSON line.
 
-``--components3d`` measures the volume-level post-processing (csrc/ccl3d.hip) on the same three inputs
+``--components3d`` measures the volume-level post-processing (csrc/ccl.hip, volumes) on the same three inputs
 stacked as ``--batch`` slices (128 for the record) in 1 and in 8 volumes: ``connected_components_3d``
 (stf_ccl3d_label) and ``filter_components_3d`` with a target and ``keep_largest`` (stf_ccl3d_filter) at
 connectivity 26 (6 for the checkerboard), next to the 2-D ``connected_components`` /
