@@ -801,6 +801,44 @@ int stf_ccl3d_filter(const uint8_t* mask, const int64_t* target, int N, int H, i
                      int keep_largest, int64_t min_size, int64_t ignore_index, uint8_t* out, int64_t* counts,
                      int32_t* num, void* scratch, stf_stream_t stream);
 
+/* ---------------------------------------------------------------- boundary metrics of volumes
+ * Per-volume (per-case) HD, HD95 and ASSD with voxel spacing: MedPy's hd / hd95 / assd on a 3-D
+ * array with voxelspacing = (sz, sy, sx) and connectivity 1 (INTEGRATION.md 2.2 states the
+ * definition, DESIGN.md 5.17 the passes), and the squared weighted distance transform underneath.
+ * The stack [N][H][W] is cut into V volumes by the starts table of stf_ccl3d_*, taken twice in the
+ * same way (starts_dev for the kernels, starts_host validated before the call returns); volumes
+ * never see each other, neither for the border (6-neighbour cross, outside the volume background)
+ * nor for distances.  spacing_dev: DEVICE double [V][3], one (sz, sy, sx) per volume, finite and
+ * > 0 (the caller's duty: the table is on the device).  Squared distances are float64 throughout,
+ * ((sx dx)^2 + (sy dy)^2) + (sz dz)^2 with one rounding per operation: exact whenever the products
+ * are (unit spacing; spacings of few significant bits).
+ * Additive to ABI v17.  Limits: 1 <= V <= N, 1 <= H, W <= 4096, N * H * W < 2^31.  STF_EINVAL
+ * (nothing launched) for a NULL required pointer, a size outside the limits, V < 1, a host starts
+ * that is not strictly ascending from 0 to N, a starts that is not 4-byte aligned, or a scratch,
+ * spacing_dev, out, counts, target or d2 that is not 8-byte aligned (mask, sites and where may sit
+ * at any byte).  No entry point allocates, reads back or waits between workgroups; the number of
+ * launches is fixed; floating-point sums are taken in a fixed order that depends only on the
+ * position inside the volume, so the results are the same bits from run to run and for a volume
+ * passed alone or inside a stack.  All outputs are OVERWRITTEN and may arrive uninitialised, the
+ * scratch too.
+ *
+ * Bytes of the scratch either call needs, a multiple of 8 (0 outside the limits). */
+size_t stf_boundary3d_scratch_bytes(int N, int H, int W, int V);
+/* mask uint8 [N][H][W] (nonzero = predicted foreground), target int64 [N][H][W] (> 0 = foreground),
+ * ignore as in stf_predict_mask.  out double [V][3] = {hd, hd95, assd} in the spacing's unit (NaN x3
+ * when either border of the volume is empty), counts int64 [V][2] = {|dP|, |dT|}. */
+int stf_boundary3d_metrics(const uint8_t* mask, const int64_t* target, int N, int H, int W,
+                           const int32_t* starts_dev, const int32_t* starts_host, int V,
+                           const double* spacing_dev, int64_t ignore, double* out, int64_t* counts,
+                           void* scratch, stf_stream_t stream);
+/* d2 double [N][H][W]: the squared weighted distance of every voxel to the nearest nonzero voxel of
+ * sites (uint8 [N][H][W]) of the same volume; +inf throughout a volume without sites.  where (uint8,
+ * may be NULL): compute only where it is nonzero, write -1 elsewhere.  The same row, plane and depth
+ * code as above.  The cost per computed voxel grows with the distance found. */
+int stf_edt3d_sq(const uint8_t* sites, const uint8_t* where, int N, int H, int W, const int32_t* starts_dev,
+                 const int32_t* starts_host, int V, const double* spacing_dev, double* d2, void* scratch,
+                 stf_stream_t stream);
+
 /* ---------------------------------------------------------------- PK maps (extended Tofts)
  * pk_fitting.py ToftsModelFitter, all fp32.  The host builds
  * the reference's constant tables exactly as the reference does (pk_fitting.py:

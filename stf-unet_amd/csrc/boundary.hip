@@ -24,7 +24,34 @@
 // Run-to-run identical bits: the counts and histograms are integer atomics (order-free); the fp64
 // sums are taken per lane in index order, then by xor shuffle, then over the waves in order.
 // Integer and fp64 only: the same code in both storage builds.
+//
+// Volumes (stf_boundary3d_metrics, stf_edt3d_sq): the [N][H][W] stack is cut into V
+// volumes by the starts table of ccl.hip (volumes.h), each with its own spacing (sz, sy, sx), and the
+// squared distance becomes float64: ((sx dx)^2 + (sy dy)^2) + (sz dz)^2, every product and sum
+// rounded once (no contraction).  One code path: unit spacing is exact because every term is an
+// integer below 2^53.
+//   row      the same kernel, instantiated with VOL: the border word also takes the words of the
+//            same row in slices z - 1 and z + 1 of the same volume (6-neighbour cross, outside the
+//            volume background), the counts are per volume, and every row with a border voxel marks
+//            its slice in has[z][side] and widens its volume's (y, x) bounding box box[v][side]
+//            (integer atomicMax on zeroed words).
+//   plane    the column scan in float64, min over y' of (sx g)^2 + (sy dy)^2, stored as the winning
+//            (g, dy) pair in one uint32 (the depth pass recomputes the same double from it: 4 bytes
+//            per voxel and side, not 8).  Only in slices that have a site and, for the metrics,
+//            inside the querying border's bounding box: the depth pass reads nothing else.
+//   depth    only at the querying border voxels (or `where`): min over the slices z' of the volume
+//            that have a site of plane(z') + (sz dz)^2, outward from z until (sz dz)^2 >= best.
+//            The metrics' depth kernel works in units of 2048 consecutive voxels of one slice and
+//            side: it sums sqrt(d2) per thread in index order, per wave by xor shuffle and over the
+//            waves in order into one partial per unit, takes the unit's maximum, and appends d2
+//            to its volume's compact list through an integer cursor.
+//   fold     one workgroup per volume: the partials summed in unit order (units are placed by
+//            in-volume position, so a volume gives the same bits alone and in a stack), and the two
+//            order statistics by an 11-bit radix select over the compact list's uint64 bit
+//            patterns (non-negative doubles order as integers).  The list's order varies from run
+//            to run; only integer histograms and minima read it.
 #include "common.h"
+#include "volumes.h"
 #include "../../include/stfunet.h"
 
 // HD95's interpolation and the ASSD mean as written in the definition, one rounding per operation
@@ -51,11 +78,12 @@ STF_DEV u64 shfl_down1(u64 v, int lane) {
 }
 
 // M & ~erode(M) with the 4-neighbour cross, outside the image background.  Lane c holds word c of
-// the row above, the row itself and the row below; bits at x >= W are zero.
-STF_DEV u64 border_word(u64 up, u64 mid, u64 down, int lane) {
+// the row above, the row itself and the row below; bits at x >= W are zero.  Volumes: zz = the
+// same row's word in slice z - 1 AND in slice z + 1 (the 6-neighbour cross); images: all ones.
+STF_DEV u64 border_word(u64 up, u64 mid, u64 down, u64 zz, int lane) {
   const u64 left = (mid << 1) | (shfl_up1(mid, lane) >> 63);        // bit i = pixel x - 1
   const u64 right = (mid >> 1) | (shfl_down1(mid, lane) << 63);     // bit i = pixel x + 1
-  return mid & ~(up & down & left & right);
+  return mid & ~(up & down & left & right & zz);
 }
 
 // g of one row from its border words (lane c holds word c): uint16 distance to the nearest set bit
@@ -94,47 +122,116 @@ STF_DEV int wave_sum_i(int v) {
   return v;
 }
 
+STF_DEV int wave_max_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+
+// The slices [z0, z1) of the volume v that slice z belongs to.  Images: {z, z, z + 1}.  Bounds do
+// not rest on the device table: z0 <= z < z1 <= N whatever it holds, and 0 <= v < V.
+struct Span {
+  int v, z0, z1;
+};
+template <bool VOL>
+STF_DEV Span span_of(const int* __restrict__ starts, int V, int N, int z) {
+  const stf::Vol vol = stf::volume_of<VOL>(starts, V, z);
+  if constexpr (!VOL) {
+    return {z, z, z + 1};
+  } else {
+    int z1 = starts[vol.v + 1];
+    if (z1 <= z || z1 > N) z1 = z + 1;
+    return {vol.v, vol.z0, z1};
+  }
+}
+
+// The prediction's and the target's words of the row that starts at element `base` (lane c keeps word c)
+STF_DEV void mask_words(const uint8_t* __restrict__ mask, const int64_t* __restrict__ target, long base, int W,
+                        long ignore, int lane, u64& p, u64& t) {
+  const int nw = (W + 63) >> 6;
+  for (int c = 0; c < nw; ++c) {
+    const int x = c * 64 + lane;
+    bool fp = false, ft = false;
+    if (x < W) {
+      const long tv = target[base + x];
+      const bool keep = !(ignore >= 0 && tv == ignore);
+      fp = keep && mask[base + x] != 0;
+      ft = keep && tv > 0;
+    }
+    const u64 wp = __ballot(fp), wt = __ballot(ft);
+    if (lane == c) { p = wp; t = wt; }
+  }
+}
+
+// Volumes: a row with border voxels marks its slice and widens its volume's bounding box.  box
+// [4] = max of (y + 1, MAXDIM - y, x + 1, MAXDIM - x) over the border voxels, 0 = none yet.
+STF_DEV void mark_row(u64 bw, int lane, int y, int* __restrict__ has, int* __restrict__ box) {
+  const int xhi = wave_max_i(bw ? lane * 64 + 64 - __builtin_clzll(bw) : 0);
+  const int xlo = wave_max_i(bw ? MAXDIM - (lane * 64 + __builtin_ctzll(bw)) : 0);
+  if (lane == 0) {
+    *has = 1;
+    atomicMax(box, y + 1);
+    atomicMax(box + 1, MAXDIM - y);
+    atomicMax(box + 2, xhi);
+    atomicMax(box + 3, xlo);
+  }
+}
+STF_DEV bool in_box(const int* __restrict__ box, int y, int x) {
+  return y + 1 <= box[0] && MAXDIM - y <= box[1] && x + 1 <= box[2] && MAXDIM - x <= box[3];
+}
+
 // Row pass of the metrics.  rows = B * H; gP / gT [B][H][W]; counts [B][2] += (|dP|, |dT|) of the row.
+// VOL: B = N slices, counts [V][2], has int [N][2], box int [V][2][4], all zeroed by the caller.
+template <bool VOL>
 __global__ __launch_bounds__(BT) void boundary_rows_kernel(const uint8_t* __restrict__ mask,
                                                            const int64_t* __restrict__ target, long rows, int H,
-                                                           int W, long ignore, uint16_t* __restrict__ gP,
-                                                           uint16_t* __restrict__ gT, u64* __restrict__ counts) {
+                                                           int W, long ignore, const int* __restrict__ starts, int N,
+                                                           int V, uint16_t* __restrict__ gP,
+                                                           uint16_t* __restrict__ gT, u64* __restrict__ counts,
+                                                           int* __restrict__ has, int* __restrict__ box) {
   const int lane = threadIdx.x & 63;
   const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
   if (r >= rows) return;                                            // whole waves leave: no barrier below
   const long b = r / H;
   const int y = (int)(r - b * H);
-  const int nw = (W + 63) >> 6;
+  const Span sp = span_of<VOL>(starts, V, N, (int)b);               // wave-uniform
   u64 p[3] = {0, 0, 0}, t[3] = {0, 0, 0};                           // words of rows y - 1, y, y + 1
 #pragma unroll
   for (int k = 0; k < 3; ++k) {
     const int yy = y + k - 1;
     if (yy < 0 || yy >= H) continue;                                // wave-uniform
-    const long base = (r + (k - 1)) * (long)W;
-    for (int c = 0; c < nw; ++c) {
-      const int x = c * 64 + lane;
-      bool fp = false, ft = false;
-      if (x < W) {
-        const long tv = target[base + x];
-        const bool keep = !(ignore >= 0 && tv == ignore);
-        fp = keep && mask[base + x] != 0;
-        ft = keep && tv > 0;
-      }
-      const u64 wp = __ballot(fp), wt = __ballot(ft);
-      if (lane == c) { p[k] = wp; t[k] = wt; }
-    }
+    mask_words(mask, target, (r + (k - 1)) * (long)W, W, ignore, lane, p[k], t[k]);
   }
-  const u64 bp = border_word(p[0], p[1], p[2], lane), bt = border_word(t[0], t[1], t[2], lane);
+  u64 zp = ~0ull, zt = ~0ull;
+  if constexpr (VOL) {
+    u64 pa = 0, ta = 0, pb = 0, tb = 0;                             // the row in slices z - 1 and z + 1
+    if ((int)b > sp.z0) mask_words(mask, target, (r - H) * (long)W, W, ignore, lane, pa, ta);
+    if ((int)b + 1 < sp.z1) mask_words(mask, target, (r + H) * (long)W, W, ignore, lane, pb, tb);
+    zp = pa & pb;
+    zt = ta & tb;
+  }
+  const u64 bp = border_word(p[0], p[1], p[2], zp, lane), bt = border_word(t[0], t[1], t[2], zt, lane);
   store_row_g(bp, lane, W, gP + r * (long)W);
   store_row_g(bt, lane, W, gT + r * (long)W);
   const int np = wave_sum_i(__builtin_popcountll(bp)), nt = wave_sum_i(__builtin_popcountll(bt));
-  if (lane == 0 && np) atomicAdd(&counts[b * 2], (u64)np);
-  if (lane == 1 && nt) atomicAdd(&counts[b * 2 + 1], (u64)nt);
+  if (lane == 0 && np) atomicAdd(&counts[(long)sp.v * 2], (u64)np);
+  if (lane == 1 && nt) atomicAdd(&counts[(long)sp.v * 2 + 1], (u64)nt);
+  if constexpr (VOL) {
+    if (np) mark_row(bp, lane, y, has + b * 2, box + (long)sp.v * 8);             // wave-uniform
+    if (nt) mark_row(bt, lane, y, has + b * 2 + 1, box + (long)sp.v * 8 + 4);
+  }
 }
 
 // Row pass of the plain transform: the sites are the border.  nsites [B] += sites of the row.
+// VOL: nsites u64 [V][2] (the first of each pair) and has int [N][2] (likewise), zeroed by the caller.
+template <bool VOL>
 __global__ __launch_bounds__(BT) void edt_rows_kernel(const uint8_t* __restrict__ sites, long rows, int H, int W,
-                                                      uint16_t* __restrict__ g, u64* __restrict__ nsites) {
+                                                      const int* __restrict__ starts, int N, int V,
+                                                      uint16_t* __restrict__ g, u64* __restrict__ nsites,
+                                                      int* __restrict__ has) {
   const int lane = threadIdx.x & 63;
   const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
   if (r >= rows) return;
@@ -147,7 +244,15 @@ __global__ __launch_bounds__(BT) void edt_rows_kernel(const uint8_t* __restrict_
   }
   store_row_g(bw, lane, W, g + r * (long)W);
   const int n = wave_sum_i(__builtin_popcountll(bw));
-  if (lane == 0 && n) atomicAdd(&nsites[r / H], (u64)n);
+  if constexpr (VOL) {
+    const Span sp = span_of<true>(starts, V, N, (int)(r / H));
+    if (lane == 0 && n) {
+      atomicAdd(&nsites[(long)sp.v * 2], (u64)n);
+      has[(r / H) * 2] = 1;
+    }
+  } else {
+    if (lane == 0 && n) atomicAdd(&nsites[r / H], (u64)n);
+  }
 }
 
 // min over y' of g[y'][x]^2 + (y - y')^2 for one column (col = &g[0][x] of the image), outward from y
@@ -203,6 +308,201 @@ __global__ __launch_bounds__(BT) void edt_cols_kernel(const uint16_t* __restrict
   d2[i] = v;
 }
 
+// ---- volumes: the plane and depth passes in float64
+constexpr unsigned PL_NONE = 0xFFFFFFFFu;   // no site in this column of the slice
+constexpr int CH = 2048;                    // voxels of one unit of the metrics' depth pass
+constexpr int MAX_UNIT_BLOCKS = 1 << 16;    // its grid; more units than this are strided over
+
+// The plane value of a packed (g << 16 | dy) pair: (sx g)^2 + (sy dy)^2, each operation rounded once
+STF_DEV double plane_value(unsigned p, double sy, double sx) {
+  const double a = sx * (double)(p >> 16), b = sy * (double)(p & 0xFFFFu);
+  return a * a + b * b;
+}
+
+// min over y' of (sx g[y'][x])^2 + (sy (y - y'))^2 for one column of one slice, outward from y; the
+// winning pair packed, PL_NONE when the column has no site
+STF_DEV unsigned plane_min(const uint16_t* __restrict__ col, int y, int H, int W, double sy, double sx) {
+  double best = __builtin_inf();
+  unsigned pack = PL_NONE;
+  unsigned v = col[(long)y * W];
+  if (v != G_NONE) { pack = v << 16; best = plane_value(pack, sy, sx); }
+  for (int d = 1; d < H; ++d) {
+    const double e = sy * (double)d, ee = e * e;
+    if (ee >= best) break;
+    const int ya = y - d, yb = y + d;
+    if (ya < 0 && yb >= H) break;
+    if (ya >= 0) {
+      v = col[(long)ya * W];
+      if (v != G_NONE) {
+        const unsigned q = (v << 16) | (unsigned)d;
+        const double s = plane_value(q, sy, sx);
+        if (s < best) { best = s; pack = q; }
+      }
+    }
+    if (yb < H) {
+      v = col[(long)yb * W];
+      if (v != G_NONE) {
+        const unsigned q = (v << 16) | (unsigned)d;
+        const double s = plane_value(q, sy, sx);
+        if (s < best) { best = s; pack = q; }
+      }
+    }
+  }
+  return pack;
+}
+
+// min over the slices z' in [z0, z1) that have a site (has[z' * 2] != 0) of plane(z') + (sz (z - z'))^2
+// at in-slice index j, outward from z; +inf when no such slice has a site in this column
+STF_DEV double depth_min(const unsigned* __restrict__ plane, const int* __restrict__ has, int z, int z0, int z1,
+                         long j, long HW, double sz, double sy, double sx) {
+  double best = __builtin_inf();
+  if (has[(long)z * 2]) {
+    const unsigned p = plane[(long)z * HW + j];
+    if (p != PL_NONE) best = plane_value(p, sy, sx);
+  }
+  for (int d = 1;; ++d) {
+    const double e = sz * (double)d, ee = e * e;
+    if (ee >= best) break;
+    const int za = z - d, zb = z + d;
+    if (za < z0 && zb >= z1) break;
+    if (za >= z0 && has[(long)za * 2]) {
+      const unsigned p = plane[(long)za * HW + j];
+      if (p != PL_NONE) { const double s = plane_value(p, sy, sx) + ee; best = s < best ? s : best; }
+    }
+    if (zb < z1 && has[(long)zb * 2]) {
+      const unsigned p = plane[(long)zb * HW + j];
+      if (p != PL_NONE) { const double s = plane_value(p, sy, sx) + ee; best = s < best ? s : best; }
+    }
+  }
+  return best;
+}
+
+// Plane pass of the metrics: plT where the depth pass of a dP voxel may read it (slices with a dT
+// voxel, inside dP's bounding box), plP the converse; nothing is written elsewhere or in a volume
+// one of whose borders is empty.
+__global__ __launch_bounds__(BT) void boundary3d_plane_kernel(const uint16_t* __restrict__ gP,
+                                                              const uint16_t* __restrict__ gT,
+                                                              const u64* __restrict__ counts,
+                                                              const int* __restrict__ has,
+                                                              const int* __restrict__ box,
+                                                              const int* __restrict__ starts, int N, int V,
+                                                              const double* __restrict__ spacing, long n, int H,
+                                                              int W, unsigned* __restrict__ plP,
+                                                              unsigned* __restrict__ plT) {
+  const long i = (long)blockIdx.x * BT + threadIdx.x;
+  if (i >= n) return;
+  const long HW = (long)H * W, z = i / HW, rem = i - z * HW;
+  const int y = (int)(rem / W), x = (int)(rem - (long)y * W);
+  const bool hp = has[z * 2] != 0, ht = has[z * 2 + 1] != 0;
+  if (!hp && !ht) return;
+  const Span sp = span_of<true>(starts, V, N, (int)z);
+  if (counts[(long)sp.v * 2] == 0 || counts[(long)sp.v * 2 + 1] == 0) return;
+  const double sy = spacing[(long)sp.v * 3 + 1], sx = spacing[(long)sp.v * 3 + 2];
+  const int* bx = box + (long)sp.v * 8;
+  if (ht && in_box(bx, y, x)) plT[i] = plane_min(gT + z * HW + x, y, H, W, sy, sx);
+  if (hp && in_box(bx + 4, y, x)) plP[i] = plane_min(gP + z * HW + x, y, H, W, sy, sx);
+}
+
+// Plane pass of the plain transform: every voxel of every slice that has a site
+__global__ __launch_bounds__(BT) void edt3d_plane_kernel(const uint16_t* __restrict__ g,
+                                                         const int* __restrict__ has,
+                                                         const int* __restrict__ starts, int N, int V,
+                                                         const double* __restrict__ spacing, long n, int H, int W,
+                                                         unsigned* __restrict__ pl) {
+  const long i = (long)blockIdx.x * BT + threadIdx.x;
+  if (i >= n) return;
+  const long HW = (long)H * W, z = i / HW, rem = i - z * HW;
+  if (!has[z * 2]) return;
+  const int y = (int)(rem / W), x = (int)(rem - (long)y * W);
+  const Span sp = span_of<true>(starts, V, N, (int)z);
+  pl[i] = plane_min(g + z * HW + x, y, H, W, spacing[(long)sp.v * 3 + 1], spacing[(long)sp.v * 3 + 2]);
+}
+
+// Depth pass of the plain transform: d2 = +inf throughout a volume without sites, -1 outside `where`
+__global__ __launch_bounds__(BT) void edt3d_depth_kernel(const unsigned* __restrict__ pl,
+                                                         const uint8_t* __restrict__ where,
+                                                         const u64* __restrict__ nsites,
+                                                         const int* __restrict__ has,
+                                                         const int* __restrict__ starts, int N, int V,
+                                                         const double* __restrict__ spacing, long n, long HW,
+                                                         double* __restrict__ d2) {
+  const long i = (long)blockIdx.x * BT + threadIdx.x;
+  if (i >= n) return;
+  double v = -1.0;
+  if (!where || where[i] != 0) {
+    const long z = i / HW;
+    const Span sp = span_of<true>(starts, V, N, (int)z);
+    const double* s = spacing + (long)sp.v * 3;
+    v = __builtin_inf();
+    if (nsites[(long)sp.v * 2] != 0) v = depth_min(pl, has, (int)z, sp.z0, sp.z1, i - z * HW, HW, s[0], s[1], s[2]);
+  }
+  d2[i] = v;
+}
+
+// Depth pass of the metrics.  Unit u = (slice z, chunk c of CH voxels, side): side 0 takes the dP
+// voxels of the chunk against dT, side 1 the converse.  psum[u] = the unit's sum of sqrt(d2) in a
+// fixed order, pmax[u] = its largest d2 (both 0 for a unit without such voxels or in an undefined
+// volume: every unit writes); each d2 also goes to the volume's list comp[2 * z0 * HW + slot], slot
+// from cursor[v] (zeroed by the caller).  The list holds at most |dP| + |dT| <= 2 * D * HW entries.
+__global__ __launch_bounds__(BT) void boundary3d_depth_kernel(const uint16_t* __restrict__ gP,
+                                                              const uint16_t* __restrict__ gT,
+                                                              const unsigned* __restrict__ plP,
+                                                              const unsigned* __restrict__ plT,
+                                                              const u64* __restrict__ counts,
+                                                              const int* __restrict__ has,
+                                                              const int* __restrict__ starts, int N, int V,
+                                                              const double* __restrict__ spacing, long units,
+                                                              int nch, long HW, double* __restrict__ psum,
+                                                              double* __restrict__ pmax,
+                                                              unsigned* __restrict__ cursor, u64* __restrict__ comp) {
+  __shared__ double wsum[BT / 64], wmax[BT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  for (long u = blockIdx.x; u < units; u += gridDim.x) {            // block-uniform
+    const int side = (int)(u & 1);
+    const long zc = u >> 1, z = zc / nch;
+    const int c = (int)(zc - z * nch);
+    const Span sp = span_of<true>(starts, V, N, (int)z);
+    const bool defined = counts[(long)sp.v * 2] != 0 && counts[(long)sp.v * 2 + 1] != 0;
+    double s = 0.0, mx = 0.0;
+    if (defined && has[z * 2 + side]) {                             // block-uniform
+      const uint16_t* gq = (side ? gT : gP) + z * HW;               // the querying border: g == 0
+      const unsigned* pl = side ? plP : plT;                        // the other side's planes
+      const int* hs = has + (side ? 0 : 1);
+      const double* spc = spacing + (long)sp.v * 3;
+      const double sz = spc[0], sy = spc[1], sx = spc[2];
+      const long cap = 2 * (long)(sp.z1 - sp.z0) * HW;
+      u64* list = comp + 2 * (long)sp.z0 * HW;
+      for (int k = 0; k < CH / BT; ++k) {
+        const long j = (long)c * CH + k * BT + tid;
+        if (j >= HW || gq[j] != 0) continue;
+        const double v = depth_min(pl, hs, (int)z, sp.z0, sp.z1, j, HW, sz, sy, sx);
+        s += sqrt(v);
+        mx = v > mx ? v : mx;
+        const unsigned slot = atomicAdd(&cursor[sp.v], 1u);
+        if ((long)slot < cap) list[slot] = (u64)__double_as_longlong(v);
+      }
+    }
+    s = wave_sum_d(s);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const double m = __shfl_xor(mx, o, 64);
+      mx = m > mx ? m : mx;
+    }
+    if (lane == 0) { wsum[wv] = s; wmax[wv] = mx; }
+    __syncthreads();
+    if (tid == 0) {
+      double a = 0.0, m = 0.0;
+      for (int w = 0; w < BT / 64; ++w) {
+        a += wsum[w];
+        m = wmax[w] > m ? wmax[w] : m;
+      }
+      psum[u] = a;
+      pmax[u] = m;
+    }
+    __syncthreads();                                                // wsum / wmax are free again
+  }
+}
+
 // ---- per-image reduction
 struct Fold {
   unsigned hist[512];
@@ -215,7 +515,8 @@ struct Fold {
 
 // Thread 0 picks the bin holding rank k among the values counted in hist (bins = 1 << bits wide at
 // `shift`), given `below` values under the prefix's range.
-STF_DEV void pick_bin(Fold& f, long k, int bins, int shift) {
+template <typename F>
+STF_DEV void pick_bin(F& f, long k, int bins, int shift) {
   if (threadIdx.x == 0) {
     long c = f.below;
     int j = 0;
@@ -225,7 +526,7 @@ STF_DEV void pick_bin(Fold& f, long k, int bins, int shift) {
     }
     f.below = c;
     f.at_or_below = c + (long)f.hist[j];
-    f.prefix |= j << shift;
+    f.prefix |= (decltype(f.prefix))j << shift;
   }
 }
 
@@ -325,6 +626,107 @@ __global__ __launch_bounds__(RT) void boundary_fold_kernel(const int* __restrict
   o[2] = 0.5 * (sp / (double)cP + st / (double)cT);
 }
 
+// ---- per-volume reduction
+struct FoldV {
+  unsigned hist[2048];
+  double dsum[2][RT / 64];
+  double dmax[RT / 64];
+  long below;
+  u64 prefix;          // the selected d2's bit pattern, high digits first
+  long at_or_below;
+};
+
+// One workgroup per volume: the units' partials in unit order (per thread in index order, xor
+// shuffle, waves in order), then the same select as boundary_fold_kernel on the compact list's
+// uint64 keys, in digits of 11 bits (the last one 9).
+__global__ __launch_bounds__(RT) void boundary3d_fold_kernel(const double* __restrict__ psum,
+                                                             const double* __restrict__ pmax,
+                                                             const u64* __restrict__ comp,
+                                                             const u64* __restrict__ counts,
+                                                             const int* __restrict__ starts, int N, int nch,
+                                                             long HW, double* __restrict__ out) {
+  __shared__ FoldV f;
+  const long b = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const long cP = (long)counts[b * 2], cT = (long)counts[b * 2 + 1];
+  double* o = out + b * 3;
+  if (cP == 0 || cT == 0) {                                         // block-uniform
+    if (tid < 3) o[tid] = __builtin_nan("");
+    return;
+  }
+  int z0 = starts[b], z1 = starts[b + 1];                           // inside [0, N] whatever the table holds
+  z0 = z0 < 0 ? 0 : (z0 >= N ? N - 1 : z0);
+  z1 = z1 <= z0 ? z0 + 1 : (z1 > N ? N : z1);
+  const u64* list = comp + 2 * (long)z0 * HW;
+  const long cap = 2 * (long)(z1 - z0) * HW;
+  const long n = cP + cT < cap ? cP + cT : cap;
+  const double r = 0.95 * (double)(n - 1);
+  const long lo = (long)floor(r);
+  const long hi = lo + 1 < n - 1 ? lo + 1 : n - 1;
+
+  double mx = 0.0, s[2] = {0.0, 0.0};
+  for (long u = (long)z0 * nch * 2 + tid; u < (long)z1 * nch * 2; u += RT) {    // RT is even: a thread keeps its side
+    s[u & 1] += psum[u];
+    mx = pmax[u] > mx ? pmax[u] : mx;
+  }
+#pragma unroll
+  for (int ofs = 32; ofs > 0; ofs >>= 1) {
+    const double m = __shfl_xor(mx, ofs, 64);
+    mx = m > mx ? m : mx;
+  }
+  s[0] = wave_sum_d(s[0]);
+  s[1] = wave_sum_d(s[1]);
+  if (lane == 0) { f.dmax[wv] = mx; f.dsum[0][wv] = s[0]; f.dsum[1][wv] = s[1]; }
+  if (tid == 0) { f.below = 0; f.prefix = 0; }
+
+  int top = 64;
+  for (int digit = 0; digit < 6; ++digit) {
+    const int bits = digit < 5 ? 11 : 9, shift = top - bits;
+    __syncthreads();                                                // prefix is final, hist is free
+    const u64 want = top < 64 ? f.prefix >> top : 0;
+    for (int j = tid; j < 2048; j += RT) f.hist[j] = 0;
+    __syncthreads();
+    for (long i = tid; i < n; i += RT) {
+      const u64 k = list[i];
+      if (top == 64 || (k >> top) == want) atomicAdd(&f.hist[(k >> shift) & ((1u << bits) - 1)], 1u);
+    }
+    __syncthreads();
+    pick_bin(f, lo, 1 << bits, shift);
+    top = shift;
+  }
+  __syncthreads();
+  const u64 slo = f.prefix;
+  u64 shi = slo;
+  if (hi >= f.at_or_below) {                                        // block-uniform: the next larger value
+    u64 m = ~0ull;
+    for (long i = tid; i < n; i += RT) {
+      const u64 k = list[i];
+      if (k > slo && k < m) m = k;
+    }
+#pragma unroll
+    for (int ofs = 32; ofs > 0; ofs >>= 1) {
+      const u64 t = __shfl_xor(m, ofs, 64);
+      m = t < m ? t : m;
+    }
+    u64* wmin = (u64*)f.hist;                                       // hist is free again
+    if (lane == 0) wmin[wv] = m;
+    __syncthreads();
+    shi = wmin[0];
+    for (int w = 1; w < RT / 64; ++w) shi = wmin[w] < shi ? wmin[w] : shi;
+  }
+  if (tid != 0) return;
+  double m = 0.0, sp = 0.0, st = 0.0;
+  for (int w = 0; w < RT / 64; ++w) {
+    m = f.dmax[w] > m ? f.dmax[w] : m;
+    sp += f.dsum[0][w];
+    st += f.dsum[1][w];
+  }
+  const double a = sqrt(__longlong_as_double((long long)slo)), c = sqrt(__longlong_as_double((long long)shi));
+  o[0] = sqrt(m);
+  o[1] = a + (c - a) * (r - (double)lo);
+  o[2] = 0.5 * (sp / (double)cP + st / (double)cT);
+}
+
 inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // B, H, W inside the limits and B * H * W < 2^31
@@ -372,8 +774,9 @@ extern "C" int stf_boundary_metrics(const uint8_t* mask, const int64_t* target, 
   u64* cnt = (u64*)counts;
   hipError_t e = stf::memset_async(counts, 0, (size_t)B * 2 * sizeof(int64_t), s);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(boundary_rows_kernel, dim3((unsigned)((rows + BT / 64 - 1) / (BT / 64))), dim3(BT), 0, s, mask,
-                     target, rows, H, W, (long)ignore, gP, gT, cnt);
+  hipLaunchKernelGGL(boundary_rows_kernel<false>, dim3((unsigned)((rows + BT / 64 - 1) / (BT / 64))), dim3(BT), 0, s,
+                     mask, target, rows, H, W, (long)ignore, (const int*)nullptr, B, B, gP, gT, cnt, (int*)nullptr,
+                     (int*)nullptr);
   STF_CHECK_LAUNCH();
   hipLaunchKernelGGL(boundary_cols_kernel, dim3((unsigned)((n + BT - 1) / BT)), dim3(BT), 0, s,
                      (const uint16_t*)gP, (const uint16_t*)gT, (const u64*)cnt, n, H, W, d2P, d2T);
@@ -393,11 +796,135 @@ extern "C" int stf_edt_sq(const uint8_t* sites, const uint8_t* where, int B, int
   const Scratch sc = carve(scratch, B, n);
   hipError_t e = stf::memset_async(sc.counts, 0, (size_t)B * sizeof(u64), s);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(edt_rows_kernel, dim3((unsigned)((rows + BT / 64 - 1) / (BT / 64))), dim3(BT), 0, s, sites, rows,
-                     H, W, sc.g, sc.counts);
+  hipLaunchKernelGGL(edt_rows_kernel<false>, dim3((unsigned)((rows + BT / 64 - 1) / (BT / 64))), dim3(BT), 0, s, sites,
+                     rows, H, W, (const int*)nullptr, B, B, sc.g, sc.counts, (int*)nullptr);
   STF_CHECK_LAUNCH();
   hipLaunchKernelGGL(edt_cols_kernel, dim3((unsigned)((n + BT - 1) / BT)), dim3(BT), 0, s, (const uint16_t*)sc.g,
                      where, (const u64*)sc.counts, n, H, W, d2);
+  STF_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---------------------------------------------------------------- volumes
+namespace {
+
+// scratch: [site counts u64 [V][2], 256-B rounded][unit partials double [2][units], 256-B rounded]
+//          [compact list u64 [2 n]][planes uint32 [2][n]]
+//          [has int [N][2], box int [V][2][4], cursor uint32 [V]: zeroed by one memset, 256-B rounded]
+//          [g uint16 [2][n]], rounded up to 8 bytes
+struct Scratch3 {
+  u64* counts;
+  double* part;
+  u64* comp;
+  unsigned* plane;
+  int* ints;
+  uint16_t* g;
+  size_t int_bytes, bytes;
+};
+inline Scratch3 carve3(void* scratch, int N, int H, int W, int V) {
+  const size_t n = (size_t)N * H * W;
+  const size_t units = (size_t)N * (((size_t)H * W + CH - 1) / CH) * 2;
+  Scratch3 s = {};
+  s.int_bytes = ((size_t)N * 2 + (size_t)V * 9) * sizeof(int);
+  const size_t o_part = round_up((size_t)V * 2 * sizeof(u64), 256);
+  const size_t o_comp = o_part + round_up(units * 2 * sizeof(double), 256);
+  const size_t o_plane = o_comp + n * 2 * sizeof(u64);
+  const size_t o_ints = o_plane + n * 2 * sizeof(unsigned);
+  const size_t o_g = o_ints + round_up(s.int_bytes, 256);
+  s.bytes = round_up(o_g + n * 2 * sizeof(uint16_t), 8);
+  if (scratch) {                                                    // NULL: the size query
+    char* p = (char*)scratch;
+    s.counts = (u64*)p;
+    s.part = (double*)(p + o_part);
+    s.comp = (u64*)(p + o_comp);
+    s.plane = (unsigned*)(p + o_plane);
+    s.ints = (int*)(p + o_ints);
+    s.g = (uint16_t*)(p + o_g);
+  }
+  return s;
+}
+
+// What both volume entry points refuse before anything is launched, from the arguments they share
+inline bool volumes_ok(int N, int H, int W, const int32_t* starts_dev, const int32_t* starts_host, int V,
+                       const double* spacing_dev, const void* scratch) {
+  if (!starts_dev || !starts_host || !spacing_dev || !scratch || !stf::volume_sizes_ok(N, H, W, V, MAXDIM))
+    return false;
+  if (((uintptr_t)starts_dev & 3) || ((uintptr_t)starts_host & 3) || ((uintptr_t)spacing_dev & 7) ||
+      ((uintptr_t)scratch & 7))
+    return false;
+  return stf::starts_ok(starts_host, V, N);
+}
+
+}  // namespace
+
+extern "C" size_t stf_boundary3d_scratch_bytes(int N, int H, int W, int V) {
+  if (!stf::volume_sizes_ok(N, H, W, V, MAXDIM)) return 0;
+  return carve3(nullptr, N, H, W, V).bytes;
+}
+
+extern "C" int stf_boundary3d_metrics(const uint8_t* mask, const int64_t* target, int N, int H, int W,
+                                      const int32_t* starts_dev, const int32_t* starts_host, int V,
+                                      const double* spacing_dev, int64_t ignore, double* out, int64_t* counts,
+                                      void* scratch, stf_stream_t stream) {
+  if (!mask || !target || !out || !counts || !volumes_ok(N, H, W, starts_dev, starts_host, V, spacing_dev, scratch))
+    return STF_EINVAL;
+  if (((uintptr_t)out & 7) || ((uintptr_t)counts & 7) || ((uintptr_t)target & 7)) return STF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long n = (long)N * H * W, rows = (long)N * H, HW = (long)H * W;
+  const int nch = (int)((HW + CH - 1) / CH);
+  const long units = (long)N * nch * 2;
+  const Scratch3 sc = carve3(scratch, N, H, W, V);
+  uint16_t *gP = sc.g, *gT = sc.g + n;
+  unsigned *plP = sc.plane, *plT = sc.plane + n;
+  double *psum = sc.part, *pmax = sc.part + units;
+  int *has = sc.ints, *box = has + (size_t)N * 2;
+  unsigned* cursor = (unsigned*)(box + (size_t)V * 8);
+  u64* cnt = (u64*)counts;
+  hipError_t e = stf::memset_async(counts, 0, (size_t)V * 2 * sizeof(int64_t), s);
+  if (e != hipSuccess) return (int)e;
+  e = stf::memset_async(sc.ints, 0, sc.int_bytes, s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(boundary_rows_kernel<true>, dim3((unsigned)((rows + BT / 64 - 1) / (BT / 64))), dim3(BT), 0, s,
+                     mask, target, rows, H, W, (long)ignore, (const int*)starts_dev, N, V, gP, gT, cnt, has, box);
+  STF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(boundary3d_plane_kernel, dim3((unsigned)((n + BT - 1) / BT)), dim3(BT), 0, s,
+                     (const uint16_t*)gP, (const uint16_t*)gT, (const u64*)cnt, (const int*)has, (const int*)box,
+                     (const int*)starts_dev, N, V, spacing_dev, n, H, W, plP, plT);
+  STF_CHECK_LAUNCH();
+  const unsigned grid = (unsigned)(units < MAX_UNIT_BLOCKS ? units : MAX_UNIT_BLOCKS);
+  hipLaunchKernelGGL(boundary3d_depth_kernel, dim3(grid), dim3(BT), 0, s, (const uint16_t*)gP, (const uint16_t*)gT,
+                     (const unsigned*)plP, (const unsigned*)plT, (const u64*)cnt, (const int*)has,
+                     (const int*)starts_dev, N, V, spacing_dev, units, nch, HW, psum, pmax, cursor, sc.comp);
+  STF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(boundary3d_fold_kernel, dim3((unsigned)V), dim3(RT), 0, s, (const double*)psum,
+                     (const double*)pmax, (const u64*)sc.comp, (const u64*)cnt, (const int*)starts_dev, N, nch, HW,
+                     out);
+  STF_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int stf_edt3d_sq(const uint8_t* sites, const uint8_t* where, int N, int H, int W,
+                            const int32_t* starts_dev, const int32_t* starts_host, int V,
+                            const double* spacing_dev, double* d2, void* scratch, stf_stream_t stream) {
+  if (!sites || !d2 || !volumes_ok(N, H, W, starts_dev, starts_host, V, spacing_dev, scratch)) return STF_EINVAL;
+  if ((uintptr_t)d2 & 7) return STF_EINVAL;
+  hipStream_t s = (hipStream_t)stream;
+  const long n = (long)N * H * W, rows = (long)N * H, HW = (long)H * W;
+  const Scratch3 sc = carve3(scratch, N, H, W, V);
+  int* has = sc.ints;
+  hipError_t e = stf::memset_async(sc.counts, 0, (size_t)V * 2 * sizeof(u64), s);
+  if (e != hipSuccess) return (int)e;
+  e = stf::memset_async(sc.ints, 0, sc.int_bytes, s);
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(edt_rows_kernel<true>, dim3((unsigned)((rows + BT / 64 - 1) / (BT / 64))), dim3(BT), 0, s, sites,
+                     rows, H, W, (const int*)starts_dev, N, V, sc.g, sc.counts, has);
+  STF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(edt3d_plane_kernel, dim3((unsigned)((n + BT - 1) / BT)), dim3(BT), 0, s, (const uint16_t*)sc.g,
+                     (const int*)has, (const int*)starts_dev, N, V, spacing_dev, n, H, W, sc.plane);
+  STF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(edt3d_depth_kernel, dim3((unsigned)((n + BT - 1) / BT)), dim3(BT), 0, s,
+                     (const unsigned*)sc.plane, where, (const u64*)sc.counts, (const int*)has,
+                     (const int*)starts_dev, N, V, spacing_dev, n, HW, d2);
   STF_CHECK_LAUNCH();
   return 0;
 }

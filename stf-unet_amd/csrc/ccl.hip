@@ -80,9 +80,14 @@
 //
 // Integer only: the same code in both storage builds.
 #include "common.h"
+#include "volumes.h"
 #include "../../include/stfunet.h"
 
 namespace {
+
+using stf::Vol;
+using stf::volume_of;
+using stf::starts_ok;
 
 constexpr int BT = 256;                 // threads per workgroup of the row passes: one wave per row
 constexpr int RT = 1024;                // threads of the raster walks
@@ -165,27 +170,7 @@ STF_DEV u64 wave_max(u64 v) {
 STF_DEV u64 key_of(int area, int root) { return ((u64)(unsigned)area << 32) | (u64)(ROOT_TOP - (unsigned)root); }
 STF_DEV int root_of(u64 key) { return key ? (int)(ROOT_TOP - (unsigned)(key & 0xFFFFFFFFull)) : -1; }
 
-struct Vol {
-  int v;        // the volume of slice z
-  int z0;       // its first slice, 0 <= z0 <= z
-};
-
-// wave-uniform.  Volumes: the largest v with starts[v] <= z.  Images: slice z is volume z.
-template <bool VOL>
-STF_DEV Vol volume_of(const int* __restrict__ starts, int V, int z) {
-  if constexpr (!VOL) {
-    return {z, z};
-  } else {
-    int lo = 0, hi = V;
-    while (hi - lo > 1) {
-      const int mid = (lo + hi) >> 1;
-      if (starts[mid] <= z) lo = mid; else hi = mid;
-    }
-    int z0 = starts[lo];
-    if ((unsigned)z0 > (unsigned)z) z0 = z;
-    return {lo, z0};
-  }
-}
+// Vol and volume_of<VOL> (volumes.h): the volume of slice z and its first slice; images: {z, z}.
 
 // rows = N * H.  L = in-volume index of the first voxel of the voxel's horizontal run, -1 on the
 // background; area (or NULL) = 0.
@@ -545,18 +530,7 @@ inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline unsigned row_grid(long rows) { return (unsigned)((rows + BT / 64 - 1) / (BT / 64)); }
 
 // N, H, W, V inside the limits and N * H * W < 2^31 (images: V = N)
-inline bool sizes_ok(int N, int H, int W, int V) {
-  if (N < 1 || H < 1 || W < 1 || H > MAXDIM || W > MAXDIM || V < 1 || V > N) return false;
-  return (long)N * H * W < (1L << 31);
-}
-
-// strictly ascending from 0 to N
-inline bool starts_ok(const int32_t* starts, int V, int N) {
-  if (starts[0] != 0 || starts[V] != N) return false;
-  for (int v = 0; v < V; ++v)
-    if (starts[v] >= starts[v + 1]) return false;
-  return true;
-}
+inline bool sizes_ok(int N, int H, int W, int V) { return stf::volume_sizes_ok(N, H, W, V, MAXDIM); }
 
 // What all four entry points refuse before anything is launched, from the arguments they share:
 // the row of the neighbour table for `connectivity`, 0 to refuse.  num may be NULL here.

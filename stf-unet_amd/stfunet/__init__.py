@@ -10,14 +10,16 @@ from . import predict  # noqa: F401  (the module; its loop is stfunet.predict.pr
 from .ema import WeightEMA  # noqa: F401
 from .loss import criterion  # noqa: F401
 from .optim import clip_grad_norm_  # noqa: F401
-from .predict import (boundary_metrics, connected_components, connected_components_3d,  # noqa: F401
-                      distance_transform_sq, filter_components, filter_components_3d, flip_planes, image_metrics,
-                      overlay, predict_masks, predict_tta, predict_volumes, tta_probabilities)
+from .predict import (boundary_metrics, boundary_metrics_3d, connected_components,  # noqa: F401
+                      connected_components_3d, distance_transform_3d, distance_transform_sq, filter_components,
+                      filter_components_3d, flip_planes, image_metrics, overlay, predict_masks, predict_tta,
+                      predict_volumes, tta_probabilities)
 from .resize import upsample_logits  # noqa: F401
 from .stf_lstm_unet import STFLSTMUNet  # noqa: F401
 from .unet import UNet  # noqa: F401
 
-__all__ = ["STFLSTMUNet", "UNet", "WeightEMA", "boundary_metrics", "clip_grad_norm_", "connected_components",
-           "connected_components_3d", "criterion", "distance_transform_sq", "filter_components", "filter_components_3d",
-           "flip_planes", "image_metrics", "overlay", "predict", "predict_masks", "predict_tta", "predict_volumes",
-           "tta_probabilities", "upsample_logits"]
+__all__ = ["STFLSTMUNet", "UNet", "WeightEMA", "boundary_metrics", "boundary_metrics_3d", "clip_grad_norm_",
+           "connected_components", "connected_components_3d", "criterion", "distance_transform_3d",
+           "distance_transform_sq", "filter_components", "filter_components_3d", "flip_planes", "image_metrics",
+           "overlay", "predict", "predict_masks", "predict_tta", "predict_volumes", "tta_probabilities",
+           "upsample_logits"]

@@ -23,6 +23,9 @@ gfx950 kernels of ``csrc/predict.hip``:
 * ``connected_components_3d`` / ``filter_components_3d`` / ``predict_volumes``  the same labels and
   clean-up per volume of stacked slices (6 / 18 / 26 connectivity, the same ``csrc/ccl.hip``), and the loop
   that groups a patient's slices: 3-D post-processing and per-volume (per-case) Dice / IoU
+* ``boundary_metrics_3d`` / ``distance_transform_3d``  per-volume HD, HD95 and ASSD with voxel spacing
+  ``(sz, sy, sx)`` (MedPy on the 3-D array) and the weighted squared distance transform underneath
+  (the volume kernels of ``csrc/boundary.hip``); ``predict_volumes(boundary=True)`` reports them per case
 
 ``predict(model, loader, device, rule="sigmoid", channel=0, paint=0)`` reproduces test.py bit for
 bit (it thresholds channel 0 and inverts the mask before painting, :75-76), except that the
@@ -413,6 +416,140 @@ def filter_components_3d(mask, depths=None, keep_largest=False, min_size=0, conn
     return out if target is None else (out, counts)
 
 
+def _is_real(x):
+    return isinstance(x, numbers.Real) and not isinstance(x, bool)
+
+
+def _check_spacing_3d(spacing, V):
+    """``spacing`` of the volume calls as ``V`` rows ``[sz, sy, sx]`` of floats: a positive finite
+    number (isotropic), one triple ``(sz, sy, sx)`` for every volume, or ``V`` triples (a sequence or
+    a ``[V, 3]`` tensor; a tensor on the device is copied to the host to be checked)."""
+    what = (f"spacing must be a finite positive number, a triple (sz, sy, sx) of such numbers or one triple per "
+            f"volume ({V}), not {spacing!r}")
+    if torch.is_tensor(spacing):
+        if spacing.dim() not in (1, 2) or spacing.dtype in (torch.bool,) or spacing.dtype.is_complex:
+            raise ValueError(what)
+        spacing = spacing.detach().to("cpu", torch.float64).tolist()
+    if _is_real(spacing):
+        rows = [[spacing] * 3] * V
+    elif isinstance(spacing, (str, bytes)) or spacing is None:
+        raise ValueError(what)
+    else:
+        try:
+            items = list(spacing)
+        except TypeError:
+            raise ValueError(what) from None
+        if len(items) == 3 and all(_is_real(s) for s in items):
+            rows = [items] * V
+        else:
+            rows = []
+            for item in items:
+                if isinstance(item, (str, bytes)) or _is_real(item) or isinstance(item, bool) or item is None:
+                    raise ValueError(what)
+                try:
+                    row = item.tolist() if torch.is_tensor(item) else list(item)
+                except TypeError:
+                    raise ValueError(what) from None
+                if len(row) != 3 or not all(_is_real(s) for s in row):
+                    raise ValueError(what)
+                rows.append(row)
+            if len(rows) != V:
+                raise ValueError(what)
+    rows = [[float(s) for s in row] for row in rows]
+    if not all(0.0 < s < float("inf") for row in rows for s in row):
+        raise ValueError(what)
+    return rows
+
+
+def _boundary3d_scratch(N, H, W, V, device):
+    nbytes = load().stf_boundary3d_scratch_bytes(N, H, W, V)
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def _boundary3d(mask, target, depths, rows, ignore_index):
+    """``stf_boundary3d_metrics`` on a checked uint8 device mask with checked ``depths`` and spacing
+    ``rows``: (out float64 [V, 3], border counts int64 [V, 2])."""
+    N, H, W = mask.shape
+    dev, V = mask.device, len(depths)
+    out = torch.empty((V, 3), dtype=torch.float64, device=dev)
+    counts = torch.empty((V, 2), dtype=torch.int64, device=dev)
+    if N:
+        target = target.detach().to(device=dev, dtype=torch.int64).contiguous()
+        host, starts = _starts(depths, dev)                   # the call reads the host table before it returns
+        spacing = torch.tensor(rows, dtype=torch.float64).reshape(V, 3).to(dev)
+        scratch = _boundary3d_scratch(N, H, W, V, dev)
+        with torch.cuda.device(dev):
+            call("stf_boundary3d_metrics", _p(mask), _p(target), N, H, W, _p(starts), host.data_ptr(), V, _p(spacing),
+                 _ignore(ignore_index), _p(out), _p(counts), _p(scratch), stream())
+    return out, counts
+
+
+def boundary_metrics_3d(mask, target, depths=None, spacing=1.0, ignore_index=None):
+    """Per-volume (per-case) boundary metrics of ``mask`` against ``target`` (both ``[N, H, W]``, a
+    stack of slices cut into ``V = len(depths)`` volumes as in ``connected_components_3d``; ``mask``
+    bool, uint8 or any integer, nonzero = foreground; ``target`` any integer, > 0 = foreground; voxels
+    whose target equals ``ignore_index`` are background on both sides).
+
+    Returns ``{"hd", "hd95", "assd"}`` as float64 ``[V]`` device tensors in the unit of ``spacing`` and
+    ``border_counts`` int64 ``[V, 2]`` = (|dP|, |dT|): MedPy's ``hd`` / ``hd95`` / ``assd`` on each
+    volume with ``voxelspacing=(sz, sy, sx)`` and ``connectivity=1``.  The border of M is
+    ``M & ~erode(M)`` with the 6-neighbour cross and background outside the volume (so in a volume
+    one slice deep every foreground voxel is a border voxel, unlike ``boundary_metrics``); volumes
+    never see each other.  ``spacing``: a positive finite number, a triple ``(sz, sy, sx)`` or one
+    triple per volume (a sequence or a ``[V, 3]`` tensor).  A volume with an empty mask or target
+    gets NaN in all three.  The same bits from run to run, and for a volume passed alone or in a
+    stack."""
+    _check_target_shape(target, mask.shape)
+    N, H, W = _check_bhw(mask, "mask")
+    depths = _check_depths(depths, N)
+    rows = _check_spacing_3d(spacing, len(depths))
+    _check_target_dtype(target)
+    mask = _as_u8(mask.detach(), "mask")
+    _device_only(mask, "boundary_metrics_3d")
+    _device_only(target, "boundary_metrics_3d")
+    out, counts = _boundary3d(mask, target, depths, rows, ignore_index)
+    hd, hd95, assd = out.unbind(1)
+    return {"hd": hd, "hd95": hd95, "assd": assd, "border_counts": counts}
+
+
+def distance_transform_3d(sites, depths=None, spacing=1.0, where=None):
+    """float64 ``[N, H, W]``: the squared distance, weighted by ``spacing``, of every voxel to the
+    nearest nonzero voxel of ``sites`` (bool or integer ``[N, H, W]``) of the same volume (``depths``
+    and ``spacing`` as in ``boundary_metrics_3d``); ``+inf`` throughout a volume without sites.  With
+    ``where`` (same shape) only its nonzero voxels are computed, the others are -1.
+
+    The plane pass scans along ``y`` in every slice that has a site and the depth pass along ``z``
+    from every computed voxel, each about as far as the distance found.  Without ``where`` a call
+    whose bound ``N * H * W * (H + max(depths))`` exceeds ``MAX_FULL_SCAN`` is refused
+    (``ValueError``); passing ``where`` (all ones, if every voxel is wanted) lifts the guard."""
+    N, H, W = _check_bhw(sites, "sites")
+    if where is not None and tuple(where.shape) != tuple(sites.shape):
+        raise ValueError(f"where {tuple(where.shape)} does not match the sites' {tuple(sites.shape)}")
+    depths = _check_depths(depths, N)
+    rows = _check_spacing_3d(spacing, len(depths))
+    bound = N * H * W * (H + max(depths, default=0))
+    if where is None and bound > MAX_FULL_SCAN:
+        raise ValueError(f"distance_transform_3d without `where` may read N * H * W * (H + depth) = {bound} values "
+                         f"(more than {MAX_FULL_SCAN}) when the sites are sparse; pass `where` to name the voxels "
+                         "that are needed, or all ones to accept the cost")
+    sites = _as_u8(sites.detach(), "sites")
+    _device_only(sites, "distance_transform_3d")
+    dev, V = sites.device, len(depths)
+    if where is not None:
+        where = _as_u8(where.detach(), "where")
+        _device_only(where, "distance_transform_3d")
+        where = where.to(dev)
+    d2 = torch.empty((N, H, W), dtype=torch.float64, device=dev)
+    if N:
+        host, starts = _starts(depths, dev)
+        table = torch.tensor(rows, dtype=torch.float64).reshape(V, 3).to(dev)
+        scratch = _boundary3d_scratch(N, H, W, V, dev)
+        with torch.cuda.device(dev):
+            call("stf_edt3d_sq", _p(sites), _p(where), N, H, W, _p(starts), host.data_ptr(), V, _p(table), _p(d2),
+                 _p(scratch), stream())
+    return d2
+
+
 def overlay(frames, mask, color=(0, 255, 0), alpha=0.5, paint=1):
     """``uint8 [B, H, W, 3]``: ``frames`` normalised to 0..255 per image, with ``color`` blended
     at ``alpha`` into the pixels where the mask is non-zero (``paint=1``) or zero (``paint=0``).
@@ -681,7 +818,8 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
 
 
 def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argmax", channel=0, threshold=0.5,
-                    ignore_index=None, keep_largest=False, min_size=0, connectivity=26, keep_masks=False):
+                    ignore_index=None, keep_largest=False, min_size=0, connectivity=26, keep_masks=False,
+                    boundary=False, spacing=1.0):
     """The inference loop over volumes: the loader yields slices in volume order -- ``depths[0]``
     slices of volume 0, then volume 1 and so on (``stfunet.dataset.volume_order`` puts a
     ``DriveDataset`` into that order); batches may straddle volume boundaries.
@@ -701,8 +839,16 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
     of ``V`` ``uint8 [D_v, H, W]`` masks.  Raises ``ValueError`` when the loader's slice total is not
     ``sum(depths)``.
 
-    Not here: boundary metrics in 3-D (HD95 with slice spacing), overlays (``keep_masks=True`` and
-    ``overlay`` cover them) and anisotropic connectivity."""
+    ``boundary=True`` adds, when targets came, ``boundary_metrics_3d`` of every volume's mask (after
+    the component filter, when one is on) against its target at ``spacing`` (a number, a triple
+    ``(sz, sy, sx)`` or one triple per volume): per-volume ``hd`` / ``hd95`` / ``assd`` (NaN where the
+    mask or the target is empty), their means over the defined volumes ``mean_hd`` / ``mean_hd95`` /
+    ``mean_assd`` (NaN when there is none) and ``num_boundary``, the number of defined volumes; all
+    None without targets.  The slices are then held until their volume is complete, as for the
+    component options; with those off still no labelling kernel runs.  Without ``boundary`` nothing
+    of this runs and the result has no such key.
+
+    Not here: overlays (``keep_masks=True`` and ``overlay`` cover them) and anisotropic connectivity."""
     batches = _batches(model, data_loader, device, tta, rule, channel, threshold, ignore_index)
     connectivity, min_size = _check_components_3d(connectivity, min_size)
     if depths is None:
@@ -710,11 +856,12 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
     depths = _check_depths(depths)
     components = bool(keep_largest) or min_size > 0
     V, total = len(depths), sum(depths)
+    rows = _check_spacing_3d(spacing, V) if boundary else None
     model.eval()
     slice_volume = torch.repeat_interleave(torch.arange(V), torch.tensor(depths, dtype=torch.int64)).to(device)
     vol_counts = None                               # options off: int64 [V, 3], summed as the slices come
     held_masks, held_targets, held, done = [], [], 0, 0   # options on: slices of volumes not yet complete
-    all_counts, all_num, masks, idx, with_targets = [], [], [], 0, None
+    all_counts, all_num, all_boundary, masks, idx, with_targets = [], [], [], [], 0, None
     with torch.no_grad():
         for _, targets, mask, counts, _ in batches:
             if with_targets is None:
@@ -731,7 +878,7 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
                     vol_counts.index_add_(0, slice_volume[idx:idx + B], counts)
                 if keep_masks:
                     masks.append(mask)
-            else:
+            if components or (boundary and targets is not None):
                 held_masks.append(mask)
                 if targets is not None:
                     held_targets.append(targets)
@@ -745,13 +892,18 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
                     t = None
                     if targets is not None:
                         t = torch.cat(held_targets) if len(held_targets) > 1 else held_targets[0]
-                    out, counts, num = _filter(m[:take], None if t is None else t[:take], depths[done:done + k],
-                                               keep_largest, min_size, connectivity, ignore_index)
-                    all_num.append(num)
-                    if counts is not None:
-                        all_counts.append(counts)
-                    if keep_masks:
-                        masks.extend(out.split(depths[done:done + k]))
+                    out = m[:take]
+                    if components:
+                        out, counts, num = _filter(out, None if t is None else t[:take], depths[done:done + k],
+                                                   keep_largest, min_size, connectivity, ignore_index)
+                        all_num.append(num)
+                        if counts is not None:
+                            all_counts.append(counts)
+                        if keep_masks:
+                            masks.extend(out.split(depths[done:done + k]))
+                    if boundary and t is not None:
+                        all_boundary.append(_boundary3d(out.contiguous(), t[:take], depths[done:done + k],
+                                                        rows[done:done + k], ignore_index)[0])
                     held_masks = [m[take:]] if take < held else []
                     held_targets = [t[take:]] if t is not None and take < held else []
                     held -= take
@@ -767,6 +919,13 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
     if vol_counts is not None:
         dice, iou = image_metrics(vol_counts)
         res.update(dice=dice, iou=iou, mean_dice=dice.mean(), mean_iou=iou.mean())
+    if boundary:
+        per_volume = torch.cat(all_boundary) if all_boundary else None
+        for j, k in enumerate(("hd", "hd95", "assd")):
+            v = None if per_volume is None else per_volume[:, j]
+            res[k] = v
+            res["mean_" + k] = None if v is None else torch.nanmean(v)
+        res["num_boundary"] = None if per_volume is None else (~torch.isnan(per_volume[:, 0])).sum()
     if components:
         res["num_components"] = torch.cat(all_num).to(torch.int64) if all_num else None
     if keep_masks:

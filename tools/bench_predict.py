@@ -35,6 +35,15 @@ stacked as ``--batch`` slices (128 for the record) in 1 and in 8 volumes: ``conn
 connectivity 26 (6 for the checkerboard), next to the 2-D ``connected_components`` /
 ``filter_components`` on the same slices in the same rounds.  Prints one JSON line.
 
+``--boundary3d`` measures the per-volume boundary metrics (csrc/boundary.hip, volumes) on ``--batch``
+slices (128 for the record) cut into 8 volumes, each holding one lesion-sized ellipsoid per side
+(``overlap``: the prediction a few voxels off the target; ``far_apart``: in opposite corners), at
+spacing (2.5, 0.75, 0.75): ``boundary_metrics_3d`` per call, every launch of one call as the
+difference of two replays of a recorded plan (entries 0..i and 0..i-1), ``filter_components_3d``
+with ``keep_largest`` on the same volumes for scale, the host computation (scipy on one volume, copy
+included) and the ``predict_volumes`` loop (UNet) without and with ``boundary=True``.  Prints one
+JSON line.
+
 ``--tta`` measures the work mirror test-time augmentation adds around the forwards (csrc/tta.hip) at
 the same shape: ``flip_planes`` of the 64 x 8 x 256^2 input per view, and ``stf_tta_accumulate`` on
 64 x K x 256^2 logits for K = 2 and 16 (a middle view: K planes read, K planes read and written; the
@@ -64,6 +73,7 @@ ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--boundary", action="store_true", help="measure boundary_metrics instead")
 ap.add_argument("--components", action="store_true", help="measure the connected-component kernels instead")
 ap.add_argument("--components3d", action="store_true", help="measure the volume-level component kernels instead")
+ap.add_argument("--boundary3d", action="store_true", help="measure the per-volume boundary metrics instead")
 ap.add_argument("--tta", action="store_true", help="measure the test-time-augmentation kernels instead")
 ap.add_argument("--host-images", type=int, default=8, help="images per regime of the scipy host timing")
 args = ap.parse_args()
@@ -336,6 +346,133 @@ if args.components3d:
         "ratio_3d_over_2d": {f"{op}_V{v}_{k}": round(med[f"{op}3d_V{v}_{k}"] / med[f"{op}2d_{k}"], 2)
                              for op in ("label", "filter") for v in volumes for k in data},
         "mean_components_per_volume": num,
+    }))
+    sys.exit(0)
+
+if args.boundary3d:
+    import time
+    from stfunet import _lib, boundary_metrics_3d, filter_components_3d
+    from stfunet import predict as P3
+    from stfunet.predict import predict_volumes
+    from stfunet.unet import UNet
+    V = 8 if B % 8 == 0 else 1
+    D = B // V
+    depths, spacing = [D] * V, (2.5, 0.75, 0.75)
+    g = torch.Generator().manual_seed(5)
+    zz, yy, xx = torch.meshgrid(torch.arange(D), torch.arange(H), torch.arange(W), indexing="ij")
+
+    def ball(cz, cy, cx, rz, r):
+        return ((zz - cz) / rz) ** 2 + ((yy - cy) / r) ** 2 + ((xx - cx) / r) ** 2 <= 1.0
+
+    data = {}
+    for regime in ("overlap", "far_apart"):
+        Pm, Tm = torch.zeros(B, H, W, dtype=torch.uint8), torch.zeros(B, H, W, dtype=torch.int64)
+        for v in range(V):
+            r, rz = int(torch.randint(H // 16, H // 8, (1,), generator=g)), max(1.5, D / 5)
+            if regime == "overlap":
+                cy, cx = (int(c) for c in torch.randint(H // 4, 3 * H // 4, (2,), generator=g))
+                dy, dx = (int(c) for c in torch.randint(-4, 5, (2,), generator=g))
+                pc, tc = (D / 2 + 0.5, cy + dy, cx + dx), (D / 2, cy, cx)
+            else:
+                pc, tc = (rz, r + 2, r + 2), (D - 1 - rz, H - 3 - r, W - 3 - r)
+            Pm[v * D:(v + 1) * D] = ball(*pc, rz, r).to(torch.uint8)
+            Tm[v * D:(v + 1) * D] = ball(*tc, rz, r).long()
+        data[regime] = (Pm.cuda(), Tm.cuda())
+    legs = []
+    for k, (m, t) in data.items():
+        legs += [(f"boundary3d_{k}", lambda m=m, t=t: boundary_metrics_3d(m, t, depths, spacing)),
+                 (f"filter3d_{k}", lambda m=m, t=t: filter_components_3d(m, depths, True, 0, 26, target=t))]
+    for _, fn in legs:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name, _ in legs}
+    for _ in range(args.rounds):
+        for name, fn in legs:
+            us[name].append(timed(fn, args.iters))
+    med = {k: statistics.median(v) for k, v in us.items()}
+    # every launch of one call on its own: the call recorded into a plan, its entries replayed singly
+    lib = _lib.load()
+    names = ("memset_counts", "memset_flags", "rows", "plane", "depth", "fold")
+    kernels = {}
+    for k, (m, t) in data.items():
+        host_starts, starts = P3._starts(depths, m.device)
+        table = torch.tensor([spacing] * V, dtype=torch.float64, device=m.device)
+        out = torch.empty(V, 3, dtype=torch.float64, device=m.device)
+        cnt = torch.empty(V, 2, dtype=torch.int64, device=m.device)
+        scratch = P3._boundary3d_scratch(B, H, W, V, m.device)        # held while the plan replays
+        plan = lib.stf_plan_create()
+        assert lib.stf_plan_record(plan) == 0
+        try:
+            _lib.call("stf_boundary3d_metrics", m.data_ptr(), t.data_ptr(), B, H, W, starts.data_ptr(),
+                      host_starts.data_ptr(), V, table.data_ptr(), -1, out.data_ptr(), cnt.data_ptr(),
+                      scratch.data_ptr(), _lib.stream())
+        finally:
+            assert lib.stf_plan_stop() == 0
+        torch.cuda.synchronize()
+        assert lib.stf_plan_size(plan) == len(names), lib.stf_plan_size(plan)
+        # entry i = replay of entries 0..i minus replay of 0..i-1: every replay starts from the memsets, so
+        # the counts and the cursor the later launches read are those of one call
+        prefix = [0.0]
+        for i in range(len(names)):
+            one = [timed(lambda: lib.stf_plan_replay(plan, 0, i + 1, None), args.iters) for _ in range(args.rounds)]
+            prefix.append(statistics.median(one))
+        kernels[k] = {name: round(prefix[i + 1] - prefix[i], 1) for i, name in enumerate(names)}
+        kernels[k]["all"] = round(prefix[-1], 1)
+        lib.stf_plan_destroy(plan)
+
+    def scipy_volume_ms(m, t):
+        try:
+            import numpy as np
+            from scipy.ndimage import binary_erosion, distance_transform_edt, generate_binary_structure
+        except ImportError:
+            return None
+        cross = generate_binary_structure(3, 1)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        p, q = m[:D].cpu().numpy().astype(bool), t[:D].cpu().numpy() > 0
+        bp, bt = p ^ binary_erosion(p, cross), q ^ binary_erosion(q, cross)
+        a, c = distance_transform_edt(~bt, sampling=spacing)[bp], distance_transform_edt(~bp, sampling=spacing)[bt]
+        _ = max(a.max(), c.max()), np.percentile(np.hstack((a, c)), 95), (a.mean() + c.mean()) / 2
+        return (time.perf_counter() - t0) * 1e3
+
+    host = {k: scipy_volume_ms(*v) for k, v in data.items()}
+    model = UNet(in_channels=8, num_classes=2).cuda()
+    half = B // 2
+    loader = [(inputs[i:i + half].view(half, 1, 8, H, W), data["overlap"][1][i:i + half]) for i in (0, half)]
+
+    def loop_ms(flag):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        predict_volumes(model, loader, torch.device("cuda"), depths, boundary=flag, spacing=spacing)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for flag in (False, True, False, True):
+        loop_ms(flag)
+    loop = {False: [], True: []}
+    for _ in range(args.rounds):
+        for flag in (False, True):
+            loop[flag].append(loop_ms(flag))
+    loop_med = {k: statistics.median(v) for k, v in loop.items()}
+    res = {k: boundary_metrics_3d(m, t, depths, spacing) for k, (m, t) in data.items()}
+    print(json.dumps({
+        "tool": "bench_predict", "leg": "boundary3d", "shape": [B, H, W], "volumes": V, "spacing": spacing,
+        "rounds": args.rounds, "iters": args.iters,
+        "scratch_bytes": int(lib.stf_boundary3d_scratch_bytes(B, H, W, V)),
+        "us_per_call": {k: round(v, 1) for k, v in med.items()},
+        "us_per_call_min_max": {k: [round(min(v), 1), round(max(v), 1)] for k, v in us.items()},
+        "us_per_volume": {k: round(v / V, 1) for k, v in med.items()},
+        "boundary3d_over_filter3d": {k: round(med[f"boundary3d_{k}"] / med[f"filter3d_{k}"], 2) for k in data},
+        "us_per_launch": kernels,
+        "mean_hd95": {k: float(torch.nanmean(v["hd95"])) for k, v in res.items()},
+        "mean_border_voxels": {k: float(v["border_counts"].double().mean()) for k, v in res.items()},
+        "scipy_host_ms_per_volume": {k: None if v is None else round(v, 1) for k, v in host.items()},
+        "predict_volumes_loop_ms": {"slices": B, "plain": round(loop_med[False], 3),
+                                    "boundary": round(loop_med[True], 3),
+                                    "plain_min_max": [round(min(loop[False]), 3), round(max(loop[False]), 3)],
+                                    "boundary_min_max": [round(min(loop[True]), 3), round(max(loop[True]), 3)],
+                                    "added_us_per_volume": round((loop_med[True] - loop_med[False]) * 1e3 / V, 1)},
     }))
     sys.exit(0)
 
