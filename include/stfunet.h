@@ -839,6 +839,43 @@ int stf_edt3d_sq(const uint8_t* sites, const uint8_t* where, int N, int H, int W
                  const int32_t* starts_host, int V, const double* spacing_dev, double* d2, void* scratch,
                  stf_stream_t stream);
 
+/* ---------------------------------------------------------------- boundary loss
+ * The boundary loss of Kervadec et al. (MIDL 2019; INTEGRATION.md 2.1 states the definition, DESIGN.md
+ * 5.18 the passes): dense signed distance maps of the targets, the term and its gradient.  Additive
+ * to ABI v17; no entry point allocates or reads back; no floating-point atomics, the same bits from
+ * run to run.
+ *
+ * The maps.  target int64 [N][H][W], classes K in 2..16; phi float32 [N][K-1][H][W], OVERWRITTEN,
+ * channel k-1 for class k = 1..K-1 with G = {target == k} (a pixel whose target equals ignore, when
+ * ignore >= 0, is in no G): +d(q, G) outside G, 1 - d(q, not G) inside (0 on G's innermost border),
+ * d the exact Euclidean distance in pixels as (float)sqrt((double)d2); 0 everywhere where G is empty
+ * or the whole image.  Limits: N >= 1, 1 <= H, W <= 4096, N * (K-1) * H * W < 2^31.  The cost does
+ * not depend on where the sites are.  STF_EINVAL (nothing launched) for a NULL pointer, a size outside
+ * the limits, a scratch or target that is not 8-byte aligned or a phi that is not 4-byte aligned.
+ *
+ * Bytes of the scratch stf_sdf needs, a multiple of 8 (0 outside the limits). */
+size_t stf_sdf_scratch_bytes(int N, int H, int W, int classes);
+int stf_sdf(const int64_t* target, int N, int H, int W, int classes, int64_t ignore, float* phi, void* scratch,
+            stf_stream_t stream);
+/* The term.  With m = (ignore >= 0 ? target != ignore : 1), p = softmax(logits) over the K classes,
+ * M = sum m over the batch and phi_0 = 0:
+ *   L_B  = sum_{n, q, k >= 1} m p_k phi_k / ((K-1) M)
+ *   dz_j = m p_j (phi_j - sum_{c >= 1} p_c phi_c) / ((K-1) M)
+ * Both entry points ACCUMULATE, so they follow a criterion route's forward / backward on the same
+ * stream: stf_bloss_fwd does loss[0] += alpha * L_B (NaN when every pixel is ignored, as the
+ * cross-entropy) and leaves (sum, M) in partials[0..1]; stf_bloss_bwd does
+ * dlogits += grad_out[0] * alpha * dz (grad_out NULL = 1) with M = partials + 1 of the forward, and
+ * does not touch an ignored pixel.  logits fp32 [N][K][H][W], phi as above, partials
+ * stf_bloss_scratch_floats(N) floats (0 for N outside 1..65535).  STF_EINVAL (nothing launched) for a
+ * NULL required pointer, K outside 2..16, an ignore that is a class id, N outside 1..65535,
+ * H * W >= 2^31 or an alpha that is negative or not finite. */
+int stf_bloss_scratch_floats(int N);
+int stf_bloss_fwd(const float* logits, const int64_t* target, const float* phi, int N, int H, int W, int classes,
+                  int ignore, float alpha, float* partials, float* loss, stf_stream_t stream);
+int stf_bloss_bwd(const float* logits, const int64_t* target, const float* phi, int N, int H, int W, int classes,
+                  int ignore, float alpha, const float* grad_out, const float* M, float* dlogits,
+                  stf_stream_t stream);
+
 /* ---------------------------------------------------------------- PK maps (extended Tofts)
  * pk_fitting.py ToftsModelFitter, all fp32.  The host builds
  * the reference's constant tables exactly as the reference does (pk_fitting.py:

@@ -51,6 +51,7 @@
 //            patterns (non-negative doubles order as integers).  The list's order varies from run
 //            to run; only integer histograms and minima read it.
 #include "common.h"
+#include "edt_rows.h"
 #include "volumes.h"
 #include "../../include/stfunet.h"
 
@@ -62,11 +63,14 @@ namespace {
 constexpr int BT = 256;                 // threads per workgroup of the row and column passes
 constexpr int RT = 1024;                // threads of the per-image reduction
 constexpr int MAXDIM = 4096;
-constexpr unsigned G_NONE = 0xFFFFu;    // no border pixel in this row
-constexpr int X_NONE = 1 << 20;         // "no border pixel to the right" (> any x)
 constexpr int D2_NONE = 0x7fffffff;
 
-typedef unsigned long long u64;
+// the row pass's words, g and its "no border pixel in this row" value: edt_rows.h
+using stf::G_NONE;
+using stf::X_NONE;
+using stf::store_row_g;
+using stf::u64;
+using stf::wave_sum_i;
 
 STF_DEV u64 shfl_up1(u64 v, int lane) {
   const u64 t = __shfl_up(v, 1, 64);
@@ -84,42 +88,6 @@ STF_DEV u64 border_word(u64 up, u64 mid, u64 down, u64 zz, int lane) {
   const u64 left = (mid << 1) | (shfl_up1(mid, lane) >> 63);        // bit i = pixel x - 1
   const u64 right = (mid >> 1) | (shfl_down1(mid, lane) << 63);     // bit i = pixel x + 1
   return mid & ~(up & down & left & right & zz);
-}
-
-// g of one row from its border words (lane c holds word c): uint16 distance to the nearest set bit
-// of the row, G_NONE when the row has none.
-STF_DEV void store_row_g(u64 bw, int lane, int W, uint16_t* __restrict__ grow) {
-  int last = bw ? lane * 64 + 63 - __builtin_clzll(bw) : -1;        // last set bit at or before this word
-  int first = bw ? lane * 64 + __builtin_ctzll(bw) : X_NONE;        // first set bit at or after it
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int a = __shfl_up(last, o, 64), b = __shfl_down(first, o, 64);
-    if (lane >= o) last = a > last ? a : last;
-    if (lane + o < 64) first = b < first ? b : first;
-  }
-  int before = __shfl_up(last, 1, 64), after = __shfl_down(first, 1, 64);
-  if (lane == 0) before = -1;
-  if (lane == 63) after = X_NONE;
-  const int nw = (W + 63) >> 6;
-  for (int c = 0; c < nw; ++c) {
-    const u64 w = __shfl(bw, c, 64);
-    const int wl = __shfl(before, c, 64), wr = __shfl(after, c, 64);
-    const int x = c * 64 + lane;
-    const u64 lo = w & (~0ull >> (63 - lane));                      // bits 0..lane
-    const u64 hi = w >> lane;                                       // bits lane..63, moved down
-    const int xl = lo ? c * 64 + 63 - __builtin_clzll(lo) : wl;
-    const int xr = hi ? x + __builtin_ctzll(hi) : wr;
-    unsigned g = G_NONE;
-    if (xl >= 0) g = (unsigned)(x - xl);
-    if (xr < X_NONE && (unsigned)(xr - x) < g) g = (unsigned)(xr - x);
-    if (x < W) grow[x] = (uint16_t)g;
-  }
-}
-
-STF_DEV int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 STF_DEV int wave_max_i(int v) {

@@ -8,7 +8,7 @@ kernels through the C ABI in ``include/stfunet.h``.
 from . import _lib  # noqa: F401
 from . import predict  # noqa: F401  (the module; its loop is stfunet.predict.predict)
 from .ema import WeightEMA  # noqa: F401
-from .loss import criterion  # noqa: F401
+from .loss import boundary_criterion, boundary_loss, criterion, signed_distance_maps  # noqa: F401
 from .optim import clip_grad_norm_  # noqa: F401
 from .predict import (boundary_metrics, boundary_metrics_3d, connected_components,  # noqa: F401
                       connected_components_3d, distance_transform_3d, distance_transform_sq, filter_components,
@@ -18,8 +18,9 @@ from .resize import upsample_logits  # noqa: F401
 from .stf_lstm_unet import STFLSTMUNet  # noqa: F401
 from .unet import UNet  # noqa: F401
 
-__all__ = ["STFLSTMUNet", "UNet", "WeightEMA", "boundary_metrics", "boundary_metrics_3d", "clip_grad_norm_",
+__all__ = ["STFLSTMUNet", "UNet", "WeightEMA", "boundary_criterion", "boundary_loss", "boundary_metrics",
+           "boundary_metrics_3d", "clip_grad_norm_",
            "connected_components", "connected_components_3d", "criterion", "distance_transform_3d",
            "distance_transform_sq", "filter_components", "filter_components_3d", "flip_planes", "image_metrics",
-           "overlay", "predict", "predict_masks", "predict_tta", "predict_volumes", "tta_probabilities",
-           "upsample_logits"]
+           "overlay", "predict", "predict_masks", "predict_tta", "predict_volumes", "signed_distance_maps",
+           "tta_probabilities", "upsample_logits"]

@@ -207,6 +207,11 @@ _SIGS = {
     "stf_boundary3d_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stf_boundary3d_metrics": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, c_int64, P, P, P, P]),
     "stf_edt3d_sq": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, P, P, P]),
+    "stf_sdf_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "stf_sdf": (c_int, [P, c_int, c_int, c_int, c_int, c_int64, P, P, P]),
+    "stf_bloss_scratch_floats": (c_int, [c_int]),
+    "stf_bloss_fwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P]),
+    "stf_bloss_bwd": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P, P, P, P]),
     "stf_tofts_forward": (c_int, [P, P, P, c_int, c_int, P, P, P, P, P, c_int, c_float, P, P]),
     "stf_tofts_fit": (c_int, [P, c_int, c_int, P, P, P, P, P, c_int, c_float, c_int, c_int, P, c_float, c_float,
                               c_float, P, P, P]),

@@ -29,7 +29,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .loss import criterion  # noqa: F401  (re-export, reference name)
+from .loss import boundary_criterion, criterion  # noqa: F401  (criterion: re-export, reference name)
 
 
 def preprocess_input(inputs, model):
@@ -318,7 +318,7 @@ def evaluate(model, data_loader, device, num_classes, *, ema=None):
 
 def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler=None,
                     print_freq=10, scaler=None, *, loss_weight=None, dice=True, ignore_index=-100,
-                    max_grad_norm=None, focal_gamma=0.0, tversky=None, ema=None):
+                    max_grad_norm=None, focal_gamma=0.0, tversky=None, ema=None, boundary_weight=0.0):
     """The reference's loop (its positional signature and defaults); the keyword-only
     ``loss_weight`` / ``dice`` / ``ignore_index`` / ``focal_gamma`` / ``tversky`` go to ``criterion``
     (``ignore_index=255`` for batches whose targets ``collate_fn`` padded to a common size).
@@ -330,8 +330,14 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
     step.  The logger gains a ``grad_norm`` meter, read in the same host read as the loss.
 
     ``ema`` (a ``stfunet.WeightEMA``; ``None``: the loop as it was): ``ema.update()`` after every
-    optimizer step, a step the GradScaler or a non-finite clip norm skipped included."""
+    optimizer step, a step the GradScaler or a non-finite clip norm skipped included.
+
+    ``boundary_weight`` (0: the loop as it was) takes ``boundary_criterion``: that many times the boundary loss
+    on signed distance maps made from each step's targets on the device.  The caller raises it from epoch
+    to epoch (Kervadec's rebalancing); the loop has no schedule of its own."""
+    from .loss import _boundary_weight
     from .optim import AdamW, clip_grad_norm_
+    boundary_weight = _boundary_weight(boundary_weight, num_classes)    # ValueError before any step runs
     fused_clip = max_grad_norm is not None and isinstance(optimizer, AdamW)
     if fused_clip:
         previous = [group.get("max_grad_norm") for group in optimizer.param_groups]
@@ -340,7 +346,7 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
     try:
         return _train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler,
                                 print_freq, scaler, loss_weight, dice, ignore_index, max_grad_norm, fused_clip,
-                                clip_grad_norm_, focal_gamma, tversky, ema)
+                                clip_grad_norm_, focal_gamma, tversky, ema, boundary_weight)
     finally:
         if fused_clip:
             for group, value in zip(optimizer.param_groups, previous):
@@ -349,7 +355,7 @@ def train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, l
 
 def _train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, lr_scheduler, print_freq, scaler,
                      loss_weight, dice, ignore_index, max_grad_norm, fused_clip, clip_grad_norm_, focal_gamma,
-                     tversky, ema=None):
+                     tversky, ema=None, boundary_weight=0.0):
     model.train()
     logger = MetricLogger(delimiter="  ")
     logger.add_meter("lr", SmoothedValue(window_size=1, fmt="{value:.6f}"))
@@ -360,8 +366,13 @@ def _train_one_epoch(model, optimizer, data_loader, device, epoch, num_classes, 
         image = preprocess_input(image, model).to(device)
         target = target.to(device)
         with torch.amp.autocast(device_type="cuda", enabled=scaler is not None):
-            loss = criterion(model(image), target, loss_weight=loss_weight, num_classes=num_classes, dice=dice,
-                             ignore_index=ignore_index, focal_gamma=focal_gamma, tversky=tversky)
+            if boundary_weight == 0:
+                loss = criterion(model(image), target, loss_weight=loss_weight, num_classes=num_classes, dice=dice,
+                                 ignore_index=ignore_index, focal_gamma=focal_gamma, tversky=tversky)
+            else:
+                loss = boundary_criterion(model(image), target, loss_weight=loss_weight, num_classes=num_classes,
+                                          dice=dice, ignore_index=ignore_index, focal_gamma=focal_gamma,
+                                          tversky=tversky, boundary_weight=boundary_weight)
         optimizer.zero_grad()
         grad_norm = None
         if scaler is not None:

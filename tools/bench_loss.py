@@ -31,7 +31,16 @@ with us per launch, TB/s on the same byte model (fwd 4K+8, bwd 8K+8 bytes per pi
 
 --pair: the many-class (stf_loss_mc_*) or the focal / Tversky (stf_loss_ft_*, gamma = 2, (0.3, 0.7)) fwd + bwd pair
 of --base-lib's build and of this tree's on the same inputs (class weights, a W/8 band of 255), in turn inside each
-round.  One JSON line with every round's times, the medians, each build's own spread and new / base."""
+round.  One JSON line with every round's times, the medians, each build's own spread and new / base.
+
+    python tools/bench_loss.py --boundary [--base-lib PATH] [--out FILE]
+
+--boundary: the boundary loss at 64 x 2 x 256 x 256 and 16 x 2 x 512 x 512 on lesion-like targets (one ellipse
+of 0.5-2 % of the pixels per image, every eighth image empty), one JSON line per shape.  The map: stf_sdf
+against the route the build of --base-lib (default: this one) has to it, stf_edt_sq with where = ones twice per
+class (sites = G, sites = not G) on site masks made beforehand, the select / sqrt glue left out; in turn
+inside each round, with the base route's own spread.  The term: stf_bloss_fwd + stf_bloss_bwd, and the default
+criterion pair with and without them."""
 import argparse
 import ctypes
 import json
@@ -57,6 +66,7 @@ ap.add_argument("--channels", type=int, default=64)
 ap.add_argument("--focal", action="store_true", help="time the focal / Tversky pair against the option pair")
 ap.add_argument("--pair", choices=("mc", "ft"), default=None,
                 help="A/B of the many-class or the focal / Tversky pair against --base-lib's")
+ap.add_argument("--boundary", action="store_true", help="time the boundary loss's maps and term")
 args = ap.parse_args()
 
 N, K, H, W = (int(v) for v in args.shape.split(","))
@@ -217,6 +227,106 @@ def pair_ab(fam):
             "new_pair_us": {"median": mn, "min": min(tn), "spread": (max(tn) - min(tn)) / mn},
             "new_over_base": mn / mb}
 
+
+def lesion_targets(n, h, w, seed):
+    """One ellipse of 0.5-2 % of the pixels per image, anywhere inside it; every eighth image empty."""
+    g = torch.Generator().manual_seed(seed)
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+    t = torch.zeros(n, h, w, dtype=torch.long)
+    for i in range(n):
+        if i % 8 == 7:
+            continue
+        area = (0.005 + 0.015 * torch.rand(1, generator=g).item()) * h * w
+        ratio = 0.5 + torch.rand(1, generator=g).item()
+        a = (area / 3.141592653589793 * ratio) ** 0.5
+        b = area / 3.141592653589793 / a
+        cy = a + (h - 2 * a) * torch.rand(1, generator=g).item()
+        cx = b + (w - 2 * b) * torch.rand(1, generator=g).item()
+        t[i] = ((((ys - cy) / a) ** 2 + ((xs - cx) / b) ** 2) <= 1).long()
+    return t
+
+
+def boundary_leg(n, k, h, w):
+    from stfunet import _lib as L
+    t = lesion_targets(n, h, w, 7 * h + n).to(dev)
+    gen = torch.Generator(device=dev).manual_seed(h)
+    x = torch.randn(n, k, h, w, device=dev, generator=gen) * 2
+    phi = torch.empty(n, k - 1, h, w, device=dev)
+    scr = torch.empty((lib.stf_sdf_scratch_bytes(n, h, w, k) + 7) // 8, dtype=torch.int64, device=dev)
+    sites = [(t == c).to(torch.uint8) for c in range(1, k)]
+    sites += [1 - m for m in sites]
+    ones = torch.ones(n, h, w, dtype=torch.uint8, device=dev)
+    d2 = torch.empty(n, h, w, dtype=torch.int32, device=dev)
+    for name in ("stf_boundary_scratch_bytes", "stf_edt_sq"):
+        getattr(base, name).restype, getattr(base, name).argtypes = L._SIGS[name]
+    escr = torch.empty((base.stf_boundary_scratch_bytes(n, h, w) + 7) // 8, dtype=torch.int64, device=dev)
+    trm = torch.empty(lib.stf_loss_scratch_floats(n, k), device=dev)
+    part = torch.empty(lib.stf_bloss_scratch_floats(n), device=dev)
+    out1, one, dx = torch.zeros(1, device=dev), torch.ones(1, device=dev), torch.zeros_like(x)
+
+    def chk(rc):
+        if rc != 0:
+            raise RuntimeError(f"launch failed: {rc}")
+
+    def sdf():
+        chk(lib.stf_sdf(_p(t), n, h, w, k, -1, _p(phi), _p(scr), stream()))
+
+    def edt_route():
+        for m in sites:
+            chk(base.stf_edt_sq(_p(m), _p(ones), n, h, w, _p(d2), _p(escr), stream()))
+
+    def term():
+        chk(lib.stf_bloss_fwd(_p(x), _p(t), _p(phi), n, h, w, k, -100, 0.01, _p(part), _p(out1), stream()))
+        chk(lib.stf_bloss_bwd(_p(x), _p(t), _p(phi), n, h, w, k, -100, 0.01, _p(one), _p(part) + 4, _p(dx), stream()))
+
+    def crit():
+        chk(base.stf_loss_fwd(_p(x), _p(t), n, h, w, k, _p(trm), _p(out1), stream()))
+        chk(base.stf_loss_bwd(_p(x), _p(t), n, h, w, k, _p(trm), _p(one), _p(dx), stream()))
+
+    def crit_boundary():
+        chk(lib.stf_loss_fwd(_p(x), _p(t), n, h, w, k, _p(trm), _p(out1), stream()))
+        sdf()
+        chk(lib.stf_bloss_fwd(_p(x), _p(t), _p(phi), n, h, w, k, -100, 0.01, _p(part), _p(out1), stream()))
+        chk(lib.stf_loss_bwd(_p(x), _p(t), n, h, w, k, _p(trm), _p(one), _p(dx), stream()))
+        chk(lib.stf_bloss_bwd(_p(x), _p(t), _p(phi), n, h, w, k, -100, 0.01, _p(one), _p(part) + 4, _p(dx), stream()))
+
+    def timeit(fn, reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / reps * 1e3
+
+    fns = {"sdf_us": sdf, "edt_route_us": edt_route, "term_pair_us": term, "criterion_us": crit,
+           "criterion_boundary_us": crit_boundary}
+    reps = max(1, args.reps // 5)
+    for fn in fns.values():
+        timeit(fn, 3)
+    rounds = {key: [] for key in fns}
+    for _ in range(args.rounds):
+        for key, fn in fns.items():
+            rounds[key].append(timeit(fn, reps))
+    res = {"shape": [n, k, h, w], "reps": reps, "rounds": args.rounds, "base_lib": args.base_lib or "in-tree",
+           "build": L.build_info(), "foreground_fraction": (t > 0).float().mean().item()}
+    for key, v in rounds.items():
+        med = statistics.median(v)
+        res[key] = {"median": med, "min": min(v), "spread": (max(v) - min(v)) / med, "rounds": v}
+    res["sdf_over_edt_route"] = res["sdf_us"]["median"] / res["edt_route_us"]["median"]
+    res["sdf_ns_per_pixel"] = res["sdf_us"]["median"] * 1e3 / (n * h * w)
+    res["boundary_added_us"] = res["criterion_boundary_us"]["median"] - res["criterion_us"]["median"]
+    return res
+
+
+if args.boundary:
+    lines = [json.dumps(boundary_leg(*shape)) for shape in ((64, 2, 256, 256), (16, 2, 512, 512))]
+    print("\n".join(lines))
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    sys.exit(0)
 
 if args.pair:
     if not args.base_lib:
