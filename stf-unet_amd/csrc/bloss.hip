@@ -9,11 +9,13 @@
 //   phi = 0 everywhere when G is empty or is the whole image.
 // d2 is an exact int32 (g <= 4095, |dy| <= 4095, d2 < 2^25) and the stored value is one double square
 // root and one rounding to float.  Three launches:
-//   row      edt_rows.h's pass, one wave per (image, class, row): the row's G words by ballot, then g
-//            to the nearest G pixel (plane 0) and to the nearest pixel outside G (plane 1) from the
-//            same words, and the per-(image, class) count of G pixels (integer atomics).
-//   column   Meijster's two-scan lower envelope, one lane per (image, class, side, column), adjacent
-//            lanes on adjacent columns so the g reads coalesce.  The envelope's stack holds (s, t) as
+//   row      edt_rows.h's row words (shared with boundary.hip), one wave per (image,
+//            class, row): the words of G and of its complement from one read of the row, g to the
+//            nearest pixel of each (planes 0 and 1), and the per-(image, class) count of G pixels
+//            (integer atomics).  The scratch is laid out by edt_rows.h's carver.
+//   column   not boundary.hip's outward scan, whose cost follows the distance found: a dense map needs
+//            every pixel, so Meijster's two-scan lower envelope, one lane per (image, class, side,
+//            column), adjacent lanes on adjacent columns so the g reads coalesce.  The envelope's stack holds (s, t) as
 //            one uint32 per slot, laid out [slot][column]: the lanes' pushes and pops coalesce as well.
 //            Sep(i, u) = (u^2 - i^2 + g(u)^2 - g(i)^2) div (2 (u - i)) stays in int32 and is never
 //            negative where it is used; rows with G_NONE are skipped, never squared.  The cost is
@@ -49,8 +51,6 @@ constexpr int NT = 256;                 // threads per workgroup of the term's k
 constexpr int LCHUNK = 64;              // partial chunks per image, as loss.hip
 constexpr int UB = 8;                   // rows whose g a lane loads ahead of the envelope's updates
 
-inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 // ---------------------------------------------------------------- the maps
 // rows = N * (K-1) * H; row r = ((n (K-1) + k - 1) H + y).  gIn / gOut [N (K-1)][H][W]; counts [N (K-1)]
 // += |G| of the row, zeroed by the caller.
@@ -63,21 +63,14 @@ __global__ __launch_bounds__(BT) void sdf_rows_kernel(const int64_t* __restrict_
   const long ic = r / H, n = ic / KM1;
   const int y = (int)(r - ic * H), k = (int)(ic - n * KM1) + 1;
   const int64_t* trow = target + (n * H + y) * (long)W;
-  const int nw = (W + 63) >> 6;
-  u64 in = 0, out = 0;
-  for (int c = 0; c < nw; ++c) {
-    const int x = c * 64 + lane;
-    bool g = false;
-    if (x < W) {
-      const long tv = trow[x];
-      g = tv == k && !(ignore >= 0 && tv == ignore);
-    }
-    const u64 wi = __ballot(g), wo = __ballot(x < W && !g);
-    if (lane == c) { in = wi; out = wo; }
-  }
-  stf::store_row_g(in, lane, W, gIn + r * (long)W);
-  stf::store_row_g(out, lane, W, gOut + r * (long)W);
-  const int cnt = stf::wave_sum_i(__builtin_popcountll(in));
+  u64 w[2];                                                         // G and its complement inside the row
+  stf::row_words<2>(W, lane, [&](int x) {
+    const long tv = trow[x];
+    return tv == k && !(ignore >= 0 && tv == ignore) ? 1u : 2u;
+  }, w);
+  stf::store_row_g(w[0], lane, W, gIn + r * (long)W);
+  stf::store_row_g(w[1], lane, W, gOut + r * (long)W);
+  const int cnt = stf::row_count(w[0]);
   if (lane == 0 && cnt) atomicAdd(&counts[ic], (u64)cnt);
 }
 
@@ -186,17 +179,14 @@ struct SdfScratch {
   uint16_t* g;
   size_t bytes;
 };
-inline SdfScratch sdf_carve(void* scratch, int N, int H, int W, int classes) {
-  const size_t n = (size_t)N * (classes - 1) * H * W;
-  const size_t o_stack = round_up((size_t)N * (classes - 1) * sizeof(u64), 256);
-  const size_t o_g = o_stack + n * 2 * sizeof(uint32_t);
-  SdfScratch s = {nullptr, nullptr, nullptr, round_up(o_g + n * 2 * sizeof(uint16_t), 8)};
-  if (scratch) {                                                    // NULL: the size query
-    char* p = (char*)scratch;
-    s.counts = (u64*)p;
-    s.stack = (uint32_t*)(p + o_stack);
-    s.g = (uint16_t*)(p + o_g);
-  }
+inline SdfScratch sdf_carve(void* scratch, int N, int H, int W, int classes) {    // NULL: the size query
+  const size_t ics = (size_t)N * (classes - 1), n = ics * H * W;
+  stf::Carver c{(char*)scratch};
+  SdfScratch s;
+  s.counts = c.take<u64>(ics, 256);
+  s.stack = c.take<uint32_t>(n * 2);
+  s.g = c.take<uint16_t>(n * 2);
+  s.bytes = c.bytes();
   return s;
 }
 
@@ -348,6 +338,7 @@ extern "C" int stf_bloss_fwd(const float* logits, const int64_t* target, const f
   float* part = partials + 2;
   BLOSS_KPDISPATCH(classes, hipLaunchKernelGGL((bloss_fwd_kernel<KP>), dim3(LCHUNK, N), dim3(NT), 0, s, logits, target,
                                                phi, H * W, classes, ignore, part));
+  STF_CHECK_LAUNCH();
   hipLaunchKernelGGL(bloss_finalize_kernel, dim3(1), dim3(NT), 0, s, (const float*)part, N * LCHUNK, classes, alpha,
                      partials, loss);
   STF_CHECK_LAUNCH();

@@ -3,23 +3,23 @@
 // assd define them at unit spacing, and the exact squared Euclidean
 // distance transform they are built on.
 //
+// The row words, the outward scan and the scratch carver are edt_rows.h's, shared with bloss.hip; the
+// rank select and the end of the fold are written once below, for images and volumes.
 // Three passes, all integer except the final square roots:
 //   row      one wave per image row.  The row (and, for the metrics, its two vertical neighbours)
-//            becomes 64-pixel bit words by ballot, lane c keeping word c (W <= 4096 = 64 words).
-//            Border = M & ~erode4(M) is bit arithmetic on those words; g[y][x], the distance to the
-//            nearest border pixel of the same row, comes from clz / ctz inside the word and a
-//            max / min scan of the words' last / first bit across the lanes.  A row without a
-//            border pixel stores G_NONE, which the column pass branches on (never squared).
+//            becomes row words; border = M & ~erode4(M) is bit arithmetic on those words, and g[y][x]
+//            is the distance to the nearest border pixel of the same row.  A row without a border
+//            pixel stores G_NONE, which the column pass branches on (never squared).
 //   column   one lane per pixel, x along the lanes (coalesced g reads).  Only where the result is
-//            needed (the other mask's border, or `where`): d2 = min_y' g[y'][x]^2 + (y - y')^2 by
-//            scanning outward from y until (y - y')^2 >= best.  Exact in int32: g <= 4095,
-//            |y - y'| <= 4095, d2 < 2^25.  Cost per pixel is about the distance found, so masks that
-//            overlap cost O(1) and far-apart ones O(distance); an image without sites is answered
-//            from the row pass's count without a scan.  g is read from global memory (an image's g
-//            is 2 B per pixel and sits in L2); a column tile of 4096 rows does not fit the LDS.
-//   reduce   one workgroup per image over both directions' d2: the maximum, each direction's sum of
+//            needed (the other mask's border, or `where`): d2 = min_y' g[y'][x]^2 + (y - y')^2 by the
+//            outward scan from y with step (y - y')^2.  Exact in int32: g <= 4095, |y - y'| <= 4095,
+//            d2 < 2^25.  Cost per pixel is about the distance found, so masks that overlap cost O(1)
+//            and far-apart ones O(distance); an image without sites is answered from the row pass's
+//            count without a scan.  g is read from global memory (an image's g is 2 B per pixel and
+//            sits in L2); a column tile of 4096 rows does not fit the LDS.
+//   fold     one workgroup per image over both directions' d2: the maximum, each direction's sum of
 //            sqrt((double)d2), and the order statistics of the merged multiset at the two ranks of
-//            numpy's linear percentile by a 9 + 8 + 8 bit radix select on LDS histograms.
+//            numpy's linear percentile by the rank select in digits of 9 + 8 + 8 bits.
 //
 // Run-to-run identical bits: the counts and histograms are integer atomics (order-free); the fp64
 // sums are taken per lane in index order, then by xor shuffle, then over the waves in order.
@@ -35,21 +35,21 @@
 //            volume background), the counts are per volume, and every row with a border voxel marks
 //            its slice in has[z][side] and widens its volume's (y, x) bounding box box[v][side]
 //            (integer atomicMax on zeroed words).
-//   plane    the column scan in float64, min over y' of (sx g)^2 + (sy dy)^2, stored as the winning
-//            (g, dy) pair in one uint32 (the depth pass recomputes the same double from it: 4 bytes
+//   plane    the outward scan along y in float64, min over y' of (sx g)^2 + (sy dy)^2, stored as the
+//            winning (g, dy) pair in one uint32 (the depth pass recomputes the same double from it: 4 bytes
 //            per voxel and side, not 8).  Only in slices that have a site and, for the metrics,
 //            inside the querying border's bounding box: the depth pass reads nothing else.
 //   depth    only at the querying border voxels (or `where`): min over the slices z' of the volume
-//            that have a site of plane(z') + (sz dz)^2, outward from z until (sz dz)^2 >= best.
+//            that have a site of plane(z') + (sz dz)^2, the outward scan from z with step (sz dz)^2.
 //            The metrics' depth kernel works in units of 2048 consecutive voxels of one slice and
 //            side: it sums sqrt(d2) per thread in index order, per wave by xor shuffle and over the
 //            waves in order into one partial per unit, takes the unit's maximum, and appends d2
 //            to its volume's compact list through an integer cursor.
 //   fold     one workgroup per volume: the partials summed in unit order (units are placed by
 //            in-volume position, so a volume gives the same bits alone and in a stack), and the two
-//            order statistics by an 11-bit radix select over the compact list's uint64 bit
-//            patterns (non-negative doubles order as integers).  The list's order varies from run
-//            to run; only integer histograms and minima read it.
+//            order statistics by the same rank select, in digits of 11 bits (the last one 9), over
+//            the compact list's uint64 bit patterns (non-negative doubles order as integers).  The
+//            list's order varies from run to run; only integer histograms and minima read it.
 #include "common.h"
 #include "edt_rows.h"
 #include "volumes.h"
@@ -69,8 +69,8 @@ constexpr int D2_NONE = 0x7fffffff;
 using stf::G_NONE;
 using stf::X_NONE;
 using stf::store_row_g;
+using stf::row_count;
 using stf::u64;
-using stf::wave_sum_i;
 
 STF_DEV u64 shfl_up1(u64 v, int lane) {
   const u64 t = __shfl_up(v, 1, 64);
@@ -88,15 +88,6 @@ STF_DEV u64 border_word(u64 up, u64 mid, u64 down, u64 zz, int lane) {
   const u64 left = (mid << 1) | (shfl_up1(mid, lane) >> 63);        // bit i = pixel x - 1
   const u64 right = (mid >> 1) | (shfl_down1(mid, lane) << 63);     // bit i = pixel x + 1
   return mid & ~(up & down & left & right & zz);
-}
-
-STF_DEV int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
 }
 
 // The slices [z0, z1) of the volume v that slice z belongs to.  Images: {z, z, z + 1}.  Bounds do
@@ -119,26 +110,21 @@ STF_DEV Span span_of(const int* __restrict__ starts, int V, int N, int z) {
 // The prediction's and the target's words of the row that starts at element `base` (lane c keeps word c)
 STF_DEV void mask_words(const uint8_t* __restrict__ mask, const int64_t* __restrict__ target, long base, int W,
                         long ignore, int lane, u64& p, u64& t) {
-  const int nw = (W + 63) >> 6;
-  for (int c = 0; c < nw; ++c) {
-    const int x = c * 64 + lane;
-    bool fp = false, ft = false;
-    if (x < W) {
-      const long tv = target[base + x];
-      const bool keep = !(ignore >= 0 && tv == ignore);
-      fp = keep && mask[base + x] != 0;
-      ft = keep && tv > 0;
-    }
-    const u64 wp = __ballot(fp), wt = __ballot(ft);
-    if (lane == c) { p = wp; t = wt; }
-  }
+  u64 w[2];
+  stf::row_words<2>(W, lane, [&](int x) {
+    const long tv = target[base + x];
+    const bool keep = !(ignore >= 0 && tv == ignore);
+    return (unsigned)(keep && mask[base + x] != 0) | (unsigned)(keep && tv > 0) << 1;
+  }, w);
+  p = w[0];
+  t = w[1];
 }
 
 // Volumes: a row with border voxels marks its slice and widens its volume's bounding box.  box
 // [4] = max of (y + 1, MAXDIM - y, x + 1, MAXDIM - x) over the border voxels, 0 = none yet.
 STF_DEV void mark_row(u64 bw, int lane, int y, int* __restrict__ has, int* __restrict__ box) {
-  const int xhi = wave_max_i(bw ? lane * 64 + 64 - __builtin_clzll(bw) : 0);
-  const int xlo = wave_max_i(bw ? MAXDIM - (lane * 64 + __builtin_ctzll(bw)) : 0);
+  const int xhi = wave_max(bw ? lane * 64 + 64 - __builtin_clzll(bw) : 0);
+  const int xlo = wave_max(bw ? MAXDIM - (lane * 64 + __builtin_ctzll(bw)) : 0);
   if (lane == 0) {
     *has = 1;
     atomicMax(box, y + 1);
@@ -184,7 +170,7 @@ __global__ __launch_bounds__(BT) void boundary_rows_kernel(const uint8_t* __rest
   const u64 bp = border_word(p[0], p[1], p[2], zp, lane), bt = border_word(t[0], t[1], t[2], zt, lane);
   store_row_g(bp, lane, W, gP + r * (long)W);
   store_row_g(bt, lane, W, gT + r * (long)W);
-  const int np = wave_sum_i(__builtin_popcountll(bp)), nt = wave_sum_i(__builtin_popcountll(bt));
+  const int np = row_count(bp), nt = row_count(bt);
   if (lane == 0 && np) atomicAdd(&counts[(long)sp.v * 2], (u64)np);
   if (lane == 1 && nt) atomicAdd(&counts[(long)sp.v * 2 + 1], (u64)nt);
   if constexpr (VOL) {
@@ -203,15 +189,9 @@ __global__ __launch_bounds__(BT) void edt_rows_kernel(const uint8_t* __restrict_
   const int lane = threadIdx.x & 63;
   const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
   if (r >= rows) return;
-  const int nw = (W + 63) >> 6;
-  u64 bw = 0;
-  for (int c = 0; c < nw; ++c) {
-    const int x = c * 64 + lane;
-    const u64 w = __ballot(x < W && sites[r * (long)W + x] != 0);
-    if (lane == c) bw = w;
-  }
+  const u64 bw = stf::row_words(W, lane, [&](int x) { return sites[r * (long)W + x] != 0; });
   store_row_g(bw, lane, W, g + r * (long)W);
-  const int n = wave_sum_i(__builtin_popcountll(bw));
+  const int n = row_count(bw);
   if constexpr (VOL) {
     const Span sp = span_of<true>(starts, V, N, (int)(r / H));
     if (lane == 0 && n) {
@@ -225,24 +205,11 @@ __global__ __launch_bounds__(BT) void edt_rows_kernel(const uint8_t* __restrict_
 
 // min over y' of g[y'][x]^2 + (y - y')^2 for one column (col = &g[0][x] of the image), outward from y
 STF_DEV int column_min(const uint16_t* __restrict__ col, int y, int H, int W) {
-  int best = D2_NONE;
-  unsigned v = col[(long)y * W];
-  if (v != G_NONE) best = (int)(v * v);
-  for (int d = 1; d < H; ++d) {
-    const int dd = d * d;
-    if (dd >= best) break;
-    const int ya = y - d, yb = y + d;
-    if (ya < 0 && yb >= H) break;
-    if (ya >= 0) {
-      v = col[(long)ya * W];
-      if (v != G_NONE) { const int s = (int)(v * v) + dd; best = s < best ? s : best; }
-    }
-    if (yb < H) {
-      v = col[(long)yb * W];
-      if (v != G_NONE) { const int s = (int)(v * v) + dd; best = s < best ? s : best; }
-    }
-  }
-  return best;
+  return stf::scan_outward(y, 0, H, D2_NONE, [](int d) { return d * d; },
+                           [&](int yy, int, int dd, int& best) {
+                             const unsigned v = col[(long)yy * W];
+                             if (v != G_NONE) { const int s = (int)(v * v) + dd; best = s < best ? s : best; }
+                           });
 }
 
 // Column pass of the metrics: d2P = squared distance of every dP pixel to dT, d2T the converse,
@@ -290,32 +257,15 @@ STF_DEV double plane_value(unsigned p, double sy, double sx) {
 // min over y' of (sx g[y'][x])^2 + (sy (y - y'))^2 for one column of one slice, outward from y; the
 // winning pair packed, PL_NONE when the column has no site
 STF_DEV unsigned plane_min(const uint16_t* __restrict__ col, int y, int H, int W, double sy, double sx) {
-  double best = __builtin_inf();
   unsigned pack = PL_NONE;
-  unsigned v = col[(long)y * W];
-  if (v != G_NONE) { pack = v << 16; best = plane_value(pack, sy, sx); }
-  for (int d = 1; d < H; ++d) {
-    const double e = sy * (double)d, ee = e * e;
-    if (ee >= best) break;
-    const int ya = y - d, yb = y + d;
-    if (ya < 0 && yb >= H) break;
-    if (ya >= 0) {
-      v = col[(long)ya * W];
-      if (v != G_NONE) {
-        const unsigned q = (v << 16) | (unsigned)d;
-        const double s = plane_value(q, sy, sx);
-        if (s < best) { best = s; pack = q; }
-      }
-    }
-    if (yb < H) {
-      v = col[(long)yb * W];
-      if (v != G_NONE) {
-        const unsigned q = (v << 16) | (unsigned)d;
-        const double s = plane_value(q, sy, sx);
-        if (s < best) { best = s; pack = q; }
-      }
-    }
-  }
+  stf::scan_outward(y, 0, H, __builtin_inf(), [&](int d) { const double e = sy * (double)d; return e * e; },
+                    [&](int yy, int d, double, double& best) {
+                      const unsigned v = col[(long)yy * W];
+                      if (v == G_NONE) return;
+                      const unsigned q = (v << 16) | (unsigned)d;
+                      const double s = plane_value(q, sy, sx);
+                      if (s < best) { best = s; pack = q; }
+                    });
   return pack;
 }
 
@@ -323,26 +273,14 @@ STF_DEV unsigned plane_min(const uint16_t* __restrict__ col, int y, int H, int W
 // at in-slice index j, outward from z; +inf when no such slice has a site in this column
 STF_DEV double depth_min(const unsigned* __restrict__ plane, const int* __restrict__ has, int z, int z0, int z1,
                          long j, long HW, double sz, double sy, double sx) {
-  double best = __builtin_inf();
-  if (has[(long)z * 2]) {
-    const unsigned p = plane[(long)z * HW + j];
-    if (p != PL_NONE) best = plane_value(p, sy, sx);
-  }
-  for (int d = 1;; ++d) {
-    const double e = sz * (double)d, ee = e * e;
-    if (ee >= best) break;
-    const int za = z - d, zb = z + d;
-    if (za < z0 && zb >= z1) break;
-    if (za >= z0 && has[(long)za * 2]) {
-      const unsigned p = plane[(long)za * HW + j];
-      if (p != PL_NONE) { const double s = plane_value(p, sy, sx) + ee; best = s < best ? s : best; }
-    }
-    if (zb < z1 && has[(long)zb * 2]) {
-      const unsigned p = plane[(long)zb * HW + j];
-      if (p != PL_NONE) { const double s = plane_value(p, sy, sx) + ee; best = s < best ? s : best; }
-    }
-  }
-  return best;
+  return stf::scan_outward(z, z0, z1, __builtin_inf(), [&](int d) { const double e = sz * (double)d; return e * e; },
+                           [&](int zz, int, double ee, double& best) {
+                             if (!has[(long)zz * 2]) return;
+                             const unsigned p = plane[(long)zz * HW + j];
+                             if (p == PL_NONE) return;
+                             const double s = plane_value(p, sy, sx) + ee;
+                             best = s < best ? s : best;
+                           });
 }
 
 // Plane pass of the metrics: plT where the depth pass of a dP voxel may read it (slices with a dT
@@ -451,11 +389,7 @@ __global__ __launch_bounds__(BT) void boundary3d_depth_kernel(const uint16_t* __
       }
     }
     s = wave_sum_d(s);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const double m = __shfl_xor(mx, o, 64);
-      mx = m > mx ? m : mx;
-    }
+    mx = wave_max(mx);
     if (lane == 0) { wsum[wv] = s; wmax[wv] = mx; }
     __syncthreads();
     if (tid == 0) {
@@ -471,18 +405,35 @@ __global__ __launch_bounds__(BT) void boundary3d_depth_kernel(const uint16_t* __
   }
 }
 
-// ---- per-image reduction
-struct Fold {
-  unsigned hist[512];
-  double dsum[2][RT / 64];
-  int imax[RT / 64];
-  long below;          // values below the selected prefix's range
-  int prefix;          // the selected value's high bits so far (in place)
-  long at_or_below;    // values <= the selected value (after the last digit)
+// ---- the fold: one workgroup of RT threads per image or volume
+// What a fold selects over: the key type, its digits from the top down, the key of a squared distance.
+struct ImageKeys {                          // d2 itself, 25 bits as 9 + 8 + 8
+  typedef int Key;
+  static constexpr int BITS = 25, DIGITS = 3, HIST_BITS = 9;
+  static constexpr Key NONE = D2_NONE;
+  STF_DEV static constexpr int digit_bits(int i) { return i == 0 ? 9 : 8; }
+  STF_DEV static double d2(Key k) { return (double)k; }
+};
+struct VolumeKeys {                         // the bit pattern of a non-negative double, 64 bits as 5 x 11 + 9
+  typedef u64 Key;
+  static constexpr int BITS = 64, DIGITS = 6, HIST_BITS = 11;
+  static constexpr Key NONE = ~0ull;
+  STF_DEV static constexpr int digit_bits(int i) { return i < 5 ? 11 : 9; }
+  STF_DEV static double d2(Key k) { return __longlong_as_double((long long)k); }
 };
 
-// Thread 0 picks the bin holding rank k among the values counted in hist (bins = 1 << bits wide at
-// `shift`), given `below` values under the prefix's range.
+template <typename Keys>
+struct Fold {
+  unsigned hist[1 << Keys::HIST_BITS];
+  double dsum[2][RT / 64];
+  double dmax[RT / 64];
+  long below;                   // keys below the selected prefix's range
+  typename Keys::Key prefix;    // the selected key's high digits so far (in place)
+  long at_or_below;             // keys <= the selected key (after the last digit)
+};
+
+// Thread 0 picks the bin holding rank k among the keys counted in hist (bins = 1 << bits wide at
+// `shift`), given `below` keys under the prefix's range.
 template <typename F>
 STF_DEV void pick_bin(F& f, long k, int bins, int shift) {
   if (threadIdx.x == 0) {
@@ -498,128 +449,122 @@ STF_DEV void pick_bin(F& f, long k, int bins, int shift) {
   }
 }
 
-__global__ __launch_bounds__(RT) void boundary_fold_kernel(const int* __restrict__ d2P, const int* __restrict__ d2T,
-                                                           const u64* __restrict__ counts, long HW,
-                                                           double* __restrict__ out) {
-  __shared__ Fold f;
-  const long b = blockIdx.x;
+// The rank select.  for_each_key(pass, f) calls f(key) for this thread's share of the keys, the same
+// multiset on every pass, in any order (only integer histograms and minima read it); pass counts from 0,
+// so a source may fold work of its own into its first visit.  Radix select from the top digit down: per
+// digit the histogram of the keys that share the prefix found so far, and thread 0's pick_bin.  slo = the
+// key of rank lo; shi = the key of rank hi (lo or lo + 1): slo again when rank hi is still at or below
+// slo's last duplicate, else the smallest key above slo.  All branches are block-uniform.
+template <typename Keys, typename Src>
+STF_DEV void select_ranks(Fold<Keys>& f, long lo, long hi, Src for_each_key, typename Keys::Key& slo,
+                          typename Keys::Key& shi) {
+  typedef typename Keys::Key Key;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const long cP = (long)counts[b * 2], cT = (long)counts[b * 2 + 1];
-  double* o = out + b * 3;
-  if (cP == 0 || cT == 0) {                                         // block-uniform
-    if (tid < 3) o[tid] = __builtin_nan("");
-    return;
+  if (tid == 0) { f.below = 0; f.prefix = 0; }
+  int top = Keys::BITS;
+#pragma unroll
+  for (int digit = 0; digit < Keys::DIGITS; ++digit) {
+    const int bits = Keys::digit_bits(digit), shift = top - bits;
+    __syncthreads();                                                // prefix is final, hist is free
+    const Key want = digit ? f.prefix >> top : 0;
+    for (int j = tid; j < (1 << bits); j += RT) f.hist[j] = 0;
+    __syncthreads();
+    for_each_key(digit, [&](Key k) {
+      if (digit == 0 || (k >> top) == want) atomicAdd(&f.hist[(k >> shift) & ((1u << bits) - 1)], 1u);
+    });
+    __syncthreads();
+    pick_bin(f, lo, 1 << bits, shift);
+    top = shift;
   }
-  const int* src[2] = {d2P + b * HW, d2T + b * HW};
-  const long n = cP + cT;
+  __syncthreads();
+  slo = shi = f.prefix;
+  if (hi >= f.at_or_below) {                                        // the next larger key
+    Key m = Keys::NONE;
+    for_each_key(Keys::DIGITS, [&](Key k) {
+      if (k > slo && k < m) m = k;
+    });
+    m = wave_min(m);
+    Key* wmin = (Key*)f.hist;                                       // hist is free again
+    if (lane == 0) wmin[wv] = m;
+    __syncthreads();
+    shi = wmin[0];
+    for (int w = 1; w < RT / 64; ++w) shi = wmin[w] < shi ? wmin[w] : shi;
+  }
+}
+
+// The end of both folds.  n keys (n >= 1), cP + cT of them unless the list was capped; this thread's
+// maximum mx and sums s[0] (the dP side) and s[1], which the source may still be adding to during its
+// first pass.  The ranks of numpy's linear percentile, the select, then the per-wave maxima and sums by xor
+// shuffle and over the waves in order, and o[0..2] = HD, HD95, ASSD as the definitions write them.
+template <typename Keys, typename M, typename Src>
+STF_DEV void fold_finish(Fold<Keys>& f, long n, long cP, long cT, M& mx, double (&s)[2], Src for_each_key,
+                         double* __restrict__ o) {
+  const int tid = threadIdx.x;
   const double r = 0.95 * (double)(n - 1);
   const long lo = (long)floor(r);
   const long hi = lo + 1 < n - 1 ? lo + 1 : n - 1;
-
-  // digit 0 (bits 24..16) with the maximum and the two sums of roots
-  for (int j = tid; j < 512; j += RT) f.hist[j] = 0;
-  if (tid == 0) { f.below = 0; f.prefix = 0; }
+  typename Keys::Key slo, shi;
+  select_ranks(f, lo, hi, for_each_key, slo, shi);
+  const double wm = (double)wave_max(mx), w0 = wave_sum_d(s[0]), w1 = wave_sum_d(s[1]);
+  if ((tid & 63) == 0) { f.dmax[tid >> 6] = wm; f.dsum[0][tid >> 6] = w0; f.dsum[1][tid >> 6] = w1; }
   __syncthreads();
-  int mx = 0;
-  double s[2] = {0.0, 0.0};
-#pragma unroll
-  for (int dir = 0; dir < 2; ++dir)
-    for (long i = tid; i < HW; i += RT) {
-      const int v = src[dir][i];
-      if (v < 0) continue;
-      mx = v > mx ? v : mx;
-      s[dir] += sqrt((double)v);
-      atomicAdd(&f.hist[v >> 16], 1u);
-    }
-#pragma unroll
-  for (int ofs = 32; ofs > 0; ofs >>= 1) {
-    const int m = __shfl_xor(mx, ofs, 64);
-    mx = m > mx ? m : mx;
-  }
-  s[0] = wave_sum_d(s[0]);
-  s[1] = wave_sum_d(s[1]);
-  if (lane == 0) { f.imax[wv] = mx; f.dsum[0][wv] = s[0]; f.dsum[1][wv] = s[1]; }
-  __syncthreads();
-  pick_bin(f, lo, 512, 16);
-  __syncthreads();
-
-  // digits 1 and 2 (bits 15..8, 7..0) among the values that share the prefix
-#pragma unroll
-  for (int shift = 8; shift >= 0; shift -= 8) {
-    const int want = f.prefix >> (shift + 8);
-    __syncthreads();                                                // everyone has read prefix and is done with hist
-    for (int j = tid; j < 256; j += RT) f.hist[j] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int dir = 0; dir < 2; ++dir)
-      for (long i = tid; i < HW; i += RT) {
-        const int v = src[dir][i];
-        if (v >= 0 && (v >> (shift + 8)) == want) atomicAdd(&f.hist[(v >> shift) & 255], 1u);
-      }
-    __syncthreads();
-    pick_bin(f, lo, 256, shift);
-    __syncthreads();
-  }
-  const int slo = f.prefix;
-  int shi = slo;
-  if (hi >= f.at_or_below) {                                        // block-uniform: the next larger value
-    int m = D2_NONE;
-#pragma unroll
-    for (int dir = 0; dir < 2; ++dir)
-      for (long i = tid; i < HW; i += RT) {
-        const int v = src[dir][i];
-        if (v > slo && v < m) m = v;
-      }
-#pragma unroll
-    for (int ofs = 32; ofs > 0; ofs >>= 1) {
-      const int t = __shfl_xor(m, ofs, 64);
-      m = t < m ? t : m;
-    }
-    __syncthreads();                                                // hist is free again
-    if (lane == 0) f.hist[wv] = (unsigned)m;
-    __syncthreads();
-    for (int w = 0; w < RT / 64; ++w) shi = w == 0 ? (int)f.hist[0] : ((int)f.hist[w] < shi ? (int)f.hist[w] : shi);
-  }
   if (tid != 0) return;
-  int m = 0;
-  double sp = 0.0, st = 0.0;
+  double m = 0.0, sp = 0.0, st = 0.0;
   for (int w = 0; w < RT / 64; ++w) {
-    m = f.imax[w] > m ? f.imax[w] : m;
+    m = f.dmax[w] > m ? f.dmax[w] : m;
     sp += f.dsum[0][w];
     st += f.dsum[1][w];
   }
-  const double a = sqrt((double)slo), c = sqrt((double)shi);
-  o[0] = sqrt((double)m);
+  const double a = sqrt(Keys::d2(slo)), c = sqrt(Keys::d2(shi));
+  o[0] = sqrt(m);
   o[1] = a + (c - a) * (r - (double)lo);
   o[2] = 0.5 * (sp / (double)cP + st / (double)cT);
 }
 
-// ---- per-volume reduction
-struct FoldV {
-  unsigned hist[2048];
-  double dsum[2][RT / 64];
-  double dmax[RT / 64];
-  long below;
-  u64 prefix;          // the selected d2's bit pattern, high digits first
-  long at_or_below;
-};
+// Images: the keys are the entries >= 0 of d2P and d2T, each thread's strided by RT over HW; the maximum
+// and the two sums of roots are taken on the first pass, per thread in index order.
+__global__ __launch_bounds__(RT) void boundary_fold_kernel(const int* __restrict__ d2P, const int* __restrict__ d2T,
+                                                           const u64* __restrict__ counts, long HW,
+                                                           double* __restrict__ out) {
+  __shared__ Fold<ImageKeys> f;
+  const long b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const long cP = (long)counts[b * 2], cT = (long)counts[b * 2 + 1];
+  if (cP == 0 || cT == 0) {                                         // block-uniform
+    if (tid < 3) out[b * 3 + tid] = __builtin_nan("");
+    return;
+  }
+  const int* src[2] = {d2P + b * HW, d2T + b * HW};
+  int mx = 0;
+  double s[2] = {0.0, 0.0};
+  fold_finish(f, cP + cT, cP, cT, mx, s, [&](int pass, auto visit) {
+#pragma unroll
+    for (int dir = 0; dir < 2; ++dir)
+      for (long i = tid; i < HW; i += RT) {
+        const int v = src[dir][i];
+        if (v < 0) continue;
+        if (pass == 0) {
+          mx = v > mx ? v : mx;
+          s[dir] += sqrt((double)v);
+        }
+        visit(v);
+      }
+  }, out + b * 3);
+}
 
-// One workgroup per volume: the units' partials in unit order (per thread in index order, xor
-// shuffle, waves in order), then the same select as boundary_fold_kernel on the compact list's
-// uint64 keys, in digits of 11 bits (the last one 9).
+// Volumes: the units' partials in unit order (per thread in index order), the keys the compact list's.
 __global__ __launch_bounds__(RT) void boundary3d_fold_kernel(const double* __restrict__ psum,
                                                              const double* __restrict__ pmax,
                                                              const u64* __restrict__ comp,
                                                              const u64* __restrict__ counts,
                                                              const int* __restrict__ starts, int N, int nch,
                                                              long HW, double* __restrict__ out) {
-  __shared__ FoldV f;
+  __shared__ Fold<VolumeKeys> f;
   const long b = blockIdx.x;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int tid = threadIdx.x;
   const long cP = (long)counts[b * 2], cT = (long)counts[b * 2 + 1];
-  double* o = out + b * 3;
   if (cP == 0 || cT == 0) {                                         // block-uniform
-    if (tid < 3) o[tid] = __builtin_nan("");
+    if (tid < 3) out[b * 3 + tid] = __builtin_nan("");
     return;
   }
   int z0 = starts[b], z1 = starts[b + 1];                           // inside [0, N] whatever the table holds
@@ -628,74 +573,15 @@ __global__ __launch_bounds__(RT) void boundary3d_fold_kernel(const double* __res
   const u64* list = comp + 2 * (long)z0 * HW;
   const long cap = 2 * (long)(z1 - z0) * HW;
   const long n = cP + cT < cap ? cP + cT : cap;
-  const double r = 0.95 * (double)(n - 1);
-  const long lo = (long)floor(r);
-  const long hi = lo + 1 < n - 1 ? lo + 1 : n - 1;
-
   double mx = 0.0, s[2] = {0.0, 0.0};
   for (long u = (long)z0 * nch * 2 + tid; u < (long)z1 * nch * 2; u += RT) {    // RT is even: a thread keeps its side
     s[u & 1] += psum[u];
     mx = pmax[u] > mx ? pmax[u] : mx;
   }
-#pragma unroll
-  for (int ofs = 32; ofs > 0; ofs >>= 1) {
-    const double m = __shfl_xor(mx, ofs, 64);
-    mx = m > mx ? m : mx;
-  }
-  s[0] = wave_sum_d(s[0]);
-  s[1] = wave_sum_d(s[1]);
-  if (lane == 0) { f.dmax[wv] = mx; f.dsum[0][wv] = s[0]; f.dsum[1][wv] = s[1]; }
-  if (tid == 0) { f.below = 0; f.prefix = 0; }
-
-  int top = 64;
-  for (int digit = 0; digit < 6; ++digit) {
-    const int bits = digit < 5 ? 11 : 9, shift = top - bits;
-    __syncthreads();                                                // prefix is final, hist is free
-    const u64 want = top < 64 ? f.prefix >> top : 0;
-    for (int j = tid; j < 2048; j += RT) f.hist[j] = 0;
-    __syncthreads();
-    for (long i = tid; i < n; i += RT) {
-      const u64 k = list[i];
-      if (top == 64 || (k >> top) == want) atomicAdd(&f.hist[(k >> shift) & ((1u << bits) - 1)], 1u);
-    }
-    __syncthreads();
-    pick_bin(f, lo, 1 << bits, shift);
-    top = shift;
-  }
-  __syncthreads();
-  const u64 slo = f.prefix;
-  u64 shi = slo;
-  if (hi >= f.at_or_below) {                                        // block-uniform: the next larger value
-    u64 m = ~0ull;
-    for (long i = tid; i < n; i += RT) {
-      const u64 k = list[i];
-      if (k > slo && k < m) m = k;
-    }
-#pragma unroll
-    for (int ofs = 32; ofs > 0; ofs >>= 1) {
-      const u64 t = __shfl_xor(m, ofs, 64);
-      m = t < m ? t : m;
-    }
-    u64* wmin = (u64*)f.hist;                                       // hist is free again
-    if (lane == 0) wmin[wv] = m;
-    __syncthreads();
-    shi = wmin[0];
-    for (int w = 1; w < RT / 64; ++w) shi = wmin[w] < shi ? wmin[w] : shi;
-  }
-  if (tid != 0) return;
-  double m = 0.0, sp = 0.0, st = 0.0;
-  for (int w = 0; w < RT / 64; ++w) {
-    m = f.dmax[w] > m ? f.dmax[w] : m;
-    sp += f.dsum[0][w];
-    st += f.dsum[1][w];
-  }
-  const double a = sqrt(__longlong_as_double((long long)slo)), c = sqrt(__longlong_as_double((long long)shi));
-  o[0] = sqrt(m);
-  o[1] = a + (c - a) * (r - (double)lo);
-  o[2] = 0.5 * (sp / (double)cP + st / (double)cT);
+  fold_finish(f, n, cP, cT, mx, s, [&](int, auto visit) {
+    for (long i = tid; i < n; i += RT) visit(list[i]);
+  }, out + b * 3);
 }
-
-inline size_t round_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // B, H, W inside the limits and B * H * W < 2^31
 inline bool sizes_ok(int B, int H, int W) {
@@ -708,25 +594,23 @@ struct Scratch {
   u64* counts;
   int* d2;
   uint16_t* g;
+  size_t bytes;
 };
-inline Scratch carve(void* scratch, int B, long n) {
-  char* p = (char*)scratch;
+inline Scratch carve(void* scratch, int B, int H, int W) {           // NULL: the size query
+  const size_t n = (size_t)B * H * W;
+  stf::Carver c{(char*)scratch};
   Scratch s;
-  s.counts = (u64*)p;
-  p += round_up((size_t)B * 2 * sizeof(u64), 256);
-  s.d2 = (int*)p;
-  p += (size_t)n * 2 * sizeof(int);
-  s.g = (uint16_t*)p;
+  s.counts = c.take<u64>((size_t)B * 2, 256);
+  s.d2 = c.take<int>(n * 2);
+  s.g = c.take<uint16_t>(n * 2);
+  s.bytes = c.bytes();
   return s;
 }
 
 }  // namespace
 
 extern "C" size_t stf_boundary_scratch_bytes(int B, int H, int W) {
-  if (!sizes_ok(B, H, W)) return 0;
-  const size_t n = (size_t)B * H * W;
-  // whole 8-byte words, so a caller that allocates words never comes out short
-  return round_up(round_up((size_t)B * 2 * sizeof(u64), 256) + n * 2 * sizeof(int) + n * 2 * sizeof(uint16_t), 8);
+  return sizes_ok(B, H, W) ? carve(nullptr, B, H, W).bytes : 0;
 }
 
 extern "C" int stf_boundary_metrics(const uint8_t* mask, const int64_t* target, int B, int H, int W, int64_t ignore,
@@ -736,7 +620,7 @@ extern "C" int stf_boundary_metrics(const uint8_t* mask, const int64_t* target, 
     return STF_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const long n = (long)B * H * W, rows = (long)B * H;
-  const Scratch sc = carve(scratch, B, n);
+  const Scratch sc = carve(scratch, B, H, W);
   uint16_t *gP = sc.g, *gT = sc.g + n;
   int *d2P = sc.d2, *d2T = sc.d2 + n;
   u64* cnt = (u64*)counts;
@@ -761,7 +645,7 @@ extern "C" int stf_edt_sq(const uint8_t* sites, const uint8_t* where, int B, int
   if (((uintptr_t)scratch & 7) || ((uintptr_t)d2 & 3)) return STF_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   const long n = (long)B * H * W, rows = (long)B * H;
-  const Scratch sc = carve(scratch, B, n);
+  const Scratch sc = carve(scratch, B, H, W);
   hipError_t e = stf::memset_async(sc.counts, 0, (size_t)B * sizeof(u64), s);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(edt_rows_kernel<false>, dim3((unsigned)((rows + BT / 64 - 1) / (BT / 64))), dim3(BT), 0, s, sites,
@@ -789,26 +673,20 @@ struct Scratch3 {
   uint16_t* g;
   size_t int_bytes, bytes;
 };
-inline Scratch3 carve3(void* scratch, int N, int H, int W, int V) {
+inline Scratch3 carve3(void* scratch, int N, int H, int W, int V) {   // NULL: the size query
   const size_t n = (size_t)N * H * W;
   const size_t units = (size_t)N * (((size_t)H * W + CH - 1) / CH) * 2;
-  Scratch3 s = {};
-  s.int_bytes = ((size_t)N * 2 + (size_t)V * 9) * sizeof(int);
-  const size_t o_part = round_up((size_t)V * 2 * sizeof(u64), 256);
-  const size_t o_comp = o_part + round_up(units * 2 * sizeof(double), 256);
-  const size_t o_plane = o_comp + n * 2 * sizeof(u64);
-  const size_t o_ints = o_plane + n * 2 * sizeof(unsigned);
-  const size_t o_g = o_ints + round_up(s.int_bytes, 256);
-  s.bytes = round_up(o_g + n * 2 * sizeof(uint16_t), 8);
-  if (scratch) {                                                    // NULL: the size query
-    char* p = (char*)scratch;
-    s.counts = (u64*)p;
-    s.part = (double*)(p + o_part);
-    s.comp = (u64*)(p + o_comp);
-    s.plane = (unsigned*)(p + o_plane);
-    s.ints = (int*)(p + o_ints);
-    s.g = (uint16_t*)(p + o_g);
-  }
+  const size_t ints = (size_t)N * 2 + (size_t)V * 9;
+  stf::Carver c{(char*)scratch};
+  Scratch3 s;
+  s.counts = c.take<u64>((size_t)V * 2, 256);
+  s.part = c.take<double>(units * 2, 256);
+  s.comp = c.take<u64>(n * 2);
+  s.plane = c.take<unsigned>(n * 2);
+  s.ints = c.take<int>(ints, 256);
+  s.g = c.take<uint16_t>(n * 2);
+  s.int_bytes = ints * sizeof(int);
+  s.bytes = c.bytes();
   return s;
 }
 

@@ -150,20 +150,7 @@ STF_DEV void unite(int* L, int a, int b) {
   }
 }
 
-STF_DEV int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-STF_DEV u64 wave_max(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const u64 t = __shfl_xor(v, o, 64);
-    v = t > v ? t : v;
-  }
-  return v;
-}
+// wave_sum_i and wave_max: common.h
 
 // The keep-largest key: the largest area wins, ties go to the smaller root; 0 = no component
 // (areas are >= 1).

@@ -154,6 +154,32 @@ STF_DEV double wave_sum_d(double v) {
   return v;
 }
 
+STF_DEV int wave_sum_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// the wave's maximum / minimum on every lane (int, 64-bit unsigned, double)
+template <typename T>
+STF_DEV T wave_max(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const T t = __shfl_xor(v, o, 64);
+    v = t > v ? t : v;
+  }
+  return v;
+}
+template <typename T>
+STF_DEV T wave_min(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const T t = __shfl_xor(v, o, 64);
+    v = t < v ? t : v;
+  }
+  return v;
+}
+
 // ---------------------------------------------------------------- launch plans
 // Every launch of the library goes through stf::launch (hipLaunchKernelGGL is redefined
 // below), and every async memset / copy through stf::memset_async / memcpy_async.  While a

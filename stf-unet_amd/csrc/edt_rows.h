@@ -1,7 +1,12 @@
-// The row pass shared by the distance-transform kernels (boundary.hip, bloss.hip): one wave per
-// image row, the row's sites as 64-pixel bit words (lane c keeps word c, W <= 4096 = 64 words), and
-// g[x], the distance to the nearest site of the same row, from clz / ctz inside the word and a
-// max / min scan of the words' last / first bit across the lanes.
+// What the distance-transform kernels share (boundary.hip: image and volume metrics and transforms;
+// bloss.hip: the boundary loss's maps), each piece once:
+//   row words     one wave per image row, the row's sites as 64-pixel bit words by ballot (lane c keeps
+//                 word c, W <= 4096 = 64 words), and g[x], the distance to the nearest site of the same
+//                 row, from clz / ctz inside the word and a max / min scan of the words' last / first
+//                 bit across the lanes.
+//   outward scan  the minimum over the positions p of [lo, hi) of a candidate value(p) + step(|p - c|),
+//                 from the centre c outward.
+//   carver        a scratch layout written once, measured and handed out by the same sequence of takes.
 #pragma once
 #include "common.h"
 
@@ -11,6 +16,33 @@ typedef unsigned long long u64;
 
 constexpr unsigned G_NONE = 0xFFFFu;    // no site in this row
 constexpr int X_NONE = 1 << 20;         // "no site to the right" (> any x)
+
+// This lane's words of one row: pred(x), asked for x < W only, returns NB flags in its low bits and
+// out[k] becomes the word of flag k (bits at x >= W and words at or beyond (W + 63) / 64 are zero).
+template <int NB, typename P>
+STF_DEV void row_words(int W, int lane, P pred, u64 (&out)[NB]) {
+#pragma unroll
+  for (int k = 0; k < NB; ++k) out[k] = 0;
+  const int nw = (W + 63) >> 6;
+  for (int c = 0; c < nw; ++c) {
+    const int x = c * 64 + lane;
+    const unsigned f = x < W ? (unsigned)pred(x) : 0u;
+#pragma unroll
+    for (int k = 0; k < NB; ++k) {
+      const u64 w = __ballot((f >> k) & 1u);
+      if (lane == c) out[k] = w;
+    }
+  }
+}
+template <typename P>
+STF_DEV u64 row_words(int W, int lane, P pred) {
+  u64 w[1];
+  row_words<1>(W, lane, pred, w);
+  return w[0];
+}
+
+// the set bits of a row from its words, on every lane
+STF_DEV int row_count(u64 w) { return wave_sum_i(__builtin_popcountll(w)); }
 
 // g of one row from its site words (lane c holds word c): uint16 distance to the nearest set bit
 // of the row, G_NONE when the row has none.
@@ -42,10 +74,42 @@ STF_DEV void store_row_g(u64 bw, int lane, int W, uint16_t* __restrict__ grow) {
   }
 }
 
-STF_DEV int wave_sum_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
+// The outward scan.  probe(p, d, step(d), best) folds the candidate of position p, at distance d from
+// the centre, into best (and into whatever else the caller keeps of the winner); a candidate is never
+// below its step(d), and step does not decrease.  The centre is probed first, then c - d and c + d for
+// d = 1, 2, ... while they are inside [lo, hi).  Termination: once step(d) >= best no position at d or
+// beyond can be smaller than best, so the minimum is final; and d grows until both sides have left the
+// range, after which nothing is left to probe.  Returns the minimum, `none` if no probe found a
+// candidate.  All arithmetic is the caller's (int32 for images, float64 for volumes): T is only compared.
+template <typename T, typename Step, typename Probe>
+STF_DEV T scan_outward(int c, int lo, int hi, T none, Step step, Probe probe) {
+  T best = none;
+  probe(c, 0, T(0), best);
+  for (int d = 1;; ++d) {
+    const T cost = step(d);
+    if (cost >= best) break;
+    const int a = c - d, b = c + d;
+    if (a < lo && b >= hi) break;
+    if (a >= lo) probe(a, d, cost, best);
+    if (b < hi) probe(b, d, cost, best);
+  }
+  return best;
 }
+
+// A scratch layout is one sequence of take<T>(count, round) calls on a Carver: the block starts where
+// the last one ended and its size is rounded up to `round` bytes (every layout rounds so that each
+// block starts at a multiple of its element size from an 8-byte-aligned base).  With a NULL base the
+// same sequence only measures, so the size query and the pointers cannot drift apart.
+struct Carver {
+  char* base;
+  size_t at = 0;
+  template <typename T>
+  T* take(size_t count, size_t round = sizeof(T)) {
+    T* p = base ? (T*)(base + at) : nullptr;
+    at += (count * sizeof(T) + round - 1) / round * round;
+    return p;
+  }
+  size_t bytes() const { return (at + 7) / 8 * 8; }                 // whole 8-byte words
+};
 
 }  // namespace stf

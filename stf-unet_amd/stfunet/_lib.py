@@ -335,6 +335,15 @@ def call(name, *args):
         check(rc, name)
 
 
+MAX_SIDE = 4096     # the distance-transform kernels (boundary metrics, transforms, signed maps): 1 <= H, W <= 4096
+
+
+def scratch_words(nbytes, device):
+    """Scratch for an entry point that asked for ``nbytes`` (its ``*_scratch_bytes``): whole int64 words on
+    ``device``, so 8-byte aligned and never fewer bytes than asked for."""
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 

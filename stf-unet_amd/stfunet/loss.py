@@ -53,7 +53,7 @@ import torch
 
 from . import _lib
 from .nhwc import _p, check_num_classes
-from ._lib import call, stream
+from ._lib import MAX_SIDE, call, stream
 
 
 def _route(K, weight, ignore_index, dice, focal):
@@ -192,8 +192,7 @@ def _focal_tversky(focal_gamma, tversky, dice):
     return gamma, alpha, beta
 
 
-MAX_SIDE = 4096                  # signed_distance_maps: 1 <= H, W <= 4096
-MAX_MAP = 1 << 31                # ... and N * (K-1) * H * W below this
+MAX_MAP = 1 << 31                # signed_distance_maps: H, W <= MAX_SIDE and N * (K-1) * H * W below this
 
 
 def _boundary_weight(boundary_weight, num_classes):
@@ -251,8 +250,7 @@ def signed_distance_maps(target, num_classes, ignore_index=None):
     phi = torch.empty((N, K - 1, H, W), dtype=torch.float32, device=target.device)
     if N:
         target = target.detach().to(torch.int64).contiguous()
-        nbytes = _lib.load().stf_sdf_scratch_bytes(N, H, W, K)
-        scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=target.device)
+        scratch = _lib.scratch_words(_lib.load().stf_sdf_scratch_bytes(N, H, W, K), target.device)
         with torch.cuda.device(target.device):
             call("stf_sdf", _p(target), N, H, W, K, ignore, _p(phi), _p(scratch), stream())
     return phi

@@ -39,15 +39,14 @@ import os
 
 import torch
 
-from ._lib import call, load, stream
+from ._lib import MAX_SIDE, call, load, scratch_words, stream
 from .nhwc import _p
 
 RULES = {"argmax": 0, "sigmoid": 1, "threshold": 2}
 VIEWS = {"none": 0, "w": 1, "h": 2, "hw": 3}        # flip code: bit 0 = the last axis W, bit 1 = H
 ALL_VIEWS = ("none", "w", "h", "hw")
 MAX_CLASSES = 16
-MAX_SIDE = 4096                  # boundary metrics / distance transform: 1 <= H, W <= 4096
-MAX_PIXELS = 1 << 31             # ... and B * H * W below this
+MAX_PIXELS = 1 << 31             # boundary metrics / distance transform: H, W <= MAX_SIDE and B * H * W below this
 MAX_FULL_SCAN = 1 << 32          # distance_transform_sq without `where`: B * H * W * H at most this
 
 
@@ -166,9 +165,22 @@ def _check_spacing(spacing):
 
 
 def _boundary_scratch(B, H, W, device):
-    """The scratch of the boundary entry points: whole 8-byte words, never fewer bytes than they ask for."""
-    nbytes = load().stf_boundary_scratch_bytes(B, H, W)
-    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+    """The scratch of the image boundary entry points"""
+    return scratch_words(load().stf_boundary_scratch_bytes(B, H, W), device)
+
+
+def _checked_sites(sites, where, name):
+    """The transforms' checked ``sites`` and ``where`` (None stays None) of one shape: contiguous uint8 on
+    the sites' device."""
+    if where is not None and tuple(where.shape) != tuple(sites.shape):
+        raise ValueError(f"where {tuple(where.shape)} does not match the sites' {tuple(sites.shape)}")
+    sites = _as_u8(sites.detach(), "sites")
+    _device_only(sites, name)
+    if where is not None:
+        where = _as_u8(where.detach(), "where")
+        _device_only(where, name)
+        where = where.to(sites.device)
+    return sites, where
 
 
 def boundary_metrics(mask, target, ignore_index=None, spacing=1.0):
@@ -217,18 +229,11 @@ def distance_transform_sq(sites, where=None):
     1024 x 1024 image 2^30, one 2048 x 2048 image 2^33).  Passing ``where`` (all ones, if every pixel
     is wanted) lifts the guard: the caller then owns the cost."""
     B, H, W = _check_bhw(sites, "sites")
-    if where is not None and tuple(where.shape) != tuple(sites.shape):
-        raise ValueError(f"where {tuple(where.shape)} does not match the sites' {tuple(sites.shape)}")
     if where is None and B * H * W * H > MAX_FULL_SCAN:
         raise ValueError(f"distance_transform_sq without `where` may read B * H * W * H = {B * H * W * H} rows "
                          f"(more than {MAX_FULL_SCAN}) when the sites are sparse; pass `where` to name the pixels "
                          "that are needed, or all ones to accept the cost")
-    sites = _as_u8(sites.detach(), "sites")
-    _device_only(sites, "distance_transform_sq")
-    if where is not None:
-        where = _as_u8(where.detach(), "where")
-        _device_only(where, "distance_transform_sq")
-        where = where.to(sites.device)
+    sites, where = _checked_sites(sites, where, "distance_transform_sq")
     d2 = torch.empty((B, H, W), dtype=torch.int32, device=sites.device)
     if B:
         scratch = _boundary_scratch(B, H, W, sites.device)
@@ -295,14 +300,12 @@ def _ccl_call(op, mask, depths, before, after):
     dev = mask.device
     with torch.cuda.device(dev):
         if depths is None:
-            nbytes = load().stf_ccl_scratch_bytes(N, H, W)
-            scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+            scratch = scratch_words(load().stf_ccl_scratch_bytes(N, H, W), dev)
             call("stf_ccl_" + op, *before, N, H, W, *after, _p(scratch), stream())
         else:
             V = len(depths)
             host, starts = _starts(depths, dev)               # the call reads the host table before it returns
-            nbytes = load().stf_ccl3d_scratch_bytes(N, H, W, V)
-            scratch = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+            scratch = scratch_words(load().stf_ccl3d_scratch_bytes(N, H, W, V), dev)
             call("stf_ccl3d_" + op, *before, N, H, W, _p(starts), host.data_ptr(), V, *after, _p(scratch), stream())
 
 
@@ -461,11 +464,6 @@ def _check_spacing_3d(spacing, V):
     return rows
 
 
-def _boundary3d_scratch(N, H, W, V, device):
-    nbytes = load().stf_boundary3d_scratch_bytes(N, H, W, V)
-    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
-
-
 def _boundary3d(mask, target, depths, rows, ignore_index):
     """``stf_boundary3d_metrics`` on a checked uint8 device mask with checked ``depths`` and spacing
     ``rows``: (out float64 [V, 3], border counts int64 [V, 2])."""
@@ -477,7 +475,7 @@ def _boundary3d(mask, target, depths, rows, ignore_index):
         target = target.detach().to(device=dev, dtype=torch.int64).contiguous()
         host, starts = _starts(depths, dev)                   # the call reads the host table before it returns
         spacing = torch.tensor(rows, dtype=torch.float64).reshape(V, 3).to(dev)
-        scratch = _boundary3d_scratch(N, H, W, V, dev)
+        scratch = scratch_words(load().stf_boundary3d_scratch_bytes(N, H, W, V), dev)
         with torch.cuda.device(dev):
             call("stf_boundary3d_metrics", _p(mask), _p(target), N, H, W, _p(starts), host.data_ptr(), V, _p(spacing),
                  _ignore(ignore_index), _p(out), _p(counts), _p(scratch), stream())
@@ -523,8 +521,6 @@ def distance_transform_3d(sites, depths=None, spacing=1.0, where=None):
     whose bound ``N * H * W * (H + max(depths))`` exceeds ``MAX_FULL_SCAN`` is refused
     (``ValueError``); passing ``where`` (all ones, if every voxel is wanted) lifts the guard."""
     N, H, W = _check_bhw(sites, "sites")
-    if where is not None and tuple(where.shape) != tuple(sites.shape):
-        raise ValueError(f"where {tuple(where.shape)} does not match the sites' {tuple(sites.shape)}")
     depths = _check_depths(depths, N)
     rows = _check_spacing_3d(spacing, len(depths))
     bound = N * H * W * (H + max(depths, default=0))
@@ -532,18 +528,13 @@ def distance_transform_3d(sites, depths=None, spacing=1.0, where=None):
         raise ValueError(f"distance_transform_3d without `where` may read N * H * W * (H + depth) = {bound} values "
                          f"(more than {MAX_FULL_SCAN}) when the sites are sparse; pass `where` to name the voxels "
                          "that are needed, or all ones to accept the cost")
-    sites = _as_u8(sites.detach(), "sites")
-    _device_only(sites, "distance_transform_3d")
+    sites, where = _checked_sites(sites, where, "distance_transform_3d")
     dev, V = sites.device, len(depths)
-    if where is not None:
-        where = _as_u8(where.detach(), "where")
-        _device_only(where, "distance_transform_3d")
-        where = where.to(dev)
     d2 = torch.empty((N, H, W), dtype=torch.float64, device=dev)
     if N:
         host, starts = _starts(depths, dev)
         table = torch.tensor(rows, dtype=torch.float64).reshape(V, 3).to(dev)
-        scratch = _boundary3d_scratch(N, H, W, V, dev)
+        scratch = scratch_words(load().stf_boundary3d_scratch_bytes(N, H, W, V), dev)
         with torch.cuda.device(dev):
             call("stf_edt3d_sq", _p(sites), _p(where), N, H, W, _p(starts), host.data_ptr(), V, _p(table), _p(d2),
                  _p(scratch), stream())

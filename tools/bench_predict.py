@@ -400,7 +400,7 @@ if args.boundary3d:
         table = torch.tensor([spacing] * V, dtype=torch.float64, device=m.device)
         out = torch.empty(V, 3, dtype=torch.float64, device=m.device)
         cnt = torch.empty(V, 2, dtype=torch.int64, device=m.device)
-        scratch = P3._boundary3d_scratch(B, H, W, V, m.device)        # held while the plan replays
+        scratch = _lib.scratch_words(lib.stf_boundary3d_scratch_bytes(B, H, W, V), m.device)  # held while the plan replays
         plan = lib.stf_plan_create()
         assert lib.stf_plan_record(plan) == 0
         try:
