@@ -801,6 +801,41 @@ int stf_ccl3d_filter(const uint8_t* mask, const int64_t* target, int N, int H, i
                      int keep_largest, int64_t min_size, int64_t ignore_index, uint8_t* out, int64_t* counts,
                      int32_t* num, void* scratch, stf_stream_t stream);
 
+/* ---------------------------------------------------------------- lesion-level detection metrics
+ * How many target lesions were found and how many predicted components are false findings, per image
+ * or per volume (INTEGRATION.md 2.2 states the definition, DESIGN.md 5.19 the passes).
+ * P = (mask != 0) & (target != ignore_index), T = (target > 0) & (target != ignore_index); ignored
+ * voxels are background on BOTH sides before labelling (ignore_index < 0: none).  Each side is
+ * labelled on its own by the stf_ccl_* / stf_ccl3d_* code (connectivity 4 / 8 for images, 6 / 18 / 26
+ * for volumes, scipy's numbering).  A component of either side has an area (its voxels) and a hit
+ * (its voxels on the other side's foreground) and is MATCHED iff hit >= 1 and
+ * (double)hit >= min_overlap * (double)area.
+ *   summary int64 [V][4] = {n_T, matched_T, n_P, matched_P}  (images: V = B)
+ *   table   int64 [V][2][max_lesions][2]: side 0 the target, side 1 the prediction; row l - 1 holds
+ *           (area, hit) of label l, rows past n are 0, labels above max_lesions are left out (but
+ *           counted in summary, so n > max_lesions says the table was cut).  max_lesions = 0: no
+ *           table is written and table may be NULL.
+ * Additive to ABI v17.  Limits as for stf_ccl_* / stf_ccl3d_*.  STF_EINVAL (nothing launched) for a
+ * NULL mask, target, summary, scratch (or table with max_lesions > 0, or starts), a size outside the
+ * limits, a bad connectivity, a min_overlap outside [0, 1] or NaN, max_lesions < 0, a host starts
+ * that is not strictly ascending from 0 to N, a starts that is not 4-byte aligned, or a target,
+ * summary, table or scratch that is not 8-byte aligned (mask may sit at any byte).  No entry point
+ * allocates, reads back or waits between workgroups; the number of launches is fixed (images 6;
+ * volumes 8, 7 without a table); atomics are integer only, so the results are the same bits from run
+ * to run and for a volume passed alone or inside a stack.  All outputs are OVERWRITTEN and may arrive
+ * uninitialised, the scratch too.
+ *
+ * Bytes of the scratch either call needs, a multiple of 8 (0 outside the limits); V = B for images. */
+size_t stf_lesion_scratch_bytes(int N, int H, int W, int V);
+int stf_lesion_metrics(const uint8_t* mask, const int64_t* target, int B, int H, int W, int connectivity,
+                       double min_overlap, int max_lesions, int64_t ignore_index, int64_t* summary,
+                       int64_t* table, void* scratch, stf_stream_t stream);
+/* The same per volume; starts_dev / starts_host / V as stf_ccl3d_* take them. */
+int stf_lesion3d_metrics(const uint8_t* mask, const int64_t* target, int N, int H, int W,
+                         const int32_t* starts_dev, const int32_t* starts_host, int V, int connectivity,
+                         double min_overlap, int max_lesions, int64_t ignore_index, int64_t* summary,
+                         int64_t* table, void* scratch, stf_stream_t stream);
+
 /* ---------------------------------------------------------------- boundary metrics of volumes
  * Per-volume (per-case) HD, HD95 and ASSD with voxel spacing: MedPy's hd / hd95 / assd on a 3-D
  * array with voxelspacing = (sz, sy, sx) and connectivity 1 (INTEGRATION.md 2.2 states the

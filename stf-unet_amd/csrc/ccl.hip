@@ -657,7 +657,288 @@ int filter(const uint8_t* mask, const int64_t* target, int N, int H, int W, cons
   return 0;
 }
 
+// ---------------------------------------------------------------- lesion-level detection metrics
+// INTEGRATION.md 2.2 states the definition, DESIGN.md 5.19 the passes.  Both sides are labelled by the
+// passes above in one go: the two binary masks lie behind each other as one stack of 2 N slices,
+// target first, and are cut by a doubled table (volumes: starts2 int32 [2 V + 1], entry V + v =
+// N + starts[v]; images need none), so side s of volume v is volume s V + v of that stack and no
+// component spans two sides.  n = N H W voxels per side.
+
+// The two masks, the doubled table and the zeroed (area << 32 | hit) words of both sides.
+template <bool VOL>
+__global__ __launch_bounds__(BT) void lesion_form_kernel(const uint8_t* __restrict__ mask,
+                                                         const int64_t* __restrict__ target, long n, long ignore,
+                                                         const int* __restrict__ starts, int V, int N,
+                                                         uint8_t* __restrict__ bin, u64* __restrict__ acc,
+                                                         int* __restrict__ starts2) {
+  const long i = (long)blockIdx.x * BT + threadIdx.x;
+  if (VOL && blockIdx.x == 0)
+    for (int v = threadIdx.x; v <= 2 * V; v += BT) {                // either half inside its own side, whatever
+      const int z = v == V ? N : starts[v < V ? v : v - V];         // the device table holds
+      starts2[v] = (v > V ? N : 0) + (z < 0 ? 0 : z > N ? N : z);
+    }
+  if (i >= n) return;
+  const long tv = target[i];
+  const bool keep = !(ignore >= 0 && tv == ignore);
+  bin[i] = keep && tv > 0;
+  bin[n + i] = keep && mask[i] != 0;
+  acc[i] = 0;
+  acc[n + i] = 0;
+}
+
+// acc[root] += val for the run segments of one chunk (`first` marks a segment's first lane, which
+// holds the segment's root and val).  The segments of the chunk's first root are summed in the wave
+// and carried along the row (hot, hot_sum: wave-uniform) while the next chunk starts with the same
+// root, as ccl_compress_kernel<VOL, true> carries its areas; every other segment adds on its own.
+STF_DEV void add_segments(u64* acc, bool first, int root, u64 val, int lane, int& hot, u64& hot_sum) {
+  const u64 adds = __ballot(first);
+  if (!adds) return;                                                // wave-uniform
+  const int r0 = __shfl(root, __builtin_ctzll(adds), 64);
+  const bool same = first && root == r0;
+  u64 s = same ? val : 0ull;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (r0 != hot) {
+    if (lane == 0 && hot_sum) atomicAdd(&acc[hot], hot_sum);
+    hot = r0;
+    hot_sum = 0;
+  }
+  hot_sum += s;
+  if (first && !same) atomicAdd(&acc[root], val);
+}
+
+// One wave per row of the N H rows of one side, after compress (L [2 n] holds roots, -1 on the
+// background).  For either side, every run segment of a chunk adds (its length << 32) | (its voxels
+// on the other side's foreground) to the word of its root: area < 2^31 and hit <= area, so the two
+// halves never carry into each other.
+template <bool VOL>
+__global__ __launch_bounds__(BT) void lesion_overlap_kernel(const int* __restrict__ L, long n, long rows, int H, int W,
+                                                            const int* __restrict__ starts2, int V, u64* acc) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const int z = (int)(r / H), N = (int)(rows / H);
+  u64* accs[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) accs[s] = acc + (long)volume_of<VOL>(starts2, 2 * V, s * N + z).z0 * H * W;
+  const int nw = (W + 63) >> 6;
+  int hot[2] = {-1, -1};
+  u64 hot_sum[2] = {0ull, 0ull};
+  for (int c = 0; c < nw; ++c) {
+    const int x = c * 64 + lane;
+    const long i = r * (long)W + x;
+    int root[2];
+    u64 fg[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      root[s] = x < W ? L[s * n + i] : -1;
+      fg[s] = __ballot(root[s] >= 0);
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const u64 w = fg[s];
+      const bool first = root[s] >= 0 && (lane == 0 || !((w >> (lane - 1)) & 1));
+      const u64 t = ~(w >> lane);                                   // zero only for lane 0 of a full word
+      const int len = t ? __builtin_ctzll(t) : 64;
+      const u64 seg = (len == 64 ? ~0ull : (1ull << len) - 1) << lane;
+      const u64 val = ((u64)len << 32) | (u64)__builtin_popcountll(seg & fg[1 - s]);
+      add_segments(accs[s], first, root[s], val, lane, hot[s], hot_sum[s]);
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+    if (lane == 0 && hot_sum[s]) atomicAdd(&accs[s][hot[s]], hot_sum[s]);
+}
+
+// The matching rule, once per root: one double multiply and one compare.
+STF_DEV bool lesion_matched(u64 a, double min_overlap) {
+  const unsigned area = (unsigned)(a >> 32), hit = (unsigned)a;
+  return hit >= 1u && (double)hit >= min_overlap * (double)area;
+}
+
+// The raster walk of slice z of side blockIdx.y (grid N x 2).  Row rank - 1 of the side's table takes
+// (area, hit) of the root with that rank while rank <= max_lesions.
+//   images            the whole job: summary {n, matched} of the side, table rows, zeros past n.
+//   volumes, COUNT    cnt[z'] = roots of the slice, mat[z'] = matched roots (z' = side N + z).
+//   volumes, !COUNT   the table rows, the carry starting at cnt[z'], by then the roots of the volume's
+//                     earlier slices (lesion_volume_kernel).
+template <bool VOL, bool COUNT>
+__global__ __launch_bounds__(RT) void lesion_walk_kernel(const int* __restrict__ L, const u64* __restrict__ acc,
+                                                         int N, int HW, const int* __restrict__ starts2, int V,
+                                                         int* __restrict__ cnt, int* __restrict__ mat,
+                                                         double min_overlap, int max_lesions,
+                                                         int64_t* __restrict__ summary, int64_t* __restrict__ table) {
+  __shared__ int wmat[RT / 64];
+  const int side = blockIdx.y, z2 = side * N + (int)blockIdx.x;
+  const Vol vol2 = volume_of<VOL>(starts2, 2 * V, z2);
+  const int v = vol2.v - side * V;                                  // the volume in the caller's numbering
+  const u64* Av = acc + (long)vol2.z0 * HW;
+  int64_t* rowsT = table ? table + ((long)v * 2 + side) * max_lesions * 2 : nullptr;
+  int matched = 0;
+  const int n = root_walk(L + (long)z2 * HW, HW, (z2 - vol2.z0) * HW, VOL && !COUNT ? cnt[z2] : 0,
+                          [&](int p, int rank) {
+    const u64 a = Av[p];
+    if (!VOL || COUNT) matched += lesion_matched(a, min_overlap);
+    if ((!VOL || !COUNT) && rowsT && rank <= max_lesions) {
+      rowsT[(long)(rank - 1) * 2] = (int64_t)(a >> 32);
+      rowsT[(long)(rank - 1) * 2 + 1] = (int64_t)(a & 0xFFFFFFFFull);
+    }
+  });
+  if (VOL && !COUNT) return;
+  matched = wave_sum_i(matched);
+  if ((threadIdx.x & 63) == 0) wmat[threadIdx.x >> 6] = matched;
+  __syncthreads();
+  if (!VOL && rowsT)
+    for (long k = (long)n * 2 + threadIdx.x; k < (long)max_lesions * 2; k += RT) rowsT[k] = 0;
+  if (threadIdx.x != 0) return;
+  matched = 0;
+  for (int w = 0; w < RT / 64; ++w) matched += wmat[w];
+  if (VOL) {
+    cnt[z2] = n;
+    mat[z2] = matched;
+  } else {
+    summary[(long)v * 4 + side * 2] = n;
+    summary[(long)v * 4 + side * 2 + 1] = matched;
+  }
+}
+
+// One wave per volume of the doubled stack (grid 2 V) over its slices in order: cnt[z'] becomes the
+// roots of the volume's earlier slices; summary {n, matched} of the side; the table's rows past n = 0.
+__global__ __launch_bounds__(64) void lesion_volume_kernel(const int* __restrict__ starts2, int N, int V,
+                                                           int* __restrict__ cnt, const int* __restrict__ mat,
+                                                           int max_lesions, int64_t* __restrict__ summary,
+                                                           int64_t* __restrict__ table) {
+  const int lane = threadIdx.x, v2 = blockIdx.x;
+  const int side = v2 >= V, v = v2 - side * V;
+  int za = starts2[v2], zb = starts2[v2 + 1];
+  za = za < 0 ? 0 : za;
+  zb = zb > 2 * N ? 2 * N : zb;
+  int carry = 0, matched = 0;
+  for (int z0 = za; z0 < zb; z0 += 64) {
+    const int z = z0 + lane;
+    const int c = z < zb ? cnt[z] : 0;
+    int inc = c;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += t;
+    }
+    if (z < zb) {
+      cnt[z] = carry + inc - c;
+      matched += mat[z];
+    }
+    carry += __shfl(inc, 63, 64);
+  }
+  matched = wave_sum_i(matched);
+  if (table) {
+    int64_t* rowsT = table + ((long)v * 2 + side) * max_lesions * 2;
+    for (long k = (long)carry * 2 + lane; k < (long)max_lesions * 2; k += 64) rowsT[k] = 0;
+  }
+  if (lane != 0) return;
+  summary[(long)v * 4 + side * 2] = carry;
+  summary[(long)v * 4 + side * 2 + 1] = matched;
+}
+
+// scratch: [starts2 int32 [2 V + 1], 256-B rounded][roots per slice int32 [2 N], 256-B rounded]
+//          [matched roots per slice int32 [2 N], 256-B rounded]       (images leave these three unused)
+//          [(area << 32 | hit) u64 [2 n]][parents int32 [2 n]][the two masks uint8 [2 n]]
+// 26 bytes per voxel of the input.
+struct LesionScratch {
+  int* starts2;
+  int* cnt;
+  int* mat;
+  u64* acc;
+  int* L;
+  uint8_t* bin;
+};
+inline size_t lesion_scratch_bytes(int N, int H, int W, int V) {
+  if (!sizes_ok(N, H, W, V)) return 0;
+  const size_t head = round_up((2 * (size_t)V + 1) * sizeof(int), 256) + 2 * round_up((size_t)N * 2 * sizeof(int), 256);
+  return round_up(head + (size_t)N * H * W * 2 * (sizeof(u64) + sizeof(int) + 1), 8);
+}
+inline LesionScratch lesion_carve(void* scratch, int N, int V, long n) {
+  char* p = (char*)scratch;
+  LesionScratch s;
+  s.starts2 = (int*)p;
+  p += round_up((2 * (size_t)V + 1) * sizeof(int), 256);
+  s.cnt = (int*)p;
+  p += round_up((size_t)N * 2 * sizeof(int), 256);
+  s.mat = (int*)p;
+  p += round_up((size_t)N * 2 * sizeof(int), 256);
+  s.acc = (u64*)p;
+  s.L = (int*)(s.acc + 2 * n);
+  s.bin = (uint8_t*)(s.L + 2 * n);
+  return s;
+}
+
+// What the lesion entry points refuse on top of level_or_refuse (which sees the rest).
+inline bool lesion_args_ok(const void* target, double min_overlap, int max_lesions, const void* summary,
+                           const void* table) {
+  if (!target || !summary || max_lesions < 0 || (max_lesions > 0 && !table)) return false;
+  if (!(min_overlap >= 0.0 && min_overlap <= 1.0)) return false;    // NaN fails both
+  return !(((uintptr_t)target | (uintptr_t)summary | (uintptr_t)table) & 7);
+}
+
+template <bool VOL>
+int lesion(const uint8_t* mask, const int64_t* target, int N, int H, int W, const int32_t* starts_dev,
+           const int32_t* starts_host, int V, int connectivity, double min_overlap, int max_lesions,
+           int64_t ignore_index, int64_t* summary, int64_t* table, void* scratch, stf_stream_t stream) {
+  const int level = level_or_refuse<VOL>(mask, N, H, W, starts_dev, starts_host, V, connectivity, nullptr, scratch);
+  if (!level || !lesion_args_ok(target, min_overlap, max_lesions, summary, table)) return STF_EINVAL;
+  if (!max_lesions) table = nullptr;
+  hipStream_t s = (hipStream_t)stream;
+  const long n = (long)N * H * W, rows = (long)N * H;
+  const LesionScratch ls = lesion_carve(scratch, N, V, n);
+  hipLaunchKernelGGL(lesion_form_kernel<VOL>, dim3((unsigned)((n + BT - 1) / BT)), dim3(BT), 0, s, mask, target, n,
+                     (long)ignore_index, starts_dev, V, N, ls.bin, ls.acc, ls.starts2);
+  STF_CHECK_LAUNCH();
+  const Scratch sc = {nullptr, nullptr, nullptr, ls.L, nullptr};
+  const int rc = label_roots<VOL>(ls.bin, 2 * N, H, W, ls.starts2, 2 * V, level, sc, false, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(lesion_overlap_kernel<VOL>, dim3(row_grid(rows)), dim3(BT), 0, s, (const int*)ls.L, n, rows, H,
+                     W, (const int*)ls.starts2, V, ls.acc);
+  STF_CHECK_LAUNCH();
+  const dim3 slices((unsigned)N, 2);
+  if (!VOL) {
+    hipLaunchKernelGGL((lesion_walk_kernel<false, false>), slices, dim3(RT), 0, s, (const int*)ls.L,
+                       (const u64*)ls.acc, N, H * W, (const int*)nullptr, V, ls.cnt, ls.mat, min_overlap, max_lesions,
+                       summary, table);
+    STF_CHECK_LAUNCH();
+    return 0;
+  }
+  hipLaunchKernelGGL((lesion_walk_kernel<true, true>), slices, dim3(RT), 0, s, (const int*)ls.L, (const u64*)ls.acc,
+                     N, H * W, (const int*)ls.starts2, V, ls.cnt, ls.mat, min_overlap, max_lesions, summary, table);
+  STF_CHECK_LAUNCH();
+  hipLaunchKernelGGL(lesion_volume_kernel, dim3((unsigned)(2 * V)), dim3(64), 0, s, (const int*)ls.starts2, N, V,
+                     ls.cnt, (const int*)ls.mat, max_lesions, summary, table);
+  STF_CHECK_LAUNCH();
+  if (!table) return 0;
+  hipLaunchKernelGGL((lesion_walk_kernel<true, false>), slices, dim3(RT), 0, s, (const int*)ls.L, (const u64*)ls.acc,
+                     N, H * W, (const int*)ls.starts2, V, ls.cnt, ls.mat, min_overlap, max_lesions, summary, table);
+  STF_CHECK_LAUNCH();
+  return 0;
+}
+
 }  // namespace
+
+extern "C" size_t stf_lesion_scratch_bytes(int N, int H, int W, int V) {
+  return lesion_scratch_bytes(N, H, W, V);
+}
+
+extern "C" int stf_lesion_metrics(const uint8_t* mask, const int64_t* target, int B, int H, int W, int connectivity,
+                                  double min_overlap, int max_lesions, int64_t ignore_index, int64_t* summary,
+                                  int64_t* table, void* scratch, stf_stream_t stream) {
+  return lesion<false>(mask, target, B, H, W, nullptr, nullptr, B, connectivity, min_overlap, max_lesions,
+                       ignore_index, summary, table, scratch, stream);
+}
+
+extern "C" int stf_lesion3d_metrics(const uint8_t* mask, const int64_t* target, int N, int H, int W,
+                                    const int32_t* starts_dev, const int32_t* starts_host, int V, int connectivity,
+                                    double min_overlap, int max_lesions, int64_t ignore_index, int64_t* summary,
+                                    int64_t* table, void* scratch, stf_stream_t stream) {
+  return lesion<true>(mask, target, N, H, W, starts_dev, starts_host, V, connectivity, min_overlap, max_lesions,
+                      ignore_index, summary, table, scratch, stream);
+}
 
 extern "C" size_t stf_ccl_scratch_bytes(int B, int H, int W) { return scratch_bytes<false>(B, H, W, B); }
 

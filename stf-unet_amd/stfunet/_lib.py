@@ -204,6 +204,10 @@ _SIGS = {
     "stf_ccl3d_label": (c_int, [P, c_int, c_int, c_int, P, P, c_int, c_int, P, P, P, P]),
     "stf_ccl3d_filter": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, c_int, c_int, c_int64, c_int64, P, P, P, P,
                                  P]),
+    "stf_lesion_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "stf_lesion_metrics": (c_int, [P, P, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_int64, P, P, P, P]),
+    "stf_lesion3d_metrics": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, c_int, ctypes.c_double, c_int, c_int64,
+                                     P, P, P, P]),
     "stf_boundary3d_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stf_boundary3d_metrics": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, c_int64, P, P, P, P]),
     "stf_edt3d_sq": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, P, P, P]),

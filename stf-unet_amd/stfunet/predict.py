@@ -27,6 +27,11 @@ gfx950 kernels of ``csrc/predict.hip``:
   ``(sz, sy, sx)`` (MedPy on the 3-D array) and the weighted squared distance transform underneath
   (the volume kernels of ``csrc/boundary.hip``); ``predict_volumes(boundary=True)`` reports them per case
 
+* ``lesion_metrics`` / ``lesion_metrics_3d``  lesion-level detection per image / per volume: target lesions
+  found and missed, predicted components that are false findings, and the (area, hit) table of either
+  side (the lesion kernels of ``csrc/ccl.hip``); ``predict_volumes(lesions=True)`` and
+  ``predict_tta(lesions=True)`` report lesion-level sensitivity, precision and false findings
+
 ``predict(model, loader, device, rule="sigmoid", channel=0, paint=0)`` reproduces test.py bit for
 bit (it thresholds channel 0 and inverts the mask before painting, :75-76), except that the
 PNGs are RGB: channel ``c`` of an overlay takes ``color[c]``, where the reference hands the same
@@ -423,6 +428,102 @@ def _is_real(x):
     return isinstance(x, numbers.Real) and not isinstance(x, bool)
 
 
+MAX_LESIONS = 1 << 20            # rows of a lesion table: a limit on the argument, not on the counts
+
+
+def _check_lesions(min_overlap, max_lesions=0):
+    if not _is_real(min_overlap) or not 0.0 <= min_overlap <= 1.0:
+        raise ValueError(f"min_overlap must be a number in [0, 1], not {min_overlap!r}")
+    if isinstance(max_lesions, bool) or not isinstance(max_lesions, numbers.Integral) or \
+            not 0 <= max_lesions <= MAX_LESIONS:
+        raise ValueError(f"max_lesions must be an integer in 0..{MAX_LESIONS}, not {max_lesions!r}")
+    return float(min_overlap), int(max_lesions)
+
+
+def _lesions(mask, target, depths, connectivity, min_overlap, max_lesions, ignore_index):
+    """``stf_lesion_metrics`` / ``stf_lesion3d_metrics`` on a checked uint8 device mask: (summary int64
+    [V, 4], table int64 [V, 2, max_lesions, 2] or None), per image (``depths`` None) or per volume."""
+    N, H, W = mask.shape
+    dev = mask.device
+    V = N if depths is None else len(depths)
+    summary = torch.empty((V, 4), dtype=torch.int64, device=dev)
+    table = torch.empty((V, 2, max_lesions, 2), dtype=torch.int64, device=dev) if max_lesions else None
+    if N:
+        target = target.detach().to(device=dev, dtype=torch.int64).contiguous()
+        after = (connectivity, min_overlap, max_lesions, _ignore(ignore_index), _p(summary), _p(table))
+        with torch.cuda.device(dev):
+            scratch = scratch_words(load().stf_lesion_scratch_bytes(N, H, W, V), dev)
+            if depths is None:
+                call("stf_lesion_metrics", _p(mask), _p(target), N, H, W, *after, _p(scratch), stream())
+            else:
+                host, starts = _starts(depths, dev)           # the call reads the host table before it returns
+                call("stf_lesion3d_metrics", _p(mask), _p(target), N, H, W, _p(starts), host.data_ptr(), V, *after,
+                     _p(scratch), stream())
+    return summary, table
+
+
+def _lesion_result(summary, table):
+    """The dict of ``lesion_metrics``: the summary's columns and the two ratios, torch ops on the device."""
+    n_t, m_t, n_p, m_p = summary.unbind(1)
+    res = {"n_target": n_t, "matched_target": m_t, "n_pred": n_p, "matched_pred": m_p,
+           "sensitivity": m_t.to(torch.float64) / n_t.to(torch.float64),        # 0 / 0 = NaN
+           "precision": m_p.to(torch.float64) / n_p.to(torch.float64)}
+    if table is not None:
+        res["lesions"] = table
+    return res
+
+
+def lesion_metrics(mask, target, connectivity=8, min_overlap=0.0, max_lesions=64, ignore_index=None):
+    """Lesion-level detection metrics of ``mask`` against ``target``, per image (both ``[B, H, W]``;
+    ``mask`` bool, uint8 or any integer, nonzero = foreground; ``target`` any integer, > 0 = foreground;
+    pixels whose target equals ``ignore_index`` are background on both sides before labelling).
+
+    Either side is labelled on its own (``connected_components`` at ``connectivity``).  A target lesion
+    has an ``area`` and a ``hit`` (its pixels under the predicted foreground), a predicted component
+    likewise against the target foreground; either is matched iff ``hit >= 1`` and
+    ``float(hit) >= min_overlap * float(area)`` (``min_overlap`` in [0, 1]; 0: any overlap).
+
+    Returns a dict of device tensors: int64 ``[B]`` ``n_target``, ``matched_target`` (lesions found; the
+    rest were missed), ``n_pred``, ``matched_pred`` (the rest are false findings), float64
+    ``sensitivity = matched_target / n_target`` and ``precision = matched_pred / n_pred`` (NaN where the
+    denominator is 0) and, unless ``max_lesions`` is 0, ``lesions`` int64 ``[B, 2, max_lesions, 2]``: side
+    0 the target, side 1 the prediction, row ``l - 1`` = (area, hit) of label ``l``, zero past ``n``;
+    labels above ``max_lesions`` are left out of the table but still counted.  Integers only: the same
+    bits from run to run; no host synchronisation."""
+    _check_target_shape(target, mask.shape)
+    _check_bhw(mask, "mask")
+    connectivity, _ = _check_components(connectivity)
+    min_overlap, max_lesions = _check_lesions(min_overlap, max_lesions)
+    mask = _checked_mask(mask, target, "lesion_metrics")
+    return _lesion_result(*_lesions(mask, target, None, connectivity, min_overlap, max_lesions, ignore_index))
+
+
+def lesion_metrics_3d(mask, target, depths=None, connectivity=26, min_overlap=0.0, max_lesions=64,
+                      ignore_index=None):
+    """``lesion_metrics`` per volume (per case) instead of per image: ``mask`` and ``target`` are stacks
+    of slices ``[N, H, W]`` cut into ``V = len(depths)`` volumes as in ``connected_components_3d``
+    (connectivity 6, 18 or 26); every tensor of the result has ``V`` rows.  The same bits for a volume
+    passed alone or inside a stack."""
+    _check_target_shape(target, mask.shape)
+    N, H, W = _check_bhw(mask, "mask")
+    connectivity, _ = _check_components_3d(connectivity)
+    depths = _check_depths(depths, N)
+    min_overlap, max_lesions = _check_lesions(min_overlap, max_lesions)
+    mask = _checked_mask(mask, target, "lesion_metrics_3d")
+    return _lesion_result(*_lesions(mask, target, depths, connectivity, min_overlap, max_lesions, ignore_index))
+
+
+def _pooled_lesions(summaries, per):
+    """The lesion keys of the predict loops from the per-flush summaries (None without targets)."""
+    keys = ("lesion_counts", "lesion_sensitivity", "lesion_precision", "false_findings", "false_findings_per_" + per)
+    if not summaries:
+        return dict.fromkeys(keys)
+    counts = torch.cat(summaries)
+    tot = counts.sum(0).to(torch.float64)
+    false = counts[:, 2] - counts[:, 3]
+    return dict(zip(keys, (counts, tot[1] / tot[0], tot[3] / tot[2], false, false.to(torch.float64).mean())))
+
+
 def _check_spacing_3d(spacing, V):
     """``spacing`` of the volume calls as ``V`` rows ``[sz, sy, sx]`` of floats: a positive finite
     number (isotropic), one triple ``(sz, sy, sx)`` for every volume, or ``V`` triples (a sequence or
@@ -733,18 +834,31 @@ def _batches(model, data_loader, device, tta, rule, channel, threshold, ignore_i
 def _predict(model, data_loader, device, views, keep_probs, rule="argmax", channel=0, threshold=0.5,
              ignore_index=None, output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5, paint=1,
              keep_masks=False, boundary=False, spacing=1.0, keep_largest=False, min_size=0, connectivity=8):
-    """The loop of ``predict`` (``views`` None) and ``predict_tta`` (``views`` a checked view set)."""
+    """The loop of ``predict`` (``views`` None) and ``predict_tta`` (``views`` a checked view set) with
+    ``predict``'s options."""
+    return _predict_loop(model, data_loader, device, views, keep_probs, False, 0.0, rule, channel, threshold,
+                         ignore_index, output_dir, prefix, color, alpha, paint, keep_masks, boundary, spacing,
+                         keep_largest, min_size, connectivity)
+
+
+def _predict_loop(model, data_loader, device, views, keep_probs, lesions, lesion_overlap, rule="argmax", channel=0,
+                  threshold=0.5, ignore_index=None, output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5,
+                  paint=1, keep_masks=False, boundary=False, spacing=1.0, keep_largest=False, min_size=0,
+                  connectivity=8):
+    """``_predict`` and the lesion-level figures (``predict_tta`` hands ``lesions`` / ``lesion_overlap`` over)."""
     batches = _batches(model, data_loader, device, views, rule, channel, threshold, ignore_index)
     color = _check_paint(color, alpha, paint)
     if boundary:
         spacing = _check_spacing(spacing)
     connectivity, min_size = _check_components(connectivity, min_size)
     components = bool(keep_largest) or min_size > 0
+    if lesions:
+        lesion_overlap, _ = _check_lesions(lesion_overlap)
     if output_dir is not None:
         from PIL import Image
         os.makedirs(output_dir, exist_ok=True)
     model.eval()
-    all_counts, all_boundary, all_num, masks, probs, idx = [], [], [], [], [], 0
+    all_counts, all_boundary, all_num, all_lesions, masks, probs, idx = [], [], [], [], [], [], 0
     with torch.no_grad():
         for inputs, targets, mask, counts, outputs in batches:
             if keep_probs:
@@ -756,6 +870,9 @@ def _predict(model, data_loader, device, views, keep_probs, rule="argmax", chann
                 all_counts.append(counts)
                 if boundary:
                     all_boundary.append(boundary_metrics(mask, targets, ignore_index, spacing))
+                if lesions:
+                    all_lesions.append(_lesions(mask, targets, None, connectivity, lesion_overlap, 0,
+                                                ignore_index)[0])
             if output_dir is not None:
                 pics = overlay(shown_frame(inputs), mask, color, alpha, paint).cpu().numpy()
                 for j, pic in enumerate(pics):
@@ -775,6 +892,8 @@ def _predict(model, data_loader, device, views, keep_probs, rule="argmax", chann
         res["num_boundary"] = None if not all_boundary else (~torch.isnan(res["hd"])).sum()
     if components:
         res["num_components"] = torch.cat(all_num).to(torch.int64) if all_num else None
+    if lesions:
+        res.update(_pooled_lesions(all_lesions, "image"))
     if keep_masks:
         res["masks"] = masks
     if keep_probs:
@@ -803,14 +922,15 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
     mask.  The result then gains ``num_components``, an int64 device tensor in slice order: the
     components of each mask before filtering.  No device-to-host copy is added.  With both options
     off nothing of this runs and the result has no such key.
-    ``predict_tta`` is this loop with mirror test-time augmentation."""
+    ``predict_tta`` is this loop with mirror test-time augmentation and, with or without it, the
+    lesion-level detection figures (``lesions=True``)."""
     return _predict(model, data_loader, device, None, False, rule, channel, threshold, ignore_index, output_dir,
                     prefix, color, alpha, paint, keep_masks, boundary, spacing, keep_largest, min_size, connectivity)
 
 
 def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argmax", channel=0, threshold=0.5,
                     ignore_index=None, keep_largest=False, min_size=0, connectivity=26, keep_masks=False,
-                    boundary=False, spacing=1.0):
+                    boundary=False, spacing=1.0, lesions=False, lesion_overlap=0.0):
     """The inference loop over volumes: the loader yields slices in volume order -- ``depths[0]``
     slices of volume 0, then volume 1 and so on (``stfunet.dataset.volume_order`` puts a
     ``DriveDataset`` into that order); batches may straddle volume boundaries.
@@ -839,6 +959,15 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
     component options; with those off still no labelling kernel runs.  Without ``boundary`` nothing
     of this runs and the result has no such key.
 
+    ``lesions=True`` adds, when targets came, ``lesion_metrics_3d`` of every volume's mask (after the
+    component filter, when one is on) against its target at ``connectivity`` and
+    ``min_overlap=lesion_overlap``, one call per flush: ``lesion_counts`` int64 ``[V, 4]`` = (n_target,
+    matched_target, n_pred, matched_pred) per case, the pooled ``lesion_sensitivity`` = sum
+    matched_target / sum n_target and ``lesion_precision`` = sum matched_pred / sum n_pred,
+    ``false_findings`` = n_pred - matched_pred per case and their mean ``false_findings_per_case``; all
+    None without targets.  The slices are held until their volume is complete, as for ``boundary``.
+    With the default ``lesions=False`` nothing of this runs and the result has no such key.
+
     Not here: overlays (``keep_masks=True`` and ``overlay`` cover them) and anisotropic connectivity."""
     batches = _batches(model, data_loader, device, tta, rule, channel, threshold, ignore_index)
     connectivity, min_size = _check_components_3d(connectivity, min_size)
@@ -848,11 +977,13 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
     components = bool(keep_largest) or min_size > 0
     V, total = len(depths), sum(depths)
     rows = _check_spacing_3d(spacing, V) if boundary else None
+    if lesions:
+        lesion_overlap, _ = _check_lesions(lesion_overlap)
     model.eval()
     slice_volume = torch.repeat_interleave(torch.arange(V), torch.tensor(depths, dtype=torch.int64)).to(device)
     vol_counts = None                               # options off: int64 [V, 3], summed as the slices come
     held_masks, held_targets, held, done = [], [], 0, 0   # options on: slices of volumes not yet complete
-    all_counts, all_num, all_boundary, masks, idx, with_targets = [], [], [], [], 0, None
+    all_counts, all_num, all_boundary, all_lesions, masks, idx, with_targets = [], [], [], [], [], 0, None
     with torch.no_grad():
         for _, targets, mask, counts, _ in batches:
             if with_targets is None:
@@ -869,7 +1000,7 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
                     vol_counts.index_add_(0, slice_volume[idx:idx + B], counts)
                 if keep_masks:
                     masks.append(mask)
-            if components or (boundary and targets is not None):
+            if components or ((boundary or lesions) and targets is not None):
                 held_masks.append(mask)
                 if targets is not None:
                     held_targets.append(targets)
@@ -895,6 +1026,9 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
                     if boundary and t is not None:
                         all_boundary.append(_boundary3d(out.contiguous(), t[:take], depths[done:done + k],
                                                         rows[done:done + k], ignore_index)[0])
+                    if lesions and t is not None:
+                        all_lesions.append(_lesions(out.contiguous(), t[:take], depths[done:done + k], connectivity,
+                                                    lesion_overlap, 0, ignore_index)[0])
                     held_masks = [m[take:]] if take < held else []
                     held_targets = [t[take:]] if t is not None and take < held else []
                     held -= take
@@ -919,25 +1053,40 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
         res["num_boundary"] = None if per_volume is None else (~torch.isnan(per_volume[:, 0])).sum()
     if components:
         res["num_components"] = torch.cat(all_num).to(torch.int64) if all_num else None
+    if lesions:
+        res.update(_pooled_lesions(all_lesions, "case"))
     if keep_masks:
         res["masks"] = masks
     return res
 
 
 def predict_tta(model, data_loader, device, tta=True, keep_probs=False, **options):
-    """``predict`` with mirror test-time augmentation: ``options`` are ``predict``'s keywords.
+    """``predict`` with mirror test-time augmentation: ``options`` are ``predict``'s keywords and the two
+    of the lesion-level figures, ``lesions=False`` and ``lesion_overlap=0.0``.
 
     Each batch's mask comes from ``tta_probabilities(model, inputs, tta, rule, channel)``: its
     first maximum over the classes for ``rule="argmax"``, ``mean > threshold`` for ``rule="sigmoid"``
     (``predict_masks``' rule ``"threshold"``).  Counts, ``ignore_index``, the component filter, the
-    boundary metrics, the overlays (painted on the un-flipped frame) and ``keep_masks`` see that mask
+    boundary metrics, the lesion metrics, the overlays (painted on the un-flipped frame) and ``keep_masks`` see that mask
     as ``predict``'s see the plain one.  ``tta``: ``True`` for ``("none", "w", "h", "hw")`` or a
     non-empty tuple of distinct views, applied in the order given; ``None`` / ``False`` is plain
     ``predict``, which then runs nothing of this.  ``keep_probs=True`` (only with ``tta`` on) adds
-    ``probs``, the list of each batch's mean probabilities."""
+    ``probs``, the list of each batch's mean probabilities.
+
+    ``lesions=True`` adds, when targets came, the lesion-level detection figures of every mask (after
+    the component filter, when one is on) against its target, one ``lesion_metrics`` launch sequence per
+    batch at ``connectivity`` and ``min_overlap=lesion_overlap``: ``lesion_counts`` int64 ``[num, 4]`` =
+    (n_target, matched_target, n_pred, matched_pred) per image, the pooled ``lesion_sensitivity`` =
+    sum matched_target / sum n_target and ``lesion_precision`` = sum matched_pred / sum n_pred (NaN
+    without lesions / components), ``false_findings`` = n_pred - matched_pred per image and their mean
+    ``false_findings_per_image``; all None without targets.  Device tensors, no host synchronisation;
+    with the default ``lesions=False`` nothing of this runs and the result has no such key.  It works
+    with ``tta=None`` too: ``predict_tta(model, loader, device, tta=None, lesions=True)`` is the plain
+    loop with the lesion figures (``predict``'s own parameter list is pinned and does not take them)."""
     views = parse_views(tta)
     if keep_probs and views is None:
         raise ValueError("keep_probs needs test-time augmentation (tta)")
-    if views is None:
+    lesions, lesion_overlap = options.pop("lesions", False), options.pop("lesion_overlap", 0.0)
+    if views is None and not lesions:
         return predict(model, data_loader, device, **options)
-    return _predict(model, data_loader, device, views, bool(keep_probs), **options)
+    return _predict_loop(model, data_loader, device, views, bool(keep_probs), lesions, lesion_overlap, **options)

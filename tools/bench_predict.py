@@ -51,6 +51,13 @@ sigmoid rule: one plane read, one read and written), each as achieved GB/s again
 ``predict_masks`` (K planes read, one byte written per pixel) in the same rounds for scale.  Then the
 ``predict_tta`` loop (UNet, one batch, four views) against four plain forwards of the same batch.
 Prints one JSON line.
+
+``--lesions`` measures the lesion-level detection metrics (csrc/ccl.hip, the lesion kernels) on the inputs
+of ``--components3d`` stacked as ``--batch`` slices (128 for the record) in 1 and in 8 volumes, the target
+being the same kind of mask moved by three voxels: ``lesion_metrics_3d`` per call next to what a user
+had to do at least without it, two ``connected_components_3d`` calls (one per side, the labels then
+still to be copied and looped over on the host), in the same rounds; ``form`` is one elementwise pass
+over the same tensors for scale.  Prints one JSON line.
 """
 import argparse
 import json
@@ -74,6 +81,7 @@ ap.add_argument("--boundary", action="store_true", help="measure boundary_metric
 ap.add_argument("--components", action="store_true", help="measure the connected-component kernels instead")
 ap.add_argument("--components3d", action="store_true", help="measure the volume-level component kernels instead")
 ap.add_argument("--boundary3d", action="store_true", help="measure the per-volume boundary metrics instead")
+ap.add_argument("--lesions", action="store_true", help="measure the lesion-level detection metrics instead")
 ap.add_argument("--tta", action="store_true", help="measure the test-time-augmentation kernels instead")
 ap.add_argument("--host-images", type=int, default=8, help="images per regime of the scipy host timing")
 args = ap.parse_args()
@@ -346,6 +354,47 @@ if args.components3d:
         "ratio_3d_over_2d": {f"{op}_V{v}_{k}": round(med[f"{op}3d_V{v}_{k}"] / med[f"{op}2d_{k}"], 2)
                              for op in ("label", "filter") for v in volumes for k in data},
         "mean_components_per_volume": num,
+    }))
+    sys.exit(0)
+
+if args.lesions:
+    from stfunet import _lib, connected_components_3d, lesion_metrics_3d
+    volumes = [v for v in (1, 8) if B % v == 0]
+    data = {}
+    for k, (m, _, c) in component_masks().items():
+        t = torch.roll(m, (3, 3), (1, 2)).long()                 # the same kind of mask, three voxels off
+        data[k] = (m.cuda(), t.cuda(), (t > 0).to(torch.uint8).cuda(), 26 if c == 8 else 6)
+    legs = []
+    for k, (m, t, tb, c3) in data.items():
+        legs.append((f"form_{k}", lambda m=m, t=t: ((m != 0) & (t > 0)).to(torch.uint8)))
+        for v in volumes:
+            d = [B // v] * v
+            legs += [(f"label_x2_V{v}_{k}", lambda m=m, tb=tb, d=d, c3=c3: (connected_components_3d(m, d, c3),
+                                                                             connected_components_3d(tb, d, c3))),
+                     (f"lesions_V{v}_{k}", lambda m=m, t=t, d=d, c3=c3: lesion_metrics_3d(m, t, d, c3))]
+    for _, fn in legs:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name, _ in legs}
+    for _ in range(args.rounds):
+        for name, fn in legs:
+            us[name].append(timed(fn, args.iters))
+    med = {k: statistics.median(v) for k, v in us.items()}
+    res = {f"V{v}_{k}": lesion_metrics_3d(m, t, [B // v] * v, c3) for k, (m, t, _, c3) in data.items() for v in volumes}
+    print(json.dumps({
+        "tool": "bench_predict", "leg": "lesions", "shape": [B, H, W], "volumes": volumes,
+        "rounds": args.rounds, "iters": args.iters,
+        "scratch_bytes": {f"V{v}": int(_lib.load().stf_lesion_scratch_bytes(B, H, W, v)) for v in volumes},
+        "us_per_call": {k: round(v, 1) for k, v in med.items()},
+        "us_per_call_min_max": {k: [round(min(v), 1), round(max(v), 1)] for k, v in us.items()},
+        "lesions_minus_label_x2_us": {f"V{v}_{k}": round(med[f"lesions_V{v}_{k}"] - med[f"label_x2_V{v}_{k}"], 1)
+                                      for k in data for v in volumes},
+        "lesions_over_label_x2": {f"V{v}_{k}": round(med[f"lesions_V{v}_{k}"] / med[f"label_x2_V{v}_{k}"], 2)
+                                  for k in data for v in volumes},
+        "mean_n_target": {k: float(r["n_target"].double().mean()) for k, r in res.items()},
+        "mean_n_pred": {k: float(r["n_pred"].double().mean()) for k, r in res.items()},
+        "pooled_sensitivity": {k: float(r["matched_target"].sum() / r["n_target"].sum()) for k, r in res.items()},
     }))
     sys.exit(0)
 
