@@ -836,6 +836,29 @@ int stf_lesion3d_metrics(const uint8_t* mask, const int64_t* target, int N, int 
                          double min_overlap, int max_lesions, int64_t ignore_index, int64_t* summary,
                          int64_t* table, void* scratch, stf_stream_t stream);
 
+/* ---------------------------------------------------------------- score histograms
+ * The object every threshold-free figure is made of (INTEGRATION.md 2.2 states the definitions,
+ * DESIGN.md 5.20 the pass): per image, the histogram of the foreground score split by the target.
+ * src fp32 [N][K][H][W]; the score p of a pixel is
+ *   source 0   plane `channel` of the softmax over the K logit planes (stf_tta_accumulate's rule 0);
+ *   source 1   1 / (1 + expf(-x)) of logit plane `channel` (stf_predict_mask's rule 1);
+ *   source 2   plane `channel` itself (probabilities already);
+ * and its row, with bins a power of two in [2, 4096],
+ *   row(p) = 0                                       if not (p > 0)   (0, -0, negatives, NaN)
+ *          = min(bins, (int)ceilf(p * (float)bins))  otherwise        (+inf and p > 1: row bins)
+ * p * bins is exact, so row j >= 1 holds (j - 1) / bins < p <= j / bins, and row(p) > j <=> p > j / bins
+ * for p <= 1: the rows above j are the pixels stf_predict_threshold marks at threshold j / bins.
+ * hist int64 [N][2][bins + 1] is OVERWRITTEN (zeroed on the stream, then counted; it may arrive
+ * uninitialised): hist[n][s][r] = pixels of image n with row r on side s; side 1 is target > 0
+ * (positive < 0) or target == positive, side 0 every other pixel; pixels whose target equals
+ * ignore_index (>= 0; negative: none) are in neither.  One launch; integer atomics only, so the same
+ * bits from run to run.  Additive to ABI v17.  Limits: 1 <= N, 1 <= H, W <= 4096, N * H * W < 2^31,
+ * 1 <= K <= 16.  STF_EINVAL (nothing launched) for a NULL pointer, a size outside the limits,
+ * channel outside [0, K), a source other than 0 / 1 / 2, bins not a power of two in [2, 4096], or a
+ * target or hist that is not 8-byte aligned (src may sit at any multiple of 4). */
+int stf_score_hist(const float* src, int N, int K, int H, int W, int source, int channel, const int64_t* target,
+                   int64_t positive, int64_t ignore_index, int bins, int64_t* hist, stf_stream_t stream);
+
 /* ---------------------------------------------------------------- boundary metrics of volumes
  * Per-volume (per-case) HD, HD95 and ASSD with voxel spacing: MedPy's hd / hd95 / assd on a 3-D
  * array with voxelspacing = (sz, sy, sx) and connectivity 1 (INTEGRATION.md 2.2 states the

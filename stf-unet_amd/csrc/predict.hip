@@ -13,6 +13,7 @@
 //
 // All inputs are fp32 / int64 / uint8: nothing here depends on the activation storage type.
 #include "common.h"
+#include "probs.h"
 #include "../../include/stfunet.h"
 
 // The overlay bytes must equal numpy's: every fp32 operation rounded on its own (no FMA); the
@@ -48,7 +49,7 @@ STF_DEV void argmax_step(float x, unsigned k, float& best, unsigned& pred) {
   if (x > best || (x != x && best == best)) { best = x; pred = k; }
 }
 // rule 1: torch.sigmoid in fp32, then > threshold (a NaN compares false)
-STF_DEV unsigned sigmoid_over(float x, float thr) { return 1.f / (1.f + expf(-x)) > thr ? 1u : 0u; }
+STF_DEV unsigned sigmoid_over(float x, float thr) { return stf::sigmoid_prob(x) > thr ? 1u : 0u; }
 // rule 2: the plane holds probabilities already (a mean over views): > threshold, a NaN compares false
 STF_DEV unsigned over(float x, float thr) { return x > thr ? 1u : 0u; }
 

@@ -10,6 +10,7 @@
 //
 // All fp32: nothing here depends on the activation storage type.
 #include "common.h"
+#include "probs.h"
 #include "../../include/stfunet.h"
 
 // The probabilities are pinned operation by operation (one rounding each, no FMA), as predict.hip's.
@@ -54,29 +55,7 @@ __global__ __launch_bounds__(MT) void flip_planes_kernel(const float* __restrict
   }
 }
 
-// One pixel of one view: p_k from the K logits (rule 0) or the one logit (rule 1), in place.
-// rule 0: m = max z, e_k = expf(z_k - m), s = e_0 + e_1 + ... (ascending k), p_k = e_k / s.
-template <int RULE, int KM>
-STF_DEV void probabilities(float (&z)[KM], int K) {
-  if (RULE == 1) {
-    z[0] = 1.f / (1.f + expf(-z[0]));          // sigmoid_over's arithmetic (predict.hip)
-    return;
-  }
-  float m = z[0];
-#pragma unroll
-  for (int k = 1; k < KM; ++k)
-    if (k < K) m = z[k] > m ? z[k] : m;
-  float s = 0.f;
-#pragma unroll
-  for (int k = 0; k < KM; ++k)
-    if (k < K) {
-      z[k] = expf(z[k] - m);
-      s = k ? s + z[k] : z[k];
-    }
-#pragma unroll
-  for (int k = 0; k < KM; ++k)
-    if (k < K) z[k] = z[k] / s;
-}
+using stf::probabilities;      // one pixel of one view: p_k from the K logits, or the sigmoid of one (probs.h)
 
 STF_DEV float fold(float p, float a, int first, float n) {
   const float s = first ? p : a + p;

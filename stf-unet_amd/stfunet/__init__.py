@@ -14,7 +14,7 @@ from .predict import (boundary_metrics, boundary_metrics_3d, connected_component
                       connected_components_3d, distance_transform_3d, distance_transform_sq, filter_components,
                       filter_components_3d, flip_planes, image_metrics, lesion_metrics, lesion_metrics_3d, overlay,
                       predict_masks, predict_tta,
-                      predict_volumes, tta_probabilities)
+                      predict_volumes, score_histogram, threshold_curves, tta_probabilities)
 from .resize import upsample_logits  # noqa: F401
 from .stf_lstm_unet import STFLSTMUNet  # noqa: F401
 from .unet import UNet  # noqa: F401
@@ -24,5 +24,5 @@ __all__ = ["STFLSTMUNet", "UNet", "WeightEMA", "boundary_criterion", "boundary_l
            "connected_components", "connected_components_3d", "criterion", "distance_transform_3d",
            "distance_transform_sq", "filter_components", "filter_components_3d", "flip_planes", "image_metrics",
            "lesion_metrics", "lesion_metrics_3d",
-           "overlay", "predict", "predict_masks", "predict_tta", "predict_volumes", "signed_distance_maps",
-           "tta_probabilities", "upsample_logits"]
+           "overlay", "predict", "predict_masks", "predict_tta", "predict_volumes", "score_histogram",
+           "signed_distance_maps", "threshold_curves", "tta_probabilities", "upsample_logits"]

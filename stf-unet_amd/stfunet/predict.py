@@ -37,6 +37,11 @@ bit (it thresholds channel 0 and inverts the mask before painting, :75-76), exce
 PNGs are RGB: channel ``c`` of an overlay takes ``color[c]``, where the reference hands the same
 triple to cv2 as B, G, R.  The default colour (0, 255, 0) reads the same both ways.
 
+* ``score_histogram`` / ``threshold_curves``  threshold-free evaluation: the per-image histogram of the
+  foreground score split by the target (``csrc/curves.hip``) and, from it, every operating point
+  (Dice / IoU per threshold and the best one), AUROC, average precision and the calibration table with
+  its ECE; ``predict_tta(curves=True)`` and ``predict_volumes(curves=True)`` report them per image / case
+
 There is no CPU path: tensors on the host raise.
 """
 import numbers
@@ -642,6 +647,214 @@ def distance_transform_3d(sites, depths=None, spacing=1.0, where=None):
     return d2
 
 
+SOURCES = {"softmax": 0, "sigmoid": 1, "probs": 2}
+MAX_BINS = 4096
+
+
+def _is_int(x):
+    return isinstance(x, numbers.Integral) and not isinstance(x, bool)
+
+
+def _check_bins(bins):
+    if not _is_int(bins) or not 2 <= bins <= MAX_BINS or bins & (bins - 1):
+        raise ValueError(f"bins must be a power of two in [2, {MAX_BINS}], not {bins!r}")
+    return int(bins)
+
+
+def _check_hist_options(positive, ignore_index):
+    if positive is not None and (not _is_int(positive) or positive < 0):
+        raise ValueError(f"positive must be None (target > 0) or a class id >= 0, not {positive!r}")
+    if ignore_index is not None and not _is_int(ignore_index):
+        raise ValueError(f"ignore_index must be None or an integer, not {ignore_index!r}")
+
+
+def _score_hist(scores, target, source, channel, bins, positive, ignore_index):
+    """One ``stf_score_hist`` launch on checked device tensors: int64 ``[N, 2, bins + 1]``."""
+    N, K, H, W = scores.shape
+    hist = torch.empty((N, 2, bins + 1), dtype=torch.int64, device=scores.device)
+    if N:
+        target = target.detach().to(device=scores.device, dtype=torch.int64).contiguous()
+        with torch.cuda.device(scores.device):
+            call("stf_score_hist", _p(scores), N, K, H, W, SOURCES[source], channel, _p(target),
+                 -1 if positive is None else positive, _ignore(ignore_index), bins, _p(hist), stream())
+    return hist
+
+
+def score_histogram(scores, target, source="probs", channel=0, bins=256, positive=None, ignore_index=None,
+                    depths=None):
+    """int64 ``[N, 2, bins + 1]``: per image, the histogram of the foreground score split by the target --
+    the one object every threshold-free figure (``threshold_curves``) is made of.
+
+    ``scores`` is fp32 ``[N, K, H, W]`` (or ``[N, H, W]``, one plane) on the device; the score ``p`` of a
+    pixel is, by ``source``: ``"probs"`` plane ``channel`` as it is, ``"sigmoid"`` ``torch.sigmoid`` of
+    logit plane ``channel`` (``predict_masks``' arithmetic), ``"softmax"`` plane ``channel`` of the
+    softmax over the ``K`` logit planes (``tta_probabilities``' arithmetic, bit for bit).  With ``bins``
+    a power of two in [2, 4096]::
+
+        row(p) = 0                                        if not (p > 0)    # 0, -0, negatives, NaN
+               = min(bins, int(ceil(float32(p * bins))))  otherwise         # +inf and p > 1: row bins
+
+    so row ``j >= 1`` holds ``(j - 1) / bins < p <= j / bins`` and the rows above ``j`` are exactly the
+    pixels ``predict_masks(rule="threshold", threshold=j / bins)`` marks.  ``hist[n, 1]`` counts the
+    pixels with ``target > 0`` (``positive=None``) or ``target == positive``, ``hist[n, 0]`` all others;
+    pixels whose target equals ``ignore_index`` are in neither.  ``depths`` (as in
+    ``connected_components_3d``) sums the rows of each volume's slices on the device: ``[V, 2, bins + 1]``,
+    the same bits for a volume passed alone or in a stack.  Integers only: the same bits from run to
+    run; one launch, no host synchronisation."""
+    if isinstance(scores, dict):
+        scores = scores["out"]
+    if source not in SOURCES:
+        raise ValueError(f"unknown source {source!r} (one of {sorted(SOURCES)})")
+    if scores.dim() == 3:
+        scores = scores.unsqueeze(1)
+    if scores.dim() != 4:
+        raise ValueError(f"scores must be [N, K, H, W] or [N, H, W], not {tuple(scores.shape)}")
+    if not scores.dtype.is_floating_point:
+        raise ValueError(f"scores must be a floating-point tensor, not {scores.dtype}")
+    N, K, H, W = scores.shape
+    if not 1 <= K <= MAX_CLASSES:
+        raise ValueError(f"1..{MAX_CLASSES} planes are supported, not {K}")
+    if not _is_int(channel) or not 0 <= channel < K:
+        raise ValueError(f"channel {channel!r} is outside [0, {K})")
+    bins = _check_bins(bins)
+    _check_hist_options(positive, ignore_index)
+    _check_target(target, (N, H, W))
+    _check_bhw(target, "target")
+    if depths is not None:
+        depths = _check_depths(depths, N)
+    _device_only(scores, "score_histogram")
+    _device_only(target, "score_histogram")
+    hist = _score_hist(scores.detach().float().contiguous(), target, source, int(channel), bins, positive,
+                       ignore_index)
+    if depths is None:
+        return hist
+    volume = torch.repeat_interleave(torch.arange(len(depths)), torch.tensor(depths, dtype=torch.int64))
+    return torch.zeros((len(depths), 2, bins + 1), dtype=torch.int64,
+                       device=hist.device).index_add_(0, volume.to(hist.device), hist)
+
+
+def _first_max(values):
+    """(index, value) of the first maximum along the last axis -- the lowest index among equals."""
+    best = values.max(-1, keepdim=True).values
+    index = torch.arange(values.shape[-1], device=values.device)
+    first = torch.where(values == best, index, values.shape[-1] - 1).min(-1).values
+    return first, best.squeeze(-1)
+
+
+def threshold_curves(hist, cal_groups=16, smooth=1e-5):
+    """Every operating point, the ranking figures and the calibration of a score histogram ``hist``
+    (``[..., 2, bins + 1]`` integers from ``score_histogram``; leading axes are kept), as a dict of
+    tensors on ``hist``'s device -- torch ops in int64 / float64, no host synchronisation.
+
+    With ``TP_j`` / ``FP_j`` the positives / negatives in the rows above ``j``, ``j = 0..bins`` -- the
+    counts ``predict_masks(rule="threshold", threshold=j / bins)`` gives:
+
+    * ``thresholds`` ``[bins + 1]`` = ``j / bins``; ``tp``, ``fp``, ``fn``, ``tn`` int64 ``[..., bins + 1]``
+    * ``dice``, ``iou``: ``image_metrics`` of ``(TP, TP + FP, TP + FN)`` at ``smooth``, so every point equals
+      the loops' figure bit for bit; ``best_threshold`` / ``best_dice``: the first maximum of ``dice`` (the
+      lowest threshold among equals)
+    * ``auroc``: the trapezoid rule over the points ``(FPR_j, TPR_j)`` preceded by ``(1, 1)``;
+      ``average_precision``: ``sum_k (R_k - R_{k+1}) Prec_k`` over the rows ``k`` in descending order with
+      the rows ``>= k`` predicted and precision 1 where nothing is.  These are scikit-learn's
+      ``roc_auc_score`` / ``average_precision_score`` of the quantised scores (the rows); both are NaN when
+      a side is empty.
+    * ``reliability`` ``[..., G, 3]`` = (count, mean confidence, positive fraction) of ``G = cal_groups``
+      equal-width groups (``G`` divides ``bins``; group ``g`` holds rows ``g * bins / G + 1 .. (g + 1) * bins / G``,
+      row 0 joins group 0), the confidence of row ``j >= 1`` being its midpoint ``(j - 0.5) / bins`` and of
+      row 0 zero, and ``ece`` = ``sum_g count_g / total * |positive fraction_g - mean confidence_g|`` (empty
+      groups add nothing; NaN without pixels).  Every score is within ``1 / (2 bins)`` of its row's
+      midpoint, so ``ece`` is within ``1 / (2 bins)`` of the expected calibration error of the same groups
+      on the unquantised scores."""
+    if hist.dim() < 2 or hist.shape[-2] != 2 or hist.shape[-1] < 3:
+        raise ValueError(f"hist must be [..., 2, bins + 1], not {tuple(hist.shape)}")
+    if hist.dtype.is_floating_point or hist.dtype.is_complex or hist.dtype == torch.bool:
+        raise ValueError(f"hist must be an integer tensor, not {hist.dtype}")
+    bins = _check_bins(hist.shape[-1] - 1)
+    if not _is_int(cal_groups) or cal_groups < 1 or bins % cal_groups:
+        raise ValueError(f"cal_groups must be a positive integer that divides bins = {bins}, not {cal_groups!r}")
+    G = int(cal_groups)
+    hist = hist.to(torch.int64)
+    total = hist.sum(-1, keepdim=True)                        # [..., 2, 1]
+    above = total - hist.cumsum(-1)                           # rows > j
+    fp, tp = above.unbind(-2)
+    n_neg, n_pos = total.unbind(-2)
+    fn, tn = n_pos - tp, n_neg - fp
+    dice, iou = image_metrics(torch.stack((tp, tp + fp, tp + fn), -1), smooth)
+    f64 = torch.float64
+    thresholds = torch.arange(bins + 1, dtype=f64, device=hist.device) / bins
+    best, best_dice = _first_max(dice)
+    # ranking: 0 / 0 = NaN marks an empty side
+    tpr, fpr = tp.to(f64) / n_pos.to(f64), fp.to(f64) / n_neg.to(f64)
+    one = torch.ones_like(tpr[..., :1])
+    x, y = torch.cat((one, fpr), -1), torch.cat((one, tpr), -1)
+    auroc = ((x[..., :-1] - x[..., 1:]) * (y[..., :-1] + y[..., 1:])).sum(-1) * 0.5
+    at = torch.flip(hist, (-1,)).cumsum(-1)                   # rows >= k, k = bins .. 0
+    fp_k, tp_k = at.to(f64).unbind(-2)
+    recall = tp_k / n_pos.to(f64)
+    precision = torch.where(tp_k + fp_k > 0, tp_k / (tp_k + fp_k), 1.0)
+    step = recall - torch.cat((torch.zeros_like(recall[..., :1]), recall[..., :-1]), -1)
+    ap = (step * precision).sum(-1)
+    empty = ((n_pos == 0) | (n_neg == 0)).squeeze(-1)
+    nan = torch.full_like(ap, float("nan"))
+    auroc, ap = torch.where(empty, nan, auroc), torch.where(empty, nan, ap)
+    # calibration
+    rows = hist.sum(-2).to(f64)                               # [..., bins + 1]
+    confidence = (torch.arange(1, bins + 1, dtype=f64, device=hist.device) - 0.5) / bins
+    lead = hist.shape[:-2]
+    count = rows[..., 1:].reshape(*lead, G, bins // G).sum(-1)
+    count = torch.cat((count[..., :1] + rows[..., :1], count[..., 1:]), -1)
+    conf_sum = (rows[..., 1:] * confidence).reshape(*lead, G, bins // G).sum(-1)
+    pos_sum = hist[..., 1, 1:].to(f64).reshape(*lead, G, bins // G).sum(-1)
+    pos_sum = torch.cat((pos_sum[..., :1] + hist[..., 1, :1].to(f64), pos_sum[..., 1:]), -1)
+    mean_conf, pos_frac = conf_sum / count, pos_sum / count
+    gap = torch.where(count > 0, count * (pos_frac - mean_conf).abs(), 0.0)
+    ece = gap.sum(-1) / count.sum(-1)
+    return {"thresholds": thresholds, "tp": tp, "fp": fp, "fn": fn, "tn": tn, "dice": dice, "iou": iou,
+            "best_threshold": thresholds[best], "best_dice": best_dice, "auroc": auroc, "average_precision": ap,
+            "reliability": torch.stack((count, mean_conf, pos_frac), -1), "ece": ece}
+
+
+CURVE_KEYS = ("score_hist", "curves", "case_auroc", "case_average_precision", "mean_case_dice_curve",
+              "best_case_threshold")
+
+
+def _check_curves(curves, curve_bins, curve_channel):
+    """The loops' checked curve options: (on, bins, channel); the two are not looked at while it is off."""
+    if not curves:
+        return False, curve_bins, curve_channel
+    if not _is_int(curve_channel) or curve_channel < 0:
+        raise ValueError(f"curve_channel must be a class id >= 0, not {curve_channel!r}")
+    return True, _check_bins(curve_bins), int(curve_channel)
+
+
+def _batch_hist(outputs, targets, views, rule, channel, bins, curve_channel, ignore_index):
+    """The loops' one ``stf_score_hist`` launch per batch on what ``_batches`` yields: logits by ``rule``
+    (softmax of class ``curve_channel``, or the sigmoid of the rule's own plane ``channel``), mean
+    probabilities and ``rule="threshold"`` planes as they are."""
+    if isinstance(outputs, dict):
+        outputs = outputs["out"]
+    if rule == "argmax":
+        source, plane = ("softmax" if views is None else "probs"), curve_channel
+    elif rule == "sigmoid":
+        source, plane = ("sigmoid", channel) if views is None else ("probs", 0)
+    else:
+        source, plane = "probs", channel
+    return score_histogram(outputs, targets, source, plane, bins, None, ignore_index)
+
+
+def _curve_result(hist):
+    """The curve keys of the predict loops from the per-image or per-case histograms (None without targets)."""
+    if hist is None:
+        return dict.fromkeys(CURVE_KEYS)
+    groups = min(16, hist.shape[-1] - 1)                       # threshold_curves' 16, or curve_bins below that
+    per_case = threshold_curves(hist, groups)
+    pooled = threshold_curves(hist.sum(0), groups)
+    mean_dice = per_case["dice"].mean(0)
+    best, _ = _first_max(mean_dice)
+    return dict(zip(CURVE_KEYS, (hist, pooled, per_case["auroc"], per_case["average_precision"], mean_dice,
+                                 pooled["thresholds"][best])))
+
+
 def overlay(frames, mask, color=(0, 255, 0), alpha=0.5, paint=1):
     """``uint8 [B, H, W, 3]``: ``frames`` normalised to 0..255 per image, with ``color`` blended
     at ``alpha`` into the pixels where the mask is non-zero (``paint=1``) or zero (``paint=0``).
@@ -844,9 +1057,11 @@ def _predict(model, data_loader, device, views, keep_probs, rule="argmax", chann
 def _predict_loop(model, data_loader, device, views, keep_probs, lesions, lesion_overlap, rule="argmax", channel=0,
                   threshold=0.5, ignore_index=None, output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5,
                   paint=1, keep_masks=False, boundary=False, spacing=1.0, keep_largest=False, min_size=0,
-                  connectivity=8):
-    """``_predict`` and the lesion-level figures (``predict_tta`` hands ``lesions`` / ``lesion_overlap`` over)."""
+                  connectivity=8, curves=False, curve_bins=256, curve_channel=1):
+    """``_predict``, the lesion-level figures and the score histograms (``predict_tta`` hands ``lesions`` /
+    ``lesion_overlap`` and the three ``curve`` options over)."""
     batches = _batches(model, data_loader, device, views, rule, channel, threshold, ignore_index)
+    curves, curve_bins, curve_channel = _check_curves(curves, curve_bins, curve_channel)
     color = _check_paint(color, alpha, paint)
     if boundary:
         spacing = _check_spacing(spacing)
@@ -859,10 +1074,14 @@ def _predict_loop(model, data_loader, device, views, keep_probs, lesions, lesion
         os.makedirs(output_dir, exist_ok=True)
     model.eval()
     all_counts, all_boundary, all_num, all_lesions, masks, probs, idx = [], [], [], [], [], [], 0
+    all_hist = []
     with torch.no_grad():
         for inputs, targets, mask, counts, outputs in batches:
             if keep_probs:
                 probs.append(outputs)
+            if curves and targets is not None:             # the raw score, before any component filter
+                all_hist.append(_batch_hist(outputs, targets, views, rule, channel, curve_bins, curve_channel,
+                                            ignore_index))
             if components:
                 mask, counts, num = _filter(mask, targets, None, keep_largest, min_size, connectivity, ignore_index)
                 all_num.append(num)
@@ -894,6 +1113,8 @@ def _predict_loop(model, data_loader, device, views, keep_probs, lesions, lesion
         res["num_components"] = torch.cat(all_num).to(torch.int64) if all_num else None
     if lesions:
         res.update(_pooled_lesions(all_lesions, "image"))
+    if curves:
+        res.update(_curve_result(torch.cat(all_hist) if all_hist else None))
     if keep_masks:
         res["masks"] = masks
     if keep_probs:
@@ -930,7 +1151,8 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
 
 def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argmax", channel=0, threshold=0.5,
                     ignore_index=None, keep_largest=False, min_size=0, connectivity=26, keep_masks=False,
-                    boundary=False, spacing=1.0, lesions=False, lesion_overlap=0.0):
+                    boundary=False, spacing=1.0, lesions=False, lesion_overlap=0.0, curves=False, curve_bins=256,
+                    curve_channel=1):
     """The inference loop over volumes: the loader yields slices in volume order -- ``depths[0]``
     slices of volume 0, then volume 1 and so on (``stfunet.dataset.volume_order`` puts a
     ``DriveDataset`` into that order); batches may straddle volume boundaries.
@@ -968,6 +1190,11 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
     None without targets.  The slices are held until their volume is complete, as for ``boundary``.
     With the default ``lesions=False`` nothing of this runs and the result has no such key.
 
+    ``curves=True`` adds, when targets came, the threshold-free figures of the raw scores (before any
+    component filter), one ``stf_score_hist`` launch per batch at ``curve_bins`` and no held slices: the
+    keys of ``predict_tta``'s ``curves=True``, per case instead of per image.  Without the flag nothing of
+    this runs and the result has no such key.
+
     Not here: overlays (``keep_masks=True`` and ``overlay`` cover them) and anisotropic connectivity."""
     batches = _batches(model, data_loader, device, tta, rule, channel, threshold, ignore_index)
     connectivity, min_size = _check_components_3d(connectivity, min_size)
@@ -979,13 +1206,16 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
     rows = _check_spacing_3d(spacing, V) if boundary else None
     if lesions:
         lesion_overlap, _ = _check_lesions(lesion_overlap)
+    curves, curve_bins, curve_channel = _check_curves(curves, curve_bins, curve_channel)
+    views = parse_views(tta)
     model.eval()
     slice_volume = torch.repeat_interleave(torch.arange(V), torch.tensor(depths, dtype=torch.int64)).to(device)
     vol_counts = None                               # options off: int64 [V, 3], summed as the slices come
+    vol_hist = None                                 # curves: int64 [V, 2, bins + 1], summed as the slices come
     held_masks, held_targets, held, done = [], [], 0, 0   # options on: slices of volumes not yet complete
     all_counts, all_num, all_boundary, all_lesions, masks, idx, with_targets = [], [], [], [], [], 0, None
     with torch.no_grad():
-        for _, targets, mask, counts, _ in batches:
+        for _, targets, mask, counts, outputs in batches:
             if with_targets is None:
                 with_targets = targets is not None
             elif with_targets != (targets is not None):
@@ -993,6 +1223,11 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
             B = mask.shape[0]
             if idx + B > total:
                 raise ValueError(f"the loader yields more than the {total} slices of depths")
+            if curves and targets is not None:
+                hist = _batch_hist(outputs, targets, views, rule, channel, curve_bins, curve_channel, ignore_index)
+                if vol_hist is None:
+                    vol_hist = torch.zeros((V,) + tuple(hist.shape[1:]), dtype=torch.int64, device=hist.device)
+                vol_hist.index_add_(0, slice_volume[idx:idx + B], hist)
             if not components:
                 if targets is not None:
                     if vol_counts is None:
@@ -1055,6 +1290,8 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
         res["num_components"] = torch.cat(all_num).to(torch.int64) if all_num else None
     if lesions:
         res.update(_pooled_lesions(all_lesions, "case"))
+    if curves:
+        res.update(_curve_result(vol_hist))
     if keep_masks:
         res["masks"] = masks
     return res
@@ -1082,11 +1319,25 @@ def predict_tta(model, data_loader, device, tta=True, keep_probs=False, **option
     ``false_findings_per_image``; all None without targets.  Device tensors, no host synchronisation;
     with the default ``lesions=False`` nothing of this runs and the result has no such key.  It works
     with ``tta=None`` too: ``predict_tta(model, loader, device, tta=None, lesions=True)`` is the plain
-    loop with the lesion figures (``predict``'s own parameter list is pinned and does not take them)."""
+    loop with the lesion figures (``predict``'s own parameter list is pinned and does not take them).
+
+    ``curves=True`` (with ``curve_bins=256`` and ``curve_channel=1``; with or without ``tta``) adds, when
+    targets came, the threshold-free figures of the raw scores, before ``keep_largest`` / ``min_size``: one
+    ``stf_score_hist`` launch per batch on what the batch's mask was taken from.  The score is, for
+    ``rule="argmax"``, the softmax probability of class ``curve_channel`` (the mean probability under
+    ``tta``); for ``rule="sigmoid"`` the sigmoid of the rule's own plane ``channel`` (its mean under ``tta``);
+    for ``rule="threshold"`` plane ``channel`` as it is.  The result gains ``score_hist`` int64
+    ``[num, 2, curve_bins + 1]`` (``score_histogram`` per image), ``curves`` = ``threshold_curves`` of the
+    histogram pooled over all images, ``case_auroc`` / ``case_average_precision`` per image (NaN where a
+    side is empty), ``mean_case_dice_curve`` = the mean over images of each image's Dice at every
+    threshold and ``best_case_threshold``, its first maximum; all None without targets.  Device tensors,
+    no host synchronisation; without the flag nothing of this runs and the result has no such key."""
     views = parse_views(tta)
     if keep_probs and views is None:
         raise ValueError("keep_probs needs test-time augmentation (tta)")
     lesions, lesion_overlap = options.pop("lesions", False), options.pop("lesion_overlap", 0.0)
-    if views is None and not lesions:
+    if views is None and not lesions and not options.get("curves"):
+        for k in ("curves", "curve_bins", "curve_channel"):
+            options.pop(k, None)
         return predict(model, data_loader, device, **options)
     return _predict_loop(model, data_loader, device, views, bool(keep_probs), lesions, lesion_overlap, **options)

@@ -58,6 +58,14 @@ being the same kind of mask moved by three voxels: ``lesion_metrics_3d`` per cal
 had to do at least without it, two ``connected_components_3d`` calls (one per side, the labels then
 still to be copied and looped over on the host), in the same rounds; ``form`` is one elementwise pass
 over the same tensors for scale.  Prints one JSON line.
+
+``--curves`` measures the score histogram (csrc/curves.hip) at the same shape against its yardstick,
+``stf_predict_threshold`` with targets on the same tensors (the same 12 bytes read per pixel, and a
+mask byte written), both through the C entry points on preallocated outputs and interleaved in every
+round, on two score distributions: ``uniform`` and ``trained`` (97 % of the pixels in rows 0 and bins).
+Further legs say where the time goes: ``zeros`` (every pixel in row 0: no LDS atomic at all), bins 16 and
+4096, the softmax (K = 2) and sigmoid sources, and ``threshold_curves`` of the 64 tables (torch ops).
+Prints one JSON line.
 """
 import argparse
 import json
@@ -83,6 +91,7 @@ ap.add_argument("--components3d", action="store_true", help="measure the volume-
 ap.add_argument("--boundary3d", action="store_true", help="measure the per-volume boundary metrics instead")
 ap.add_argument("--lesions", action="store_true", help="measure the lesion-level detection metrics instead")
 ap.add_argument("--tta", action="store_true", help="measure the test-time-augmentation kernels instead")
+ap.add_argument("--curves", action="store_true", help="measure the score histogram and the curves instead")
 ap.add_argument("--host-images", type=int, default=8, help="images per regime of the scipy host timing")
 args = ap.parse_args()
 if not torch.cuda.is_available():
@@ -201,6 +210,60 @@ def component_masks():
     board = ((yy + xx) % 2 == 0).to(torch.uint8).expand(B, H, W).contiguous()
     return {"realistic": (P, T, 8), "percolation": (perc, T, 8), "checkerboard": (board, T, 4)}
 
+
+if args.curves:
+    from stfunet import threshold_curves
+    from stfunet._lib import call, stream
+    g = torch.Generator(device="cuda").manual_seed(4)
+    uniform = torch.rand(B, 1, H, W, device="cuda", generator=g)
+    ends = torch.rand(B, 1, H, W, device="cuda", generator=g)
+    trained = torch.where(ends < 0.873, torch.zeros_like(uniform), torch.where(ends > 0.903, torch.ones_like(uniform),
+                                                                                 uniform))
+    planes = {"uniform": uniform, "trained": trained, "zeros": torch.zeros_like(uniform)}
+    mask = torch.empty(B, H, W, dtype=torch.uint8, device="cuda")
+    counts = torch.empty(B, 3, dtype=torch.int64, device="cuda")
+    hist = torch.empty(B, 2, 4097, dtype=torch.int64, device="cuda")
+
+    def threshold(x):
+        call("stf_predict_threshold", x.data_ptr(), target.data_ptr(), B, 1, H * W, 0, 0.5, -1, mask.data_ptr(),
+             counts.data_ptr(), stream())
+
+    def histogram(x, bins, source=2, k=1):
+        call("stf_score_hist", x.data_ptr(), B, k, H, W, source, 0, target.data_ptr(), -1, -1, bins, hist.data_ptr(),
+             stream())
+
+    legs = []
+    for name in ("uniform", "trained"):
+        x = planes[name]
+        legs += [(f"threshold_{name}", lambda x=x: threshold(x)), (f"hist_{name}_b256", lambda x=x: histogram(x, 256)),
+                 (f"hist_{name}_b16", lambda x=x: histogram(x, 16)), (f"hist_{name}_b4096", lambda x=x: histogram(x, 4096))]
+    legs += [("hist_zeros_b256", lambda: histogram(planes["zeros"], 256)),
+             ("hist_softmax_K2_b256", lambda: histogram(logits, 256, 0, 2)),
+             ("hist_sigmoid_b256", lambda: histogram(logits, 256, 1, 2))]
+    histogram(uniform, 256)
+    tables = hist.view(-1)[:B * 2 * 257].view(B, 2, 257).clone()
+    legs.append(("threshold_curves_64_tables", lambda: threshold_curves(tables)))
+    for _, fn in legs:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name, _ in legs}
+    for _ in range(args.rounds):
+        for name, fn in legs:
+            us[name].append(timed(fn, args.iters))
+    med = {k: statistics.median(v) for k, v in us.items()}
+    read = B * H * W * 12
+    print(json.dumps({
+        "tool": "bench_predict", "leg": "curves", "batch": B, "size": [H, W], "rounds": args.rounds, "iters": args.iters,
+        "us_per_call": {k: round(v, 1) for k, v in med.items()},
+        "us_min_max": {k: [round(min(v), 1), round(max(v), 1)] for k, v in us.items()},
+        "read_bytes": read,
+        "read_GBps": {k: round(read / v / 1e3, 1) for k, v in med.items() if k.endswith("_b256") and "softmax" not in k},
+        "hist_over_threshold": {name: round(med[f"hist_{name}_b256"] / med[f"threshold_{name}"], 3)
+                                for name in ("uniform", "trained")},
+        "interior_fraction_trained": round(float(((trained > 0) & (trained < 1)).float().mean()), 4),
+    }))
+    sys.exit(0)
 
 if args.tta:
     import time
