@@ -859,6 +859,47 @@ int stf_lesion3d_metrics(const uint8_t* mask, const int64_t* target, int N, int 
 int stf_score_hist(const float* src, int N, int K, int H, int W, int source, int channel, const int64_t* target,
                    int64_t positive, int64_t ignore_index, int bins, int64_t* hist, stf_stream_t stream);
 
+/* ---------------------------------------------------------------- lesion confidence and FROC
+ * The lesion-level metrics swept over the confidence of each predicted component, per image or per
+ * volume (INTEGRATION.md 2.2 states the definition, DESIGN.md 5.21 the passes).  mask, target, P, T,
+ * the ignore rule, the labelling, connectivity, starts and the MATCHED rule are stf_lesion_metrics' /
+ * stf_lesion3d_metrics'; every component of P is a candidate.  src fp32 [N][K][H][W], source, channel
+ * and bins are stf_score_hist's: the score p of a voxel and its row(p) in 0..bins.
+ *   conf(c) = max row(p) over the voxels of candidate c
+ *   det(t)  = max conf(c) over the MATCHED candidates c that share a voxel with lesion t, 0 without one
+ *   summary int64 [V][4] = {n_T, matched_T, n_P, matched_P}: stf_lesion_metrics' bits  (images: V = B)
+ *   table   int64 [V][2][max_lesions][3]: stf_lesion_metrics' table with a third column: row l - 1
+ *           holds (area, hit, score) of label l, score = det on side 0 (target) and conf on side 1
+ *           (prediction); rows past n are 0, labels above max_lesions are left out; max_lesions = 0:
+ *           no table is written and table may be NULL.
+ *   hist    int64 [V][3][bins + 1]: side 0 the candidates that are not matched (false findings) by
+ *           conf, side 1 the target lesions by det (row 0: the lesions no matched candidate reached),
+ *           side 2 the matched candidates by conf.  The sides sum to n_P - matched_P, n_T, matched_P.
+ *           Integers, additive over cases.
+ * Additive to ABI v17.  The limits are stf_lesion_metrics' and stf_score_hist's: 1 <= K <= 16.  STF_EINVAL
+ * (nothing launched, outputs untouched) for whatever either of the two refuses: a NULL mask, src,
+ * target, summary, hist, scratch (or table with max_lesions > 0, or starts), a size outside the limits,
+ * a bad connectivity, a min_overlap outside [0, 1] or NaN, max_lesions < 0, K outside 1..16, channel
+ * outside [0, K), a source other than 0 / 1 / 2, bins not a power of two in [2, 4096], a host starts
+ * that is not strictly ascending from 0 to N, a src or starts that is not 4-byte aligned, or a target,
+ * summary, table, hist or scratch that is not 8-byte aligned (mask may sit at any byte).  No entry
+ * point allocates, reads back or waits between workgroups; the number of launches is fixed (hist's
+ * memset and: images 7; volumes 9, 8 without a table); atomics are integer only, so the results are
+ * the same bits from run to run and for a volume passed alone or inside a stack.  All outputs are
+ * OVERWRITTEN and may arrive uninitialised, the scratch too.
+ *
+ * Bytes of the scratch either call needs, a multiple of 8 (0 outside the limits, bins' included);
+ * V = B for images. */
+size_t stf_froc_scratch_bytes(int N, int H, int W, int V, int bins);
+int stf_froc(const uint8_t* mask, const float* src, int K, int source, int channel, const int64_t* target, int B,
+             int H, int W, int connectivity, double min_overlap, int max_lesions, int64_t ignore_index, int bins,
+             int64_t* summary, int64_t* table, int64_t* hist, void* scratch, stf_stream_t stream);
+/* The same per volume; starts_dev / starts_host / V as stf_ccl3d_* take them. */
+int stf_froc3d(const uint8_t* mask, const float* src, int K, int source, int channel, const int64_t* target, int N,
+               int H, int W, const int32_t* starts_dev, const int32_t* starts_host, int V, int connectivity,
+               double min_overlap, int max_lesions, int64_t ignore_index, int bins, int64_t* summary,
+               int64_t* table, int64_t* hist, void* scratch, stf_stream_t stream);
+
 /* ---------------------------------------------------------------- boundary metrics of volumes
  * Per-volume (per-case) HD, HD95 and ASSD with voxel spacing: MedPy's hd / hd95 / assd on a 3-D
  * array with voxelspacing = (sz, sy, sx) and connectivity 1 (INTEGRATION.md 2.2 states the

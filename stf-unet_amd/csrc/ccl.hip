@@ -80,6 +80,7 @@
 //
 // Integer only: the same code in both storage builds.
 #include "common.h"
+#include "probs.h"
 #include "volumes.h"
 #include "../../include/stfunet.h"
 
@@ -707,13 +708,47 @@ STF_DEV void add_segments(u64* acc, bool first, int root, u64 val, int lane, int
   if (first && !same) atomicAdd(&acc[root], val);
 }
 
+// The matching rule, once per root: one double multiply and one compare.
+STF_DEV bool lesion_matched(u64 a, double min_overlap) {
+  const unsigned area = (unsigned)(a >> 32), hit = (unsigned)a;
+  return hit >= 1u && (double)hit >= min_overlap * (double)area;
+}
+
+// sc[root] = max(sc[root], val), val > 0.  The word only grows, so a plain load that already shows a
+// value >= val settles it without an atomic; a stale load shows an earlier, smaller value and costs
+// one redundant atomic, never a result.
+STF_DEV void raise_to(int* sc, int root, int val) {
+  if (sc[root] < val) atomicMax(&sc[root], val);
+}
+
+// sc[root] = max(sc[root], val) for the run segments of one chunk, shaped as add_segments: the
+// segments of the chunk's first root are reduced in the wave and the running maximum is carried along
+// the row (hot, hot_max: wave-uniform); every other segment raises its word on its own.
+STF_DEV void max_segments(int* sc, bool first, int root, int val, int lane, int& hot, int& hot_max) {
+  const u64 firsts = __ballot(first);
+  if (!firsts) return;                                              // wave-uniform
+  const int r0 = __shfl(root, __builtin_ctzll(firsts), 64);
+  const bool same = first && root == r0;
+  const int m = wave_max(same ? val : 0);
+  if (r0 != hot) {
+    if (lane == 0 && hot_max) raise_to(sc, hot, hot_max);
+    hot = r0;
+    hot_max = 0;
+  }
+  hot_max = m > hot_max ? m : hot_max;
+  if (first && !same && val) raise_to(sc, root, val);
+}
+
 // One wave per row of the N H rows of one side, after compress (L [2 n] holds roots, -1 on the
 // background).  For either side, every run segment of a chunk adds (its length << 32) | (its voxels
 // on the other side's foreground) to the word of its root: area < 2^31 and hit <= area, so the two
-// halves never carry into each other.
-template <bool VOL>
+// halves never carry into each other.  FROC: a segment of the prediction side also raises the
+// confidence word of its root (sc [2 n], zero on entry, indexed as acc) to the largest row of its
+// voxels (rowp uint16 [n]: row(p) on P).
+template <bool VOL, bool FROC>
 __global__ __launch_bounds__(BT) void lesion_overlap_kernel(const int* __restrict__ L, long n, long rows, int H, int W,
-                                                            const int* __restrict__ starts2, int V, u64* acc) {
+                                                            const int* __restrict__ starts2, int V, u64* acc,
+                                                            const uint16_t* __restrict__ rowp, int* sc) {
   const int lane = threadIdx.x & 63;
   const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
   if (r >= rows) return;
@@ -724,6 +759,8 @@ __global__ __launch_bounds__(BT) void lesion_overlap_kernel(const int* __restric
   const int nw = (W + 63) >> 6;
   int hot[2] = {-1, -1};
   u64 hot_sum[2] = {0ull, 0ull};
+  int* confs = FROC ? sc + (accs[1] - acc) : nullptr;               // the prediction side's words of this volume
+  int hot_conf = -1, hot_max = 0;
   for (int c = 0; c < nw; ++c) {
     const int x = c * 64 + lane;
     const long i = r * (long)W + x;
@@ -743,17 +780,52 @@ __global__ __launch_bounds__(BT) void lesion_overlap_kernel(const int* __restric
       const u64 seg = (len == 64 ? ~0ull : (1ull << len) - 1) << lane;
       const u64 val = ((u64)len << 32) | (u64)__builtin_popcountll(seg & fg[1 - s]);
       add_segments(accs[s], first, root[s], val, lane, hot[s], hot_sum[s]);
+      if (FROC && s == 1) {
+        // the segment's maximum on its first lane: a suffix maximum that stops at the segment's last lane
+        const int last = lane + len - 1;                            // background: len = 0, nothing is taken
+        int mx = root[1] >= 0 ? (int)rowp[i] : 0;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const int t = __shfl_down(mx, o, 64);
+          if (lane + o <= last && t > mx) mx = t;
+        }
+        max_segments(confs, first, root[1], mx, lane, hot_conf, hot_max);
+      }
     }
   }
 #pragma unroll
   for (int s = 0; s < 2; ++s)
     if (lane == 0 && hot_sum[s]) atomicAdd(&accs[s][hot[s]], hot_sum[s]);
+  if (FROC && lane == 0 && hot_max) raise_to(confs, hot_conf, hot_max);
 }
 
-// The matching rule, once per root: one double multiply and one compare.
-STF_DEV bool lesion_matched(u64 a, double min_overlap) {
-  const unsigned area = (unsigned)(a >> 32), hit = (unsigned)a;
-  return hit >= 1u && (double)hit >= min_overlap * (double)area;
+// FROC, after overlap (every root's (area, hit) word and confidence are final): one wave per row.  A
+// run of voxels of P & T lies in one candidate and one lesion, so its first lane speaks for it: when
+// the candidate is matched, the lesion's word (side 0 of sc) is raised to the candidate's confidence.
+// Rows where the sides do not overlap cost their two loads.
+template <bool VOL>
+__global__ __launch_bounds__(BT) void froc_pair_kernel(const int* __restrict__ L, long n, long rows, int H, int W,
+                                                       const int* __restrict__ starts2, int V,
+                                                       const u64* __restrict__ acc, double min_overlap, int* sc) {
+  const int lane = threadIdx.x & 63;
+  const long r = (long)blockIdx.x * (BT / 64) + (threadIdx.x >> 6);
+  if (r >= rows) return;
+  const int z = (int)(r / H), N = (int)(rows / H);
+  const long offT = (long)volume_of<VOL>(starts2, 2 * V, z).z0 * H * W;
+  const long offP = (long)volume_of<VOL>(starts2, 2 * V, N + z).z0 * H * W;
+  const int nw = (W + 63) >> 6;
+  for (int c = 0; c < nw; ++c) {
+    const int x = c * 64 + lane;
+    const long i = r * (long)W + x;
+    const int rt = x < W ? L[i] : -1, rp = x < W ? L[n + i] : -1;
+    const bool both = rt >= 0 && rp >= 0;
+    const u64 w = __ballot(both);
+    if (!w) continue;                                               // wave-uniform
+    if (both && (lane == 0 || !((w >> (lane - 1)) & 1))) {          // the first lane of its run
+      const int conf = sc[offP + rp];
+      if (conf && lesion_matched(acc[offP + rp], min_overlap)) raise_to(sc + offT, rt, conf);
+    }
+  }
 }
 
 // The raster walk of slice z of side blockIdx.y (grid N x 2).  Row rank - 1 of the side's table takes
@@ -762,34 +834,77 @@ STF_DEV bool lesion_matched(u64 a, double min_overlap) {
 //   volumes, COUNT    cnt[z'] = roots of the slice, mat[z'] = matched roots (z' = side N + z).
 //   volumes, !COUNT   the table rows, the carry starting at cnt[z'], by then the roots of the volume's
 //                     earlier slices (lesion_volume_kernel).
-template <bool VOL, bool COUNT>
+// FROC: a table row has a third column, the root's score word (sc, indexed as acc: det on side 0, conf on
+// side 1), and the pass that sees every root once (images; volumes, COUNT) counts the root in its row
+// of hist u64 [V][3][bins + 1] (zero on entry): a lesion in side 1, a candidate in side 2 when it is
+// matched and in side 0 when not.  The workgroup counts in LDS (dynamic: unsigned [2][bins + 1]; the two
+// end rows, where a trained model puts nearly every root, in registers, as curves.hip does) and adds
+// each non-zero counter to hist once.
+template <bool VOL, bool COUNT, bool FROC>
 __global__ __launch_bounds__(RT) void lesion_walk_kernel(const int* __restrict__ L, const u64* __restrict__ acc,
                                                          int N, int HW, const int* __restrict__ starts2, int V,
                                                          int* __restrict__ cnt, int* __restrict__ mat,
                                                          double min_overlap, int max_lesions,
-                                                         int64_t* __restrict__ summary, int64_t* __restrict__ table) {
+                                                         int64_t* __restrict__ summary, int64_t* __restrict__ table,
+                                                         const int* __restrict__ sc, int bins,
+                                                         u64* __restrict__ hist) {
+  constexpr int COLS = FROC ? 3 : 2;
+  constexpr bool HIST = FROC && (!VOL || COUNT);
+  extern __shared__ unsigned tab[];
   __shared__ int wmat[RT / 64];
   const int side = blockIdx.y, z2 = side * N + (int)blockIdx.x;
   const Vol vol2 = volume_of<VOL>(starts2, 2 * V, z2);
   const int v = vol2.v - side * V;                                  // the volume in the caller's numbering
   const u64* Av = acc + (long)vol2.z0 * HW;
-  int64_t* rowsT = table ? table + ((long)v * 2 + side) * max_lesions * 2 : nullptr;
+  const int* Sv = FROC ? sc + (long)vol2.z0 * HW : nullptr;
+  int64_t* rowsT = table ? table + ((long)v * 2 + side) * max_lesions * COLS : nullptr;
   int matched = 0;
+  unsigned ends[4] = {0, 0, 0, 0};                                  // [matched candidate * 2 + (row == bins)]
+  if (HIST) {
+    for (int i = threadIdx.x; i < 2 * (bins + 1); i += RT) tab[i] = 0;
+    __syncthreads();
+  }
   const int n = root_walk(L + (long)z2 * HW, HW, (z2 - vol2.z0) * HW, VOL && !COUNT ? cnt[z2] : 0,
                           [&](int p, int rank) {
     const u64 a = Av[p];
-    if (!VOL || COUNT) matched += lesion_matched(a, min_overlap);
+    const bool m = lesion_matched(a, min_overlap);
+    if (!VOL || COUNT) matched += m;
     if ((!VOL || !COUNT) && rowsT && rank <= max_lesions) {
-      rowsT[(long)(rank - 1) * 2] = (int64_t)(a >> 32);
-      rowsT[(long)(rank - 1) * 2 + 1] = (int64_t)(a & 0xFFFFFFFFull);
+      rowsT[(long)(rank - 1) * COLS] = (int64_t)(a >> 32);
+      rowsT[(long)(rank - 1) * COLS + 1] = (int64_t)(a & 0xFFFFFFFFull);
+      if (FROC) rowsT[(long)(rank - 1) * COLS + 2] = (int64_t)Sv[p];
+    }
+    if (HIST) {
+      int row = Sv[p];
+      row = row < 0 ? 0 : row > bins ? bins : row;                  // inside the table whatever the word holds
+      const unsigned slot = side && m, lo = row == 0, hi = row == bins;
+      ends[0] += lo & (slot ^ 1u);                                  // constant indices: registers
+      ends[1] += hi & (slot ^ 1u);
+      ends[2] += lo & slot;
+      ends[3] += hi & slot;
+      if (!(lo | hi)) atomicAdd(&tab[slot * (bins + 1) + row], 1u);
     }
   });
+  if (HIST) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const unsigned s = (unsigned)wave_sum_i((int)ends[j]);
+      if ((threadIdx.x & 63) == 0 && s) atomicAdd(&tab[(j >> 1) * (bins + 1) + ((j & 1) ? bins : 0)], s);
+    }
+    __syncthreads();
+    u64* out = hist + (long)v * 3 * (bins + 1);
+    for (int i = threadIdx.x; i < 2 * (bins + 1); i += RT) {
+      const unsigned k = tab[i];
+      const int slot = i > bins, row = i - slot * (bins + 1);
+      if (k) atomicAdd(&out[(side ? slot * 2 : 1) * (bins + 1) + row], (u64)k);
+    }
+  }
   if (VOL && !COUNT) return;
   matched = wave_sum_i(matched);
   if ((threadIdx.x & 63) == 0) wmat[threadIdx.x >> 6] = matched;
   __syncthreads();
   if (!VOL && rowsT)
-    for (long k = (long)n * 2 + threadIdx.x; k < (long)max_lesions * 2; k += RT) rowsT[k] = 0;
+    for (long k = (long)n * COLS + threadIdx.x; k < (long)max_lesions * COLS; k += RT) rowsT[k] = 0;
   if (threadIdx.x != 0) return;
   matched = 0;
   for (int w = 0; w < RT / 64; ++w) matched += wmat[w];
@@ -803,7 +918,9 @@ __global__ __launch_bounds__(RT) void lesion_walk_kernel(const int* __restrict__
 }
 
 // One wave per volume of the doubled stack (grid 2 V) over its slices in order: cnt[z'] becomes the
-// roots of the volume's earlier slices; summary {n, matched} of the side; the table's rows past n = 0.
+// roots of the volume's earlier slices; summary {n, matched} of the side; the table's rows (of COLS
+// columns) past n = 0.
+template <int COLS>
 __global__ __launch_bounds__(64) void lesion_volume_kernel(const int* __restrict__ starts2, int N, int V,
                                                            int* __restrict__ cnt, const int* __restrict__ mat,
                                                            int max_lesions, int64_t* __restrict__ summary,
@@ -831,32 +948,110 @@ __global__ __launch_bounds__(64) void lesion_volume_kernel(const int* __restrict
   }
   matched = wave_sum_i(matched);
   if (table) {
-    int64_t* rowsT = table + ((long)v * 2 + side) * max_lesions * 2;
-    for (long k = (long)carry * 2 + lane; k < (long)max_lesions * 2; k += 64) rowsT[k] = 0;
+    int64_t* rowsT = table + ((long)v * 2 + side) * max_lesions * COLS;
+    for (long k = (long)carry * COLS + lane; k < (long)max_lesions * COLS; k += 64) rowsT[k] = 0;
   }
   if (lane != 0) return;
   summary[(long)v * 4 + side * 2] = carry;
   summary[(long)v * 4 + side * 2 + 1] = matched;
 }
 
+// FROC's form pass: lesion_form_kernel's outputs, the zeroed score words sc [2 n] and the row plane
+// rowp uint16 [n] = row(p) on P, 0 elsewhere, p from src as curves.hip takes it (probs.h; SOURCE 1 / 2:
+// src already points at plane `channel` and K = 1).  One thread per voxel, or per quad of one image's
+// voxels (QUAD: HW % 4 == 0, n % 4 == 0 with it, and src / target 16-B, mask 4-B aligned; the scratch is
+// 8-B aligned, which the 8-B row store and the 4-B mask stores need).  starts: NULL for images.
+template <int SOURCE, int KM, bool QUAD>
+__global__ __launch_bounds__(BT) void froc_form_kernel(const uint8_t* __restrict__ mask, const float* __restrict__ src,
+                                                       long img_stride, int K, int channel,
+                                                       const int64_t* __restrict__ target, long n, long HW, long ignore,
+                                                       int bins, const int* __restrict__ starts, int V, int N,
+                                                       uint8_t* __restrict__ bin, u64* __restrict__ acc,
+                                                       int* __restrict__ sc, uint16_t* __restrict__ rowp,
+                                                       int* __restrict__ starts2) {
+  if (starts && blockIdx.x == 0)
+    for (int v = threadIdx.x; v <= 2 * V; v += BT) {                // as lesion_form_kernel
+      const int z = v == V ? N : starts[v < V ? v : v - V];
+      starts2[v] = (v > V ? N : 0) + (z < 0 ? 0 : z > N ? N : z);
+    }
+  const long u = (long)blockIdx.x * BT + threadIdx.x;
+  if (QUAD) {
+    const long i = u * 4;
+    if (i >= n) return;
+    const long b = i / HW, off = i - b * HW;
+    const uchar4 m = *reinterpret_cast<const uchar4*>(mask + i);
+    const longlong2 t0 = *reinterpret_cast<const longlong2*>(target + i);
+    const longlong2 t1 = *reinterpret_cast<const longlong2*>(target + i + 2);
+    const long tv[4] = {t0.x, t0.y, t1.x, t1.y};
+    const uint8_t mv[4] = {m.x, m.y, m.z, m.w};
+    bool fgT[4], fgP[4];
+    bool any = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const bool keep = !(ignore >= 0 && tv[j] == ignore);
+      fgT[j] = keep && tv[j] > 0;
+      fgP[j] = keep && mv[j] != 0;
+      any |= fgP[j];
+    }
+    float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (any) p = stf::score_quad<SOURCE, KM>(src + b * img_stride, HW, off >> 2, K, channel);
+    const float pv[4] = {p.x, p.y, p.z, p.w};
+    ushort4 rw;
+    rw.x = fgP[0] ? (uint16_t)stf::row_of(pv[0], bins) : (uint16_t)0;
+    rw.y = fgP[1] ? (uint16_t)stf::row_of(pv[1], bins) : (uint16_t)0;
+    rw.z = fgP[2] ? (uint16_t)stf::row_of(pv[2], bins) : (uint16_t)0;
+    rw.w = fgP[3] ? (uint16_t)stf::row_of(pv[3], bins) : (uint16_t)0;
+    *reinterpret_cast<ushort4*>(rowp + i) = rw;
+    *reinterpret_cast<uchar4*>(bin + i) = make_uchar4(fgT[0], fgT[1], fgT[2], fgT[3]);
+    *reinterpret_cast<uchar4*>(bin + n + i) = make_uchar4(fgP[0], fgP[1], fgP[2], fgP[3]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      acc[i + j] = 0;
+      acc[n + i + j] = 0;
+      sc[i + j] = 0;
+      sc[n + i + j] = 0;
+    }
+  } else {
+    const long i = u;
+    if (i >= n) return;
+    const long b = i / HW, off = i - b * HW;
+    const long tv = target[i];
+    const bool keep = !(ignore >= 0 && tv == ignore);
+    const bool fgP = keep && mask[i] != 0;
+    bin[i] = keep && tv > 0;
+    bin[n + i] = fgP;
+    rowp[i] = fgP ? (uint16_t)stf::row_of(stf::score_at<SOURCE, KM>(src + b * img_stride, HW, off, K, channel), bins)
+                  : (uint16_t)0;
+    acc[i] = 0;
+    acc[n + i] = 0;
+    sc[i] = 0;
+    sc[n + i] = 0;
+  }
+}
+
 // scratch: [starts2 int32 [2 V + 1], 256-B rounded][roots per slice int32 [2 N], 256-B rounded]
 //          [matched roots per slice int32 [2 N], 256-B rounded]       (images leave these three unused)
-//          [(area << 32 | hit) u64 [2 n]][parents int32 [2 n]][the two masks uint8 [2 n]]
-// 26 bytes per voxel of the input.
+//          [(area << 32 | hit) u64 [2 n]][parents int32 [2 n]]
+//          FROC only: [score words int32 [2 n]][rows uint16 [n]]
+//          [the two masks uint8 [2 n]]
+// 26 bytes per voxel of the input; FROC 36.
 struct LesionScratch {
   int* starts2;
   int* cnt;
   int* mat;
   u64* acc;
   int* L;
+  int* sc;
+  uint16_t* rowp;
   uint8_t* bin;
 };
-inline size_t lesion_scratch_bytes(int N, int H, int W, int V) {
+inline size_t lesion_scratch_bytes(int N, int H, int W, int V, bool froc) {
   if (!sizes_ok(N, H, W, V)) return 0;
   const size_t head = round_up((2 * (size_t)V + 1) * sizeof(int), 256) + 2 * round_up((size_t)N * 2 * sizeof(int), 256);
-  return round_up(head + (size_t)N * H * W * 2 * (sizeof(u64) + sizeof(int) + 1), 8);
+  const size_t n = (size_t)N * H * W;
+  return round_up(head + n * 2 * (sizeof(u64) + sizeof(int) + 1) + (froc ? n * (2 * sizeof(int) + 2) : 0), 8);
 }
-inline LesionScratch lesion_carve(void* scratch, int N, int V, long n) {
+inline LesionScratch lesion_carve(void* scratch, int N, int V, long n, bool froc) {
   char* p = (char*)scratch;
   LesionScratch s;
   s.starts2 = (int*)p;
@@ -867,7 +1062,9 @@ inline LesionScratch lesion_carve(void* scratch, int N, int V, long n) {
   p += round_up((size_t)N * 2 * sizeof(int), 256);
   s.acc = (u64*)p;
   s.L = (int*)(s.acc + 2 * n);
-  s.bin = (uint8_t*)(s.L + 2 * n);
+  s.sc = froc ? s.L + 2 * n : nullptr;
+  s.rowp = froc ? (uint16_t*)(s.sc + 2 * n) : nullptr;
+  s.bin = froc ? (uint8_t*)(s.rowp + n) : (uint8_t*)(s.L + 2 * n);
   return s;
 }
 
@@ -879,42 +1076,112 @@ inline bool lesion_args_ok(const void* target, double min_overlap, int max_lesio
   return !(((uintptr_t)target | (uintptr_t)summary | (uintptr_t)table) & 7);
 }
 
-template <bool VOL>
+// The score side of stf_froc / stf_froc3d, and what they refuse on top of the lesion entry points:
+// stf_score_hist's limits.
+constexpr int MAXK = 16;
+constexpr int MAXBINS = 4096;
+struct Froc {
+  const float* src;
+  int K, source, channel, bins;
+  int64_t* hist;
+};
+inline bool bins_ok(int bins) { return bins >= 2 && bins <= MAXBINS && (bins & (bins - 1)) == 0; }
+inline bool froc_args_ok(const Froc& f) {
+  if (!f.src || !f.hist || ((uintptr_t)f.src & 3) || ((uintptr_t)f.hist & 7)) return false;
+  if (f.K < 1 || f.K > MAXK || f.channel < 0 || f.channel >= f.K || f.source < 0 || f.source > 2) return false;
+  return bins_ok(f.bins);
+}
+
+template <int SOURCE, int KM>
+void launch_froc_form(bool quad, unsigned grid, hipStream_t s, const uint8_t* mask, const float* x, long img_stride,
+                      int K, int channel, const int64_t* target, long n, long HW, long ignore, int bins,
+                      const int* starts, int V, int N, const LesionScratch& ls) {
+  if (quad)
+    hipLaunchKernelGGL((froc_form_kernel<SOURCE, KM, true>), dim3(grid), dim3(BT), 0, s, mask, x, img_stride, K,
+                       channel, target, n, HW, ignore, bins, starts, V, N, ls.bin, ls.acc, ls.sc, ls.rowp, ls.starts2);
+  else
+    hipLaunchKernelGGL((froc_form_kernel<SOURCE, KM, false>), dim3(grid), dim3(BT), 0, s, mask, x, img_stride, K,
+                       channel, target, n, HW, ignore, bins, starts, V, N, ls.bin, ls.acc, ls.sc, ls.rowp, ls.starts2);
+}
+
+// The lesion metrics (FROC false: f is not looked at) and, with FROC, the confidences on top: the row
+// plane in form, the candidates' maxima in overlap, the lesions' in pair, the third column and hist in
+// the walks.  Launches.  Lesions: images 6; volumes 8, 7 without a table.  FROC: hist's memset and
+// images 7; volumes 9, 8 without a table.
+template <bool VOL, bool FROC>
 int lesion(const uint8_t* mask, const int64_t* target, int N, int H, int W, const int32_t* starts_dev,
            const int32_t* starts_host, int V, int connectivity, double min_overlap, int max_lesions,
-           int64_t ignore_index, int64_t* summary, int64_t* table, void* scratch, stf_stream_t stream) {
+           int64_t ignore_index, int64_t* summary, int64_t* table, void* scratch, stf_stream_t stream,
+           const Froc& f) {
   const int level = level_or_refuse<VOL>(mask, N, H, W, starts_dev, starts_host, V, connectivity, nullptr, scratch);
   if (!level || !lesion_args_ok(target, min_overlap, max_lesions, summary, table)) return STF_EINVAL;
+  if (FROC && !froc_args_ok(f)) return STF_EINVAL;
   if (!max_lesions) table = nullptr;
   hipStream_t s = (hipStream_t)stream;
-  const long n = (long)N * H * W, rows = (long)N * H;
-  const LesionScratch ls = lesion_carve(scratch, N, V, n);
-  hipLaunchKernelGGL(lesion_form_kernel<VOL>, dim3((unsigned)((n + BT - 1) / BT)), dim3(BT), 0, s, mask, target, n,
-                     (long)ignore_index, starts_dev, V, N, ls.bin, ls.acc, ls.starts2);
+  const long n = (long)N * H * W, rows = (long)N * H, HW = (long)H * W;
+  const LesionScratch ls = lesion_carve(scratch, N, V, n, FROC);
+  const int bins = FROC ? f.bins : 0;
+  const unsigned lds = FROC ? 2u * (unsigned)(bins + 1) * (unsigned)sizeof(unsigned) : 0u;
+  u64* hist = FROC ? (u64*)f.hist : nullptr;
+  if (FROC) {
+    const hipError_t e = stf::memset_async(hist, 0, (size_t)V * 3 * (bins + 1) * sizeof(int64_t), s);
+    if (e != hipSuccess) return (int)e;
+    const bool quad = HW % 4 == 0 && !((uintptr_t)f.src & 15) && !((uintptr_t)target & 15) && !((uintptr_t)mask & 3);
+    const long units = quad ? n / 4 : n;
+    const unsigned grid = (unsigned)((units + BT - 1) / BT);
+    const long ign = (long)ignore_index, stride = (long)f.K * HW;
+    const float* plane = f.src + (long)f.channel * HW;
+    if (f.source == 1)
+      launch_froc_form<1, 1>(quad, grid, s, mask, plane, stride, 1, 0, target, n, HW, ign, bins, starts_dev, V, N, ls);
+    else if (f.source == 2)
+      launch_froc_form<2, 1>(quad, grid, s, mask, plane, stride, 1, 0, target, n, HW, ign, bins, starts_dev, V, N, ls);
+    else if (f.K <= 2)
+      launch_froc_form<0, 2>(quad, grid, s, mask, f.src, stride, f.K, f.channel, target, n, HW, ign, bins, starts_dev,
+                             V, N, ls);
+    else if (f.K <= 4)
+      launch_froc_form<0, 4>(quad, grid, s, mask, f.src, stride, f.K, f.channel, target, n, HW, ign, bins, starts_dev,
+                             V, N, ls);
+    else if (f.K <= 8)
+      launch_froc_form<0, 8>(quad, grid, s, mask, f.src, stride, f.K, f.channel, target, n, HW, ign, bins, starts_dev,
+                             V, N, ls);
+    else
+      launch_froc_form<0, MAXK>(quad, grid, s, mask, f.src, stride, f.K, f.channel, target, n, HW, ign, bins,
+                                starts_dev, V, N, ls);
+  } else {
+    hipLaunchKernelGGL(lesion_form_kernel<VOL>, dim3((unsigned)((n + BT - 1) / BT)), dim3(BT), 0, s, mask, target, n,
+                       (long)ignore_index, starts_dev, V, N, ls.bin, ls.acc, ls.starts2);
+  }
   STF_CHECK_LAUNCH();
   const Scratch sc = {nullptr, nullptr, nullptr, ls.L, nullptr};
   const int rc = label_roots<VOL>(ls.bin, 2 * N, H, W, ls.starts2, 2 * V, level, sc, false, s);
   if (rc) return rc;
-  hipLaunchKernelGGL(lesion_overlap_kernel<VOL>, dim3(row_grid(rows)), dim3(BT), 0, s, (const int*)ls.L, n, rows, H,
-                     W, (const int*)ls.starts2, V, ls.acc);
+  hipLaunchKernelGGL((lesion_overlap_kernel<VOL, FROC>), dim3(row_grid(rows)), dim3(BT), 0, s, (const int*)ls.L, n,
+                     rows, H, W, (const int*)ls.starts2, V, ls.acc, (const uint16_t*)ls.rowp, ls.sc);
   STF_CHECK_LAUNCH();
+  if (FROC) {
+    hipLaunchKernelGGL(froc_pair_kernel<VOL>, dim3(row_grid(rows)), dim3(BT), 0, s, (const int*)ls.L, n, rows, H, W,
+                       (const int*)ls.starts2, V, (const u64*)ls.acc, min_overlap, ls.sc);
+    STF_CHECK_LAUNCH();
+  }
   const dim3 slices((unsigned)N, 2);
   if (!VOL) {
-    hipLaunchKernelGGL((lesion_walk_kernel<false, false>), slices, dim3(RT), 0, s, (const int*)ls.L,
+    hipLaunchKernelGGL((lesion_walk_kernel<false, false, FROC>), slices, dim3(RT), lds, s, (const int*)ls.L,
                        (const u64*)ls.acc, N, H * W, (const int*)nullptr, V, ls.cnt, ls.mat, min_overlap, max_lesions,
-                       summary, table);
+                       summary, table, (const int*)ls.sc, bins, hist);
     STF_CHECK_LAUNCH();
     return 0;
   }
-  hipLaunchKernelGGL((lesion_walk_kernel<true, true>), slices, dim3(RT), 0, s, (const int*)ls.L, (const u64*)ls.acc,
-                     N, H * W, (const int*)ls.starts2, V, ls.cnt, ls.mat, min_overlap, max_lesions, summary, table);
+  hipLaunchKernelGGL((lesion_walk_kernel<true, true, FROC>), slices, dim3(RT), lds, s, (const int*)ls.L,
+                     (const u64*)ls.acc, N, H * W, (const int*)ls.starts2, V, ls.cnt, ls.mat, min_overlap, max_lesions,
+                     summary, table, (const int*)ls.sc, bins, hist);
   STF_CHECK_LAUNCH();
-  hipLaunchKernelGGL(lesion_volume_kernel, dim3((unsigned)(2 * V)), dim3(64), 0, s, (const int*)ls.starts2, N, V,
-                     ls.cnt, (const int*)ls.mat, max_lesions, summary, table);
+  hipLaunchKernelGGL(lesion_volume_kernel<FROC ? 3 : 2>, dim3((unsigned)(2 * V)), dim3(64), 0, s,
+                     (const int*)ls.starts2, N, V, ls.cnt, (const int*)ls.mat, max_lesions, summary, table);
   STF_CHECK_LAUNCH();
   if (!table) return 0;
-  hipLaunchKernelGGL((lesion_walk_kernel<true, false>), slices, dim3(RT), 0, s, (const int*)ls.L, (const u64*)ls.acc,
-                     N, H * W, (const int*)ls.starts2, V, ls.cnt, ls.mat, min_overlap, max_lesions, summary, table);
+  hipLaunchKernelGGL((lesion_walk_kernel<true, false, FROC>), slices, dim3(RT), 0, s, (const int*)ls.L,
+                     (const u64*)ls.acc, N, H * W, (const int*)ls.starts2, V, ls.cnt, ls.mat, min_overlap, max_lesions,
+                     summary, table, (const int*)ls.sc, bins, hist);
   STF_CHECK_LAUNCH();
   return 0;
 }
@@ -922,22 +1189,43 @@ int lesion(const uint8_t* mask, const int64_t* target, int N, int H, int W, cons
 }  // namespace
 
 extern "C" size_t stf_lesion_scratch_bytes(int N, int H, int W, int V) {
-  return lesion_scratch_bytes(N, H, W, V);
+  return lesion_scratch_bytes(N, H, W, V, false);
+}
+
+extern "C" size_t stf_froc_scratch_bytes(int N, int H, int W, int V, int bins) {
+  return bins_ok(bins) ? lesion_scratch_bytes(N, H, W, V, true) : 0;
+}
+
+extern "C" int stf_froc(const uint8_t* mask, const float* src, int K, int source, int channel, const int64_t* target,
+                        int B, int H, int W, int connectivity, double min_overlap, int max_lesions,
+                        int64_t ignore_index, int bins, int64_t* summary, int64_t* table, int64_t* hist,
+                        void* scratch, stf_stream_t stream) {
+  return lesion<false, true>(mask, target, B, H, W, nullptr, nullptr, B, connectivity, min_overlap, max_lesions,
+                             ignore_index, summary, table, scratch, stream, Froc{src, K, source, channel, bins, hist});
+}
+
+extern "C" int stf_froc3d(const uint8_t* mask, const float* src, int K, int source, int channel,
+                          const int64_t* target, int N, int H, int W, const int32_t* starts_dev,
+                          const int32_t* starts_host, int V, int connectivity, double min_overlap, int max_lesions,
+                          int64_t ignore_index, int bins, int64_t* summary, int64_t* table, int64_t* hist,
+                          void* scratch, stf_stream_t stream) {
+  return lesion<true, true>(mask, target, N, H, W, starts_dev, starts_host, V, connectivity, min_overlap, max_lesions,
+                            ignore_index, summary, table, scratch, stream, Froc{src, K, source, channel, bins, hist});
 }
 
 extern "C" int stf_lesion_metrics(const uint8_t* mask, const int64_t* target, int B, int H, int W, int connectivity,
                                   double min_overlap, int max_lesions, int64_t ignore_index, int64_t* summary,
                                   int64_t* table, void* scratch, stf_stream_t stream) {
-  return lesion<false>(mask, target, B, H, W, nullptr, nullptr, B, connectivity, min_overlap, max_lesions,
-                       ignore_index, summary, table, scratch, stream);
+  return lesion<false, false>(mask, target, B, H, W, nullptr, nullptr, B, connectivity, min_overlap, max_lesions,
+                              ignore_index, summary, table, scratch, stream, Froc{});
 }
 
 extern "C" int stf_lesion3d_metrics(const uint8_t* mask, const int64_t* target, int N, int H, int W,
                                     const int32_t* starts_dev, const int32_t* starts_host, int V, int connectivity,
                                     double min_overlap, int max_lesions, int64_t ignore_index, int64_t* summary,
                                     int64_t* table, void* scratch, stf_stream_t stream) {
-  return lesion<true>(mask, target, N, H, W, starts_dev, starts_host, V, connectivity, min_overlap, max_lesions,
-                      ignore_index, summary, table, scratch, stream);
+  return lesion<true, false>(mask, target, N, H, W, starts_dev, starts_host, V, connectivity, min_overlap, max_lesions,
+                             ignore_index, summary, table, scratch, stream, Froc{});
 }
 
 extern "C" size_t stf_ccl_scratch_bytes(int B, int H, int W) { return scratch_bytes<false>(B, H, W, B); }

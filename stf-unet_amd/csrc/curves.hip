@@ -32,6 +32,10 @@ constexpr int MAXDIM = 4096;
 constexpr int MAXBINS = 4096;
 constexpr int GRID_CAP = 2048;
 
+using stf::row_of;
+using stf::score_at;
+using stf::score_quad;
+
 inline bool aligned(const void* p, unsigned a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 // blocks per image: enough for one unit per lane, at most GRID_CAP / N, at least one
@@ -41,12 +45,6 @@ inline int blocks_per_image(long units, int N) {
   if (most < 1) most = 1;
   if (want > most) want = most;
   return want < 1 ? 1 : (int)want;
-}
-
-STF_DEV int row_of(float p, int bins) {
-  if (!(p > 0.f)) return 0;
-  const float c = ceilf(p * (float)bins);
-  return c >= (float)bins ? bins : (int)c;
 }
 
 struct Ends {
@@ -64,49 +62,6 @@ STF_DEV void tally(float p, long t, long positive, long ignore, int bins, unsign
   e.c[2] += lo & side;
   e.c[3] += hi & side;
   if (!(lo | hi)) atomicAdd(&tab[side * (bins + 1) + r], 1u);
-}
-
-// SOURCE 0 reads the K logit planes (KM >= K held in registers); 1 and 2 the one plane `src` already points at
-template <int SOURCE, int KM>
-STF_DEV float score_at(const float* __restrict__ x, long HW, long i, int K, int channel) {
-  if (SOURCE == 2) return x[i];
-  if (SOURCE == 1) return stf::sigmoid_prob(x[i]);
-  float z[KM];
-#pragma unroll
-  for (int k = 0; k < KM; ++k)
-    if (k < K) z[k] = x[(long)k * HW + i];
-  stf::probabilities<0, KM>(z, K);
-  float p = z[0];
-#pragma unroll
-  for (int k = 1; k < KM; ++k)
-    if (k == channel) p = z[k];
-  return p;
-}
-
-template <int SOURCE, int KM>
-STF_DEV float4 score_quad(const float* __restrict__ x, long HW, long q, int K, int channel) {
-  if (SOURCE != 0) {
-    const float4 v = *reinterpret_cast<const float4*>(x + q * 4);
-    if (SOURCE == 2) return v;
-    return make_float4(stf::sigmoid_prob(v.x), stf::sigmoid_prob(v.y), stf::sigmoid_prob(v.z), stf::sigmoid_prob(v.w));
-  }
-  float z[4][KM];
-#pragma unroll
-  for (int k = 0; k < KM; ++k)
-    if (k < K) {
-      const float4 v = *reinterpret_cast<const float4*>(x + (long)k * HW + q * 4);
-      z[0][k] = v.x; z[1][k] = v.y; z[2][k] = v.z; z[3][k] = v.w;
-    }
-  float p[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    stf::probabilities<0, KM>(z[j], K);
-    p[j] = z[j][0];
-#pragma unroll
-    for (int k = 1; k < KM; ++k)
-      if (k == channel) p[j] = z[j][k];
-  }
-  return make_float4(p[0], p[1], p[2], p[3]);
 }
 
 // dynamic LDS: the block's table, unsigned [2][bins + 1]

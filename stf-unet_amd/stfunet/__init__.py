@@ -12,8 +12,8 @@ from .loss import boundary_criterion, boundary_loss, criterion, signed_distance_
 from .optim import clip_grad_norm_  # noqa: F401
 from .predict import (boundary_metrics, boundary_metrics_3d, connected_components,  # noqa: F401
                       connected_components_3d, distance_transform_3d, distance_transform_sq, filter_components,
-                      filter_components_3d, flip_planes, image_metrics, lesion_metrics, lesion_metrics_3d, overlay,
-                      predict_masks, predict_tta,
+                      filter_components_3d, flip_planes, froc_curves, image_metrics, lesion_metrics,
+                      lesion_metrics_3d, lesion_scores, lesion_scores_3d, overlay, predict_masks, predict_tta,
                       predict_volumes, score_histogram, threshold_curves, tta_probabilities)
 from .resize import upsample_logits  # noqa: F401
 from .stf_lstm_unet import STFLSTMUNet  # noqa: F401
@@ -22,7 +22,7 @@ from .unet import UNet  # noqa: F401
 __all__ = ["STFLSTMUNet", "UNet", "WeightEMA", "boundary_criterion", "boundary_loss", "boundary_metrics",
            "boundary_metrics_3d", "clip_grad_norm_",
            "connected_components", "connected_components_3d", "criterion", "distance_transform_3d",
-           "distance_transform_sq", "filter_components", "filter_components_3d", "flip_planes", "image_metrics",
-           "lesion_metrics", "lesion_metrics_3d",
+           "distance_transform_sq", "filter_components", "filter_components_3d", "flip_planes", "froc_curves",
+           "image_metrics", "lesion_metrics", "lesion_metrics_3d", "lesion_scores", "lesion_scores_3d",
            "overlay", "predict", "predict_masks", "predict_tta", "predict_volumes", "score_histogram",
            "signed_distance_maps", "threshold_curves", "tta_probabilities", "upsample_logits"]

@@ -209,6 +209,11 @@ _SIGS = {
     "stf_lesion3d_metrics": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, c_int, ctypes.c_double, c_int, c_int64,
                                      P, P, P, P]),
     "stf_score_hist": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, P, c_int64, c_int64, c_int, P, P]),
+    "stf_froc_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "stf_froc": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_int64,
+                         c_int, P, P, P, P, P]),
+    "stf_froc3d": (c_int, [P, P, c_int, c_int, c_int, P, c_int, c_int, c_int, P, P, c_int, c_int, ctypes.c_double,
+                           c_int, c_int64, c_int, P, P, P, P, P]),
     "stf_boundary3d_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "stf_boundary3d_metrics": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, c_int64, P, P, P, P]),
     "stf_edt3d_sq": (c_int, [P, P, c_int, c_int, c_int, P, P, c_int, P, P, P, P]),

@@ -42,7 +42,14 @@ triple to cv2 as B, G, R.  The default colour (0, 255, 0) reads the same both wa
   (Dice / IoU per threshold and the best one), AUROC, average precision and the calibration table with
   its ECE; ``predict_tta(curves=True)`` and ``predict_volumes(curves=True)`` report them per image / case
 
-There is no CPU path: tensors on the host raise.
+* ``lesion_scores`` / ``lesion_scores_3d`` / ``froc_curves``  the lesion metrics swept over the confidence of
+  each predicted component: per candidate the largest score row of its voxels, per target lesion the
+  largest confidence among the matched candidates that touch it, the three-sided histogram of both
+  (the FROC passes of ``csrc/ccl.hip``) and, from it, lesion sensitivity against false findings per case
+  at every confidence; ``predict_tta(froc=True)`` and ``predict_volumes(froc=True)`` report them
+
+There is no CPU path: tensors on the host raise (``threshold_curves`` and ``froc_curves`` are torch ops and
+take a table on any device).
 """
 import numbers
 import os
@@ -833,13 +840,19 @@ def _batch_hist(outputs, targets, views, rule, channel, bins, curve_channel, ign
     probabilities and ``rule="threshold"`` planes as they are."""
     if isinstance(outputs, dict):
         outputs = outputs["out"]
-    if rule == "argmax":
-        source, plane = ("softmax" if views is None else "probs"), curve_channel
-    elif rule == "sigmoid":
-        source, plane = ("sigmoid", channel) if views is None else ("probs", 0)
-    else:
-        source, plane = "probs", channel
+    source, plane = _loop_score(views, rule, channel, curve_channel)
     return score_histogram(outputs, targets, source, plane, bins, None, ignore_index)
+
+
+def _loop_score(views, rule, channel, curve_channel):
+    """(source, plane) of the loops' score in what ``_batches`` yields: logits by ``rule`` (softmax of class
+    ``curve_channel``, or the sigmoid of the rule's own plane ``channel``), mean probabilities and
+    ``rule="threshold"`` planes as they are."""
+    if rule == "argmax":
+        return ("softmax" if views is None else "probs"), curve_channel
+    if rule == "sigmoid":
+        return ("sigmoid", channel) if views is None else ("probs", 0)
+    return "probs", channel
 
 
 def _curve_result(hist):
@@ -853,6 +866,198 @@ def _curve_result(hist):
     best, _ = _first_max(mean_dice)
     return dict(zip(CURVE_KEYS, (hist, pooled, per_case["auroc"], per_case["average_precision"], mean_dice,
                                  pooled["thresholds"][best])))
+
+
+FROC_RATES = (0.125, 0.25, 0.5, 1, 2, 4, 8)        # false findings per case of the LUNA16 performance metric
+FROC_KEYS = ("froc_hist", "froc", "lesion_scores")
+
+
+def _checked_scores(scores, shape, source, channel, bins):
+    """``scores`` of the FROC calls as ``[N, K, H, W]`` for a mask of ``shape`` with the checked ``channel``
+    and ``bins``: ``score_histogram``'s checks and messages."""
+    if isinstance(scores, dict):
+        scores = scores["out"]
+    if source not in SOURCES:
+        raise ValueError(f"unknown source {source!r} (one of {sorted(SOURCES)})")
+    if scores.dim() == 3:
+        scores = scores.unsqueeze(1)
+    if scores.dim() != 4:
+        raise ValueError(f"scores must be [N, K, H, W] or [N, H, W], not {tuple(scores.shape)}")
+    if not scores.dtype.is_floating_point:
+        raise ValueError(f"scores must be a floating-point tensor, not {scores.dtype}")
+    N, K, H, W = scores.shape
+    if not 1 <= K <= MAX_CLASSES:
+        raise ValueError(f"1..{MAX_CLASSES} planes are supported, not {K}")
+    if not _is_int(channel) or not 0 <= channel < K:
+        raise ValueError(f"channel {channel!r} is outside [0, {K})")
+    bins = _check_bins(bins)
+    if (N, H, W) != tuple(shape):
+        raise ValueError(f"scores {(N, H, W)} do not match the mask's {tuple(shape)}")
+    return scores, int(channel), bins
+
+
+def _froc(mask, scores, target, depths, source, channel, bins, connectivity, min_overlap, max_lesions, ignore_index):
+    """``stf_froc`` / ``stf_froc3d`` on a checked uint8 device mask and checked device scores: (summary int64
+    [V, 4], table int64 [V, 2, max_lesions, 3] or None, hist int64 [V, 3, bins + 1]), per image (``depths``
+    None) or per volume."""
+    N, H, W = mask.shape
+    K = scores.shape[1]
+    dev = mask.device
+    V = N if depths is None else len(depths)
+    summary = torch.empty((V, 4), dtype=torch.int64, device=dev)
+    table = torch.empty((V, 2, max_lesions, 3), dtype=torch.int64, device=dev) if max_lesions else None
+    hist = torch.empty((V, 3, bins + 1), dtype=torch.int64, device=dev)
+    if N:
+        target = target.detach().to(device=dev, dtype=torch.int64).contiguous()
+        scores = scores.detach().to(device=dev, dtype=torch.float32).contiguous()
+        before = (_p(mask), _p(scores), K, SOURCES[source], channel, _p(target), N, H, W)
+        after = (connectivity, min_overlap, max_lesions, _ignore(ignore_index), bins, _p(summary), _p(table), _p(hist))
+        with torch.cuda.device(dev):
+            scratch = scratch_words(load().stf_froc_scratch_bytes(N, H, W, V, bins), dev)
+            if depths is None:
+                call("stf_froc", *before, *after, _p(scratch), stream())
+            else:
+                host, starts = _starts(depths, dev)           # the call reads the host table before it returns
+                call("stf_froc3d", *before, _p(starts), host.data_ptr(), V, *after, _p(scratch), stream())
+    return summary, table, hist
+
+
+def _froc_result(summary, table, hist):
+    res = _lesion_result(summary, table)
+    res["froc_hist"] = hist
+    return res
+
+
+def lesion_scores(mask, scores, target, source="probs", channel=0, bins=256, connectivity=8, min_overlap=0.0,
+                  max_lesions=64, ignore_index=None):
+    """``lesion_metrics`` with a confidence for every predicted component and a detection score for every
+    target lesion, per image: what a FROC curve is made of (``froc_curves``).
+
+    ``mask``, ``target``, ``connectivity``, ``min_overlap``, ``max_lesions`` and ``ignore_index`` are
+    ``lesion_metrics``'; every component of the prediction side is a candidate.  ``scores`` (fp32
+    ``[B, K, H, W]`` or ``[B, H, W]`` on the device), ``source``, ``channel`` and ``bins`` are
+    ``score_histogram``'s: the score ``p`` of a pixel and its ``row(p)`` in ``0..bins``.  Then
+
+    * ``conf(c)`` = the largest ``row(p)`` over the pixels of candidate ``c``;
+    * a candidate is matched by ``lesion_metrics``' rule (``hit >= 1`` and ``float(hit) >= min_overlap *
+      float(area)``); every other candidate is a false finding;
+    * ``det(t)`` = the largest ``conf(c)`` over the matched candidates that share a pixel with lesion ``t``,
+      0 without one: a candidate that fails ``min_overlap`` lends nothing to the lesions it grazes.
+
+    Returns ``lesion_metrics``' dict (the same bits) with two differences: ``lesions`` is int64 ``[B, 2,
+    max_lesions, 3]``, row ``l - 1`` = (area, hit, score) of label ``l`` with score = ``det`` on side 0 (the
+    target) and ``conf`` on side 1 (the prediction); and ``froc_hist`` int64 ``[B, 3, bins + 1]`` is added:
+    side 0 counts the false findings by ``conf``, side 1 the target lesions by ``det`` (row 0: the lesions
+    no matched candidate reached), side 2 the matched candidates by ``conf``, so the sides sum to
+    ``n_pred - matched_pred``, ``n_target`` and ``matched_pred``.  Integers only: the same bits from run to
+    run; no host synchronisation."""
+    scores, channel, bins = _checked_scores(scores, mask.shape, source, channel, bins)
+    _check_target_shape(target, mask.shape)
+    _check_bhw(mask, "mask")
+    connectivity, _ = _check_components(connectivity)
+    min_overlap, max_lesions = _check_lesions(min_overlap, max_lesions)
+    mask = _checked_mask(mask, target, "lesion_scores")
+    _device_only(scores, "lesion_scores")
+    return _froc_result(*_froc(mask, scores, target, None, source, channel, bins, connectivity, min_overlap,
+                               max_lesions, ignore_index))
+
+
+def lesion_scores_3d(mask, scores, target, depths=None, source="probs", channel=0, bins=256, connectivity=26,
+                     min_overlap=0.0, max_lesions=64, ignore_index=None):
+    """``lesion_scores`` per volume (per case) instead of per image: ``mask``, ``scores`` and ``target`` are
+    stacks of slices cut into ``V = len(depths)`` volumes as in ``lesion_metrics_3d`` (connectivity 6, 18 or
+    26); every tensor of the result has ``V`` rows.  The same bits for a volume passed alone or inside a
+    stack."""
+    scores, channel, bins = _checked_scores(scores, mask.shape, source, channel, bins)
+    _check_target_shape(target, mask.shape)
+    N, H, W = _check_bhw(mask, "mask")
+    connectivity, _ = _check_components_3d(connectivity)
+    depths = _check_depths(depths, N)
+    min_overlap, max_lesions = _check_lesions(min_overlap, max_lesions)
+    mask = _checked_mask(mask, target, "lesion_scores_3d")
+    _device_only(scores, "lesion_scores_3d")
+    return _froc_result(*_froc(mask, scores, target, depths, source, channel, bins, connectivity, min_overlap,
+                               max_lesions, ignore_index))
+
+
+def froc_curves(hist, cases=None, rates=FROC_RATES):
+    """The FROC curve of a confidence histogram ``hist`` (``froc_hist`` of ``lesion_scores``): ``[3, bins + 1]``
+    integers of ``cases`` cases (default 1), or ``[V, 3, bins + 1]``, which is summed over its ``V`` rows first
+    (``cases`` default ``V``).  A dict of tensors on ``hist``'s device, which may be the host -- torch ops in
+    int64 / float64, no host synchronisation.
+
+    With ``X_j`` the sum of a side's rows above ``j``, ``j = 0..bins`` -- the candidates and lesions whose
+    confidence exceeds ``j / bins``; point ``j`` thresholds the confidences of a fixed candidate set, it does
+    not label the mask again:
+
+    * ``thresholds`` ``[bins + 1]`` = ``j / bins``; int64 ``detected`` = ``X_j`` of side 1, ``false_findings`` of
+      side 0, ``matched`` of side 2, and ``n_lesions``, all rows of side 1
+    * ``sensitivity`` = ``detected / n_lesions`` (NaN without lesions), ``fp_per_case`` = ``false_findings /
+      cases``, ``precision`` = ``matched / (matched + false_findings)``, 1 where nothing is predicted
+    * ``sensitivity_at`` ``[len(rates)]``: for a rate ``r`` of false findings per case, ``sensitivity[j*]`` at the
+      smallest ``j`` with ``float(false_findings[j]) <= r * float(cases)`` (``j = bins`` always qualifies): a
+      step function, nothing is interpolated; and ``cpm``, their mean -- at the default rates the LUNA16
+      competition performance metric.  NaN without lesions."""
+    if hist.dim() not in (2, 3) or hist.shape[-2] != 3 or hist.shape[-1] < 3:
+        raise ValueError(f"hist must be [3, bins + 1] or [V, 3, bins + 1], not {tuple(hist.shape)}")
+    if hist.dtype.is_floating_point or hist.dtype.is_complex or hist.dtype == torch.bool:
+        raise ValueError(f"hist must be an integer tensor, not {hist.dtype}")
+    bins = _check_bins(hist.shape[-1] - 1)
+    pooled = hist.dim() == 3
+    if cases is None:
+        cases = hist.shape[0] if pooled else 1
+    if not _is_real(cases) or not cases > 0:
+        raise ValueError(f"cases must be a number > 0, not {cases!r}")
+    try:
+        rates = [r for r in rates]
+    except TypeError:
+        raise ValueError(f"rates must be a sequence of numbers >= 0, not {rates!r}") from None
+    if not rates or not all(_is_real(r) and r >= 0 for r in rates):
+        raise ValueError(f"rates must be a non-empty sequence of numbers >= 0, not {rates!r}")
+    hist = hist.to(torch.int64)
+    if pooled:
+        hist = hist.sum(0)
+    f64 = torch.float64
+    total = hist.sum(-1, keepdim=True)                        # [3, 1]
+    false, detected, matched = (total - hist.cumsum(-1)).unbind(0)   # rows > j
+    n_lesions = total[1, 0]
+    sensitivity = detected.to(f64) / n_lesions.to(f64)        # 0 / 0 = NaN
+    predicted = (matched + false).to(f64)
+    precision = torch.where(predicted > 0, matched.to(f64) / predicted, 1.0)
+    limit = torch.tensor([float(r) for r in rates], dtype=f64, device=hist.device) * float(cases)
+    index = torch.arange(bins + 1, device=hist.device)
+    first = torch.where(false.to(f64)[None, :] <= limit[:, None], index, bins).min(-1).values
+    sensitivity_at = sensitivity[first]
+    return {"thresholds": index.to(f64) / bins, "detected": detected, "false_findings": false, "matched": matched,
+            "n_lesions": n_lesions, "sensitivity": sensitivity, "fp_per_case": false.to(f64) / float(cases),
+            "precision": precision, "sensitivity_at": sensitivity_at, "cpm": sensitivity_at.mean()}
+
+
+def _check_froc(froc, froc_bins, froc_overlap, curve_channel):
+    """The loops' checked FROC options: (on, bins, overlap); nothing is looked at while it is off."""
+    if not froc:
+        return False, froc_bins, froc_overlap
+    if not _is_int(curve_channel) or curve_channel < 0:
+        raise ValueError(f"curve_channel must be a class id >= 0, not {curve_channel!r}")
+    return True, _check_bins(froc_bins), _check_lesions(froc_overlap)[0]
+
+
+def _batch_froc(mask, outputs, targets, depths, views, rule, channel, curve_channel, bins, connectivity, overlap,
+                ignore_index):
+    """The loops' one ``stf_froc`` / ``stf_froc3d`` call per batch / flush: the reported mask against the score
+    ``curves=True`` uses (``_loop_score``), the table at ``lesion_scores``' 64 rows."""
+    source, plane = _loop_score(views, rule, channel, curve_channel)
+    scores, plane, bins = _checked_scores(outputs, mask.shape, source, plane, bins)
+    return _froc(mask, scores, targets, depths, source, plane, bins, connectivity, overlap, 64, ignore_index)
+
+
+def _froc_loop_result(parts):
+    """The FROC keys of the predict loops from the per-batch / per-flush (summary, table, hist) (None without
+    targets): the tables per image / case and the curve of the pooled one, one case per row."""
+    if not parts:
+        return dict.fromkeys(FROC_KEYS)
+    hist = torch.cat([p[2] for p in parts])
+    return dict(zip(FROC_KEYS, (hist, froc_curves(hist), torch.cat([p[1] for p in parts]))))
 
 
 def overlay(frames, mask, color=(0, 255, 0), alpha=0.5, paint=1):
@@ -1057,10 +1262,12 @@ def _predict(model, data_loader, device, views, keep_probs, rule="argmax", chann
 def _predict_loop(model, data_loader, device, views, keep_probs, lesions, lesion_overlap, rule="argmax", channel=0,
                   threshold=0.5, ignore_index=None, output_dir=None, prefix="unet", color=(0, 255, 0), alpha=0.5,
                   paint=1, keep_masks=False, boundary=False, spacing=1.0, keep_largest=False, min_size=0,
-                  connectivity=8, curves=False, curve_bins=256, curve_channel=1):
-    """``_predict``, the lesion-level figures and the score histograms (``predict_tta`` hands ``lesions`` /
-    ``lesion_overlap`` and the three ``curve`` options over)."""
+                  connectivity=8, curves=False, curve_bins=256, curve_channel=1, froc=False, froc_bins=256,
+                  froc_overlap=0.0):
+    """``_predict``, the lesion-level figures, the score histograms and the FROC tables (``predict_tta`` hands
+    ``lesions`` / ``lesion_overlap``, the three ``curve`` options and the three ``froc`` options over)."""
     batches = _batches(model, data_loader, device, views, rule, channel, threshold, ignore_index)
+    froc, froc_bins, froc_overlap = _check_froc(froc, froc_bins, froc_overlap, curve_channel)
     curves, curve_bins, curve_channel = _check_curves(curves, curve_bins, curve_channel)
     color = _check_paint(color, alpha, paint)
     if boundary:
@@ -1074,7 +1281,7 @@ def _predict_loop(model, data_loader, device, views, keep_probs, lesions, lesion
         os.makedirs(output_dir, exist_ok=True)
     model.eval()
     all_counts, all_boundary, all_num, all_lesions, masks, probs, idx = [], [], [], [], [], [], 0
-    all_hist = []
+    all_hist, all_froc = [], []
     with torch.no_grad():
         for inputs, targets, mask, counts, outputs in batches:
             if keep_probs:
@@ -1092,6 +1299,9 @@ def _predict_loop(model, data_loader, device, views, keep_probs, lesions, lesion
                 if lesions:
                     all_lesions.append(_lesions(mask, targets, None, connectivity, lesion_overlap, 0,
                                                 ignore_index)[0])
+                if froc:                                   # the reported mask against the raw score
+                    all_froc.append(_batch_froc(mask, outputs, targets, None, views, rule, channel, curve_channel,
+                                                froc_bins, connectivity, froc_overlap, ignore_index))
             if output_dir is not None:
                 pics = overlay(shown_frame(inputs), mask, color, alpha, paint).cpu().numpy()
                 for j, pic in enumerate(pics):
@@ -1115,6 +1325,8 @@ def _predict_loop(model, data_loader, device, views, keep_probs, lesions, lesion
         res.update(_pooled_lesions(all_lesions, "image"))
     if curves:
         res.update(_curve_result(torch.cat(all_hist) if all_hist else None))
+    if froc:
+        res.update(_froc_loop_result(all_froc))
     if keep_masks:
         res["masks"] = masks
     if keep_probs:
@@ -1152,7 +1364,7 @@ def predict(model, data_loader, device, rule="argmax", channel=0, threshold=0.5,
 def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argmax", channel=0, threshold=0.5,
                     ignore_index=None, keep_largest=False, min_size=0, connectivity=26, keep_masks=False,
                     boundary=False, spacing=1.0, lesions=False, lesion_overlap=0.0, curves=False, curve_bins=256,
-                    curve_channel=1):
+                    curve_channel=1, froc=False, froc_bins=256, froc_overlap=0.0):
     """The inference loop over volumes: the loader yields slices in volume order -- ``depths[0]``
     slices of volume 0, then volume 1 and so on (``stfunet.dataset.volume_order`` puts a
     ``DriveDataset`` into that order); batches may straddle volume boundaries.
@@ -1195,6 +1407,13 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
     keys of ``predict_tta``'s ``curves=True``, per case instead of per image.  Without the flag nothing of
     this runs and the result has no such key.
 
+    ``froc=True`` adds, when targets came, ``lesion_scores_3d`` of every volume's mask (after the component
+    filter, when one is on) against its target and the score ``curves=True`` uses (``curve_channel``), at
+    ``connectivity``, ``bins=froc_bins`` and ``min_overlap=froc_overlap``, one ``stf_froc3d`` call per flush: the
+    keys of ``predict_tta``'s ``froc=True``, per case instead of per image.  The slices' scores are held with
+    their masks until the volume is complete.  Without the flag nothing of this runs and the result has no
+    such key.
+
     Not here: overlays (``keep_masks=True`` and ``overlay`` cover them) and anisotropic connectivity."""
     batches = _batches(model, data_loader, device, tta, rule, channel, threshold, ignore_index)
     connectivity, min_size = _check_components_3d(connectivity, min_size)
@@ -1206,6 +1425,7 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
     rows = _check_spacing_3d(spacing, V) if boundary else None
     if lesions:
         lesion_overlap, _ = _check_lesions(lesion_overlap)
+    froc, froc_bins, froc_overlap = _check_froc(froc, froc_bins, froc_overlap, curve_channel)
     curves, curve_bins, curve_channel = _check_curves(curves, curve_bins, curve_channel)
     views = parse_views(tta)
     model.eval()
@@ -1213,6 +1433,7 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
     vol_counts = None                               # options off: int64 [V, 3], summed as the slices come
     vol_hist = None                                 # curves: int64 [V, 2, bins + 1], summed as the slices come
     held_masks, held_targets, held, done = [], [], 0, 0   # options on: slices of volumes not yet complete
+    held_scores, all_froc = [], []                  # froc: the slices' scores, held like their masks
     all_counts, all_num, all_boundary, all_lesions, masks, idx, with_targets = [], [], [], [], [], 0, None
     with torch.no_grad():
         for _, targets, mask, counts, outputs in batches:
@@ -1235,10 +1456,12 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
                     vol_counts.index_add_(0, slice_volume[idx:idx + B], counts)
                 if keep_masks:
                     masks.append(mask)
-            if components or ((boundary or lesions) and targets is not None):
+            if components or ((boundary or lesions or froc) and targets is not None):
                 held_masks.append(mask)
                 if targets is not None:
                     held_targets.append(targets)
+                    if froc:
+                        held_scores.append(outputs["out"] if isinstance(outputs, dict) else outputs)
                 held += B
                 k = take = 0                         # the volumes this batch completes, and their slices
                 while done + k < V and take + depths[done + k] <= held:
@@ -1264,6 +1487,12 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
                     if lesions and t is not None:
                         all_lesions.append(_lesions(out.contiguous(), t[:take], depths[done:done + k], connectivity,
                                                     lesion_overlap, 0, ignore_index)[0])
+                    if froc and t is not None:
+                        sc = torch.cat(held_scores) if len(held_scores) > 1 else held_scores[0]
+                        all_froc.append(_batch_froc(out.contiguous(), sc[:take], t[:take], depths[done:done + k], views,
+                                                    rule, channel, curve_channel, froc_bins, connectivity,
+                                                    froc_overlap, ignore_index))
+                        held_scores = [sc[take:]] if take < held else []
                     held_masks = [m[take:]] if take < held else []
                     held_targets = [t[take:]] if t is not None and take < held else []
                     held -= take
@@ -1292,6 +1521,8 @@ def predict_volumes(model, data_loader, device, depths, *, tta=None, rule="argma
         res.update(_pooled_lesions(all_lesions, "case"))
     if curves:
         res.update(_curve_result(vol_hist))
+    if froc:
+        res.update(_froc_loop_result(all_froc))
     if keep_masks:
         res["masks"] = masks
     return res
@@ -1331,13 +1562,22 @@ def predict_tta(model, data_loader, device, tta=True, keep_probs=False, **option
     histogram pooled over all images, ``case_auroc`` / ``case_average_precision`` per image (NaN where a
     side is empty), ``mean_case_dice_curve`` = the mean over images of each image's Dice at every
     threshold and ``best_case_threshold``, its first maximum; all None without targets.  Device tensors,
-    no host synchronisation; without the flag nothing of this runs and the result has no such key."""
+    no host synchronisation; without the flag nothing of this runs and the result has no such key.
+
+    ``froc=True`` (with ``froc_bins=256`` and ``froc_overlap=0.0``; with or without ``tta``) adds, when targets
+    came, ``lesion_scores`` of every reported mask (after ``keep_largest`` / ``min_size``) against its target and
+    the score ``curves=True`` uses (``curve_channel``; the mean probability under ``tta``), at ``connectivity``,
+    ``bins=froc_bins`` and ``min_overlap=froc_overlap``, one ``stf_froc`` call per batch.  The result gains
+    ``froc_hist`` int64 ``[num, 3, froc_bins + 1]`` per image, ``froc`` = ``froc_curves`` of the table pooled over
+    all images with ``cases`` = their number, and ``lesion_scores`` int64 ``[num, 2, 64, 3]``, the (area, hit,
+    score) tables; all None without targets.  Device tensors, no host synchronisation; without the flag
+    nothing of this runs and the result has no such key."""
     views = parse_views(tta)
     if keep_probs and views is None:
         raise ValueError("keep_probs needs test-time augmentation (tta)")
     lesions, lesion_overlap = options.pop("lesions", False), options.pop("lesion_overlap", 0.0)
-    if views is None and not lesions and not options.get("curves"):
-        for k in ("curves", "curve_bins", "curve_channel"):
+    if views is None and not lesions and not options.get("curves") and not options.get("froc"):
+        for k in ("curves", "curve_bins", "curve_channel", "froc", "froc_bins", "froc_overlap"):
             options.pop(k, None)
         return predict(model, data_loader, device, **options)
     return _predict_loop(model, data_loader, device, views, bool(keep_probs), lesions, lesion_overlap, **options)

@@ -59,6 +59,11 @@ had to do at least without it, two ``connected_components_3d`` calls (one per si
 still to be copied and looped over on the host), in the same rounds; ``form`` is one elementwise pass
 over the same tensors for scale.  Prints one JSON line.
 
+``--froc`` measures lesion confidence and FROC (csrc/ccl.hip, the FROC passes) on the ``--lesions`` inputs with
+trained-like scores whose cut at 0.5 is the mask (97 % of the voxels at 0 or 1), against its two yardsticks in
+the same interleaved rounds: ``lesion_metrics_3d`` on the same masks and ``score_histogram`` at 256 bins on the
+same scores; the ratio reported is froc / (lesions + score_hist).
+
 ``--curves`` measures the score histogram (csrc/curves.hip) at the same shape against its yardstick,
 ``stf_predict_threshold`` with targets on the same tensors (the same 12 bytes read per pixel, and a
 mask byte written), both through the C entry points on preallocated outputs and interleaved in every
@@ -90,6 +95,7 @@ ap.add_argument("--components", action="store_true", help="measure the connected
 ap.add_argument("--components3d", action="store_true", help="measure the volume-level component kernels instead")
 ap.add_argument("--boundary3d", action="store_true", help="measure the per-volume boundary metrics instead")
 ap.add_argument("--lesions", action="store_true", help="measure the lesion-level detection metrics instead")
+ap.add_argument("--froc", action="store_true", help="measure lesion confidence and FROC instead")
 ap.add_argument("--tta", action="store_true", help="measure the test-time-augmentation kernels instead")
 ap.add_argument("--curves", action="store_true", help="measure the score histogram and the curves instead")
 ap.add_argument("--host-images", type=int, default=8, help="images per regime of the scipy host timing")
@@ -458,6 +464,51 @@ if args.lesions:
         "mean_n_target": {k: float(r["n_target"].double().mean()) for k, r in res.items()},
         "mean_n_pred": {k: float(r["n_pred"].double().mean()) for k, r in res.items()},
         "pooled_sensitivity": {k: float(r["matched_target"].sum() / r["n_target"].sum()) for k, r in res.items()},
+    }))
+    sys.exit(0)
+
+if args.froc:
+    from stfunet import _lib, froc_curves, lesion_metrics_3d, lesion_scores_3d, score_histogram
+    volumes = [v for v in (1, 8) if B % v == 0]
+    g = torch.Generator().manual_seed(5)
+    data = {}
+    for k, (m, _, c) in component_masks().items():
+        t = torch.roll(m, (3, 3), (1, 2)).long()                 # the --lesions targets
+        # trained-like scores whose cut at 0.5 is the mask: 97 % of the voxels at 0 or 1, the rest spread over their half
+        u, sat = torch.rand(B, H, W, generator=g), torch.rand(B, H, W, generator=g) < 0.97
+        s = torch.where(m != 0, torch.where(sat, 1.0, 0.5 + 0.5 * u.clamp_min(1e-3)), torch.where(sat, 0.0, 0.5 * u))
+        assert bool(((s > 0.5) == (m != 0)).all())
+        data[k] = (m.cuda(), s.float().cuda(), t.cuda(), 26 if c == 8 else 6)
+    legs = []
+    for k, (m, s, t, c3) in data.items():
+        legs.append((f"score_hist_{k}", lambda s=s, t=t: score_histogram(s, t, "probs", 0, 256)))
+        for v in volumes:
+            d = [B // v] * v
+            legs += [(f"lesions_V{v}_{k}", lambda m=m, t=t, d=d, c3=c3: lesion_metrics_3d(m, t, d, c3)),
+                     (f"froc_V{v}_{k}", lambda m=m, s=s, t=t, d=d, c3=c3: lesion_scores_3d(m, s, t, d, "probs", 0, 256, c3))]
+    for _, fn in legs:
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    us = {name: [] for name, _ in legs}
+    for _ in range(args.rounds):
+        for name, fn in legs:
+            us[name].append(timed(fn, args.iters))
+    med = {k: statistics.median(v) for k, v in us.items()}
+    res = {f"V{v}_{k}": lesion_scores_3d(m, s, t, [B // v] * v, "probs", 0, 256, c3)
+           for k, (m, s, t, c3) in data.items() for v in volumes}
+    print(json.dumps({
+        "tool": "bench_predict", "leg": "froc", "shape": [B, H, W], "volumes": volumes, "bins": 256,
+        "rounds": args.rounds, "iters": args.iters,
+        "scratch_bytes": {f"V{v}": int(_lib.load().stf_froc_scratch_bytes(B, H, W, v, 256)) for v in volumes},
+        "us_per_call": {k: round(v, 1) for k, v in med.items()},
+        "us_per_call_min_max": {k: [round(min(v), 1), round(max(v), 1)] for k, v in us.items()},
+        "froc_over_lesions_plus_score_hist": {
+            f"V{v}_{k}": round(med[f"froc_V{v}_{k}"] / (med[f"lesions_V{v}_{k}"] + med[f"score_hist_{k}"]), 3)
+            for k in data for v in volumes},
+        "mean_n_target": {k: float(r["n_target"].double().mean()) for k, r in res.items()},
+        "mean_n_pred": {k: float(r["n_pred"].double().mean()) for k, r in res.items()},
+        "cpm": {k: float(froc_curves(r["froc_hist"])["cpm"]) for k, r in res.items()},
     }))
     sys.exit(0)
 
