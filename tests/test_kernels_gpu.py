@@ -482,6 +482,11 @@ def test_head_and_loss():
     assert rel(dw.view(K, C), wr.grad) < 1e-4
     assert rel(dbias, br.grad) < 1e-4
     assert rel(g.dense(), gref) < 1e-2
+    # the BN-backward partial sums reduced in the same pass (per element: tests/test_tail_parity_gpu.py)
+    xhat = (y - st.mean.view(1, -1, 1, 1)) * st.invstd.view(1, -1, 1, 1)
+    part = bnp.view(tiles, 2, C).double().sum(0)
+    assert rel(part[0], gref.double().sum((0, 2, 3))) < 1e-4
+    assert rel(part[1], (gref * xhat).double().sum((0, 2, 3))) < 1e-4
 
 
 def test_loss_saturated_empty_set():
